@@ -2,7 +2,14 @@
 """Headline benchmark: device-resident N-client FedAvg fp32 reduction (aggregated GB/s).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5|c4] [--variant V]
-                    [--sweep] [--no-cpu-baseline]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline]] [--sweep]
+
+A plain run sets up, warms up, times the K steps, writes the last step's
+outputs with --dump-outputs, and prints the result line.  --full adds what
+takes runs of its own after the timed steps: the CPU baselines and their
+bit-for-bit check of the GPU output, the read-sweep ceiling and the committed
+PMC traffic of the roofline block, and the gather check of a run under a
+process group (those fields are null in a plain run's line).
 
 One "step" = one aggregation round over one batch already resident in HBM:
 the fa_fedavg_f32 fold of [N_clients x P] -> [P] (stall-aware for c5, bf16 for
@@ -21,9 +28,10 @@ WORLD_SIZE.  Under torch.distributed.run the process group is initialised even
 at WORLD_SIZE 1 (nccl = RCCL), so the gather path runs on real RCCL streams.
 
 Inputs: integer-exact synthetic generator (fedlesscan_amd/synth.py), generated
-directly in HBM by fa_synth_*; random-init, no dataset.  Rank 0 at N=1 also
-times the CPU oracle on a bounded column sample of the same workload and
-checks the GPU output on that sample bit-for-bit.
+directly in HBM by fa_synth_*; random-init, no dataset: the same arguments
+give the same inputs in every run.  With --full, rank 0 also times the CPU
+oracle on a bounded column sample of the same workload and checks the GPU
+output on that sample bit-for-bit.
 """
 from __future__ import annotations
 
@@ -48,6 +56,8 @@ from fedlesscan_amd.sharding import ALIGN, DEFAULT_TAIL, SlotLayout, gather_into
 from fedlesscan_amd.sharding import fold_stream as sharding_fold_stream  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
+DUMP_BUDGET = 60_000_000  # bytes of float32 values that one --dump-outputs writes, all its files together
+DUMP_SEED = 0x0FEDA76
 
 CONFIGS = {
     # name: (clients, params, dtype, scored, seed, card_hi, scaling, description)
@@ -84,9 +94,17 @@ def parse():
     ap.add_argument("--variants", default="", help="with --sweep: comma-separated variant numbers only")
     ap.add_argument("--splitn", action="store_true",
                     help="time the opt-in split-client fold (fa_fedavg_f32_splitn, NOT bit-exact) instead")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the CPU baselines "
+                         "(and their bit-for-bit check of the GPU output), the read-sweep ceiling and the committed "
+                         "PMC traffic of the roofline block, the gather check under a process group")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the arrays its caller "
+                         "receives) as DIR/<name>.npy in float32; more than DUMP_BUDGET bytes in all are cut to a "
+                         "fixed, seeded sample of each array (sample_index)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-full-lean", action="store_true",
-                    help="skip the full-size one-core reference timing (cpu_baseline.full_lean)")
+                    help="with --full: skip the full-size one-core reference timing (cpu_baseline.full_lean)")
     ap.add_argument("--unpadded", action="store_true",
                     help="row pitch = the model size exactly (experiments: odd sizes give rows that are not 16-B "
                          "aligned, as a torch.stack of such a model)")
@@ -130,7 +148,10 @@ def parse():
     ap.add_argument("--tail-steps", type=int, default=None,
                     help="rounds over which the slots shrink geometrically to --tail (2 with --tail 0.25 and 4 "
                          "rounds: shares 1, 1, 0.5, 0.25)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port() -> int:
@@ -406,6 +427,34 @@ def cpu_full_lean(wl: Workload):
             "impl": "oracle.fedavg_stacked: the reference op order over the full workload with one [P] product "
                     "temporary (numpy ufuncs, single-threaded)",
             "d2h_s": round(d2h_s, 2), "bit_exact_vs_gpu_all_columns": exact}
+
+
+def sample_index(n: int, keep: int, seed: int = DUMP_SEED) -> np.ndarray:
+    """`keep` increasing positions below n, one drawn from each of `keep` equal
+    strata: a function of (n, keep, seed) alone, so two runs (or two builds)
+    with the same arguments sample the same elements."""
+    edges = (np.arange(keep + 1, dtype=np.int64) * n) // keep
+    u = np.random.default_rng(seed).random(keep)
+    return edges[:-1] + (u * (edges[1:] - edges[:-1])).astype(np.int64)
+
+
+def dump_outputs(dirname: str, arrays: dict) -> dict:
+    """Write each 1-D device tensor as dirname/<name>.npy in float32 (fp32 and
+    bf16 values both convert exactly).  When all of them together exceed
+    DUMP_BUDGET bytes, every array is cut by the same factor to the elements
+    sample_index picks.  Returns what was written, for the result line."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values()) * 4
+    wrote = {}
+    for name, t in arrays.items():
+        n = t.numel()
+        keep = n if total <= DUMP_BUDGET else max(1, n * DUMP_BUDGET // total)
+        if keep < n:
+            t = t[torch.from_numpy(sample_index(n, keep)).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.to(torch.float32).cpu().numpy())
+        wrote[name] = {"elements": keep, "of": n,
+                       "sample": None if keep == n else f"sample_index({n}, {keep}, seed={DUMP_SEED})"}
+    return wrote
 
 
 def read_traffic(config: str):
@@ -720,17 +769,30 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, before any check below
+        # writes the buffers again: the model every rank holds after the
+        # exchange, or one GPU's fold result (padding columns left out)
+        if dist_on:
+            arrays = {"model": full[:wl.P_total]}
+        else:
+            arrays = {"model": wl.out[:wl.P]}
+            if wl.out_bf16 is not None:
+                arrays["model_bf16"] = wl.out_bf16[:wl.P]
+        dumped = dump_outputs(args.dump_outputs, arrays)
     if product:
         evs, agg.trace = agg.trace, None
         # the form the timed calls ran: one fold launch per call, or one per round
         one_launch = rounds > 1 and all(len(folds) == 1 for folds, _ in evs)
+    if product and args.full:
         # this rank's own slots folded by the per-round product launches: the
         # gather check's and the CPU baseline's reference for the product's model
         for k in range(rounds):
             wl.launch(0, k)
         torch.cuda.synchronize()
     gather_ok = None
-    if px is not None:
+    if args.full and px is not None:
         # the whole model the peer copy reassembled must equal an RCCL step's, bit for bit
         peer_full = full.clone()
         full.zero_()
@@ -741,7 +803,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         gather_ok = bool(t.item())
         del peer_full
-    elif dist_on:
+    elif args.full and dist_on:
         # the whole reassembled model: my slots in my copy are my fold output,
         # bit for bit, and every rank's copy is the same model (two position-
         # weighted digests of its bits agree on all ranks), so every rank's
@@ -795,19 +857,21 @@ def main():
 
     # streaming-read ceiling over the same HBM bytes (contiguous, no fold)
     # byte-level sweep: bf16 input is read as the same bytes viewed as fp32 quads
-    nfl = wl.N * wl.P * wl.X.element_size() // 4
-    sink = torch.empty(8192, dtype=torch.float32, device=dev)
-    ts = []
-    for k in range(max(3, min(args.steps, 10)) + 2):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        _lib.check(B.fa_read_sweep_f32(wl.X.data_ptr(), nfl - nfl % 4, sink.data_ptr(), 8192,
-                                       stream.cuda_stream), "read_sweep", bench=True)
-        e1.record(stream)
-        e1.synchronize()
-        if k >= 2:
-            ts.append(e0.elapsed_time(e1))
-    ceiling = (nfl - nfl % 4) * 4 / (sorted(ts)[len(ts) // 2] * 1e-3) / 1e9
+    ceiling = None
+    if args.full:
+        nfl = wl.N * wl.P * wl.X.element_size() // 4
+        sink = torch.empty(8192, dtype=torch.float32, device=dev)
+        ts = []
+        for k in range(max(3, min(args.steps, 10)) + 2):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            _lib.check(B.fa_read_sweep_f32(wl.X.data_ptr(), nfl - nfl % 4, sink.data_ptr(), 8192,
+                                           stream.cuda_stream), "read_sweep", bench=True)
+            e1.record(stream)
+            e1.synchronize()
+            if k >= 2:
+                ts.append(e0.elapsed_time(e1))
+        ceiling = (nfl - nfl % 4) * 4 / (sorted(ts)[len(ts) // 2] * 1e-3) / 1e9
 
     tb = torch.tensor([float(wl.bytes)], dtype=torch.float64, device=dev)
     if dist_on:
@@ -816,8 +880,8 @@ def main():
     value = total_bytes / elapsed / 1e9
     achieved = wl.bytes / (kern_avg * 1e-3) / 1e9
     # the committed PMC pass measured exactly this launch: the unmodified config, one fold per step
-    traffic, traffic_src = (read_traffic(args.config) if not (args.clients or args.params) and rounds == 1
-                            else (None, None))
+    traffic, traffic_src = (read_traffic(args.config) if args.full and not (args.clients or args.params)
+                            and rounds == 1 else (None, None))
     if traffic is not None and wl.dtype == "f32" and args.variant == 0:
         # the committed pass measured the policy's form; another measured choice is another kernel
         form = L.fa_fold_form(1, wl.N, lay.width(0), wl.ldx, 1 if wl.scored else 0, stream.cuda_stream).decode()
@@ -826,10 +890,10 @@ def main():
             traffic, traffic_src = None, f"{traffic_src}: measured form {pol}, this run took {form}"
     devices = rank_devices(dev)
     cpu = None
-    # the CPU baseline runs on rank 0 at every world size, after the timed
-    # region (the other ranks wait at the barrier below), so every line -- the
-    # N-GPU ones included -- carries the reference timed on the same host
-    if rank == 0 and not args.no_cpu_baseline:
+    # --full: the CPU baseline runs on rank 0 at every world size, after the
+    # timed region (the other ranks wait at the barrier below), so every such
+    # line -- the N-GPU ones included -- carries the reference timed on the same host
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(wl, args.cpu_cols, args.cpu_reps)
         except Exception as e:  # the baseline must never hide the GPU result
@@ -907,12 +971,14 @@ def main():
                 "traffic": traffic,
                 "traffic_source": traffic_src,
                 "kernel_ms_avg": round(kern_avg, 4),
-                "read_sweep_ceiling": round(ceiling, 1),
-                "frac_of_read_ceiling": round(achieved / ceiling, 4),
+                "read_sweep_ceiling": round(ceiling, 1) if ceiling else None,
+                "frac_of_read_ceiling": round(achieved / ceiling, 4) if ceiling else None,
                 "bytes_per_launch": wl.bytes,
             },
+            "full": args.full,
             "cpu_baseline": cpu,
             "gather_check": gather_ok,
+            "outputs_dumped": dumped,
             # the ranks that actually ran: torch.distributed's world and each rank's GPU
             "dist": {"backend": backend, "world_size": dist.get_world_size() if dist_on else 1,
                      "launcher": ("in-process one-rank group (--rccl-world1)" if args.rccl_world1 else

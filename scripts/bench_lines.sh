@@ -9,7 +9,7 @@ OUT=${OUT:-gpurun_out/benches}
 mkdir -p "$OUT"
 run() {  # name, seconds, args...
   local name=$1 secs=$2; shift 2
-  timeout -k 10 "$secs" python bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || exit $?
+  timeout -k 10 "$secs" python bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || exit $?
   python3 - "$OUT/$name.json" "$name" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

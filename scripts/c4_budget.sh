@@ -15,7 +15,7 @@ for r in 1 2 4 8; do
   port=$((port + 1))
   timeout -k 10 200 python -m torch.distributed.run --nnodes 1 --nproc-per-node 1 --master-addr 127.0.0.1 \
     --master-port $port bench.py --gpus 1 --config c4 --params 12500000 --rounds $r --steps 30 --warmup 5 \
-    --no-cpu-baseline > "$OUT/rounds$r.json" 2> "$OUT/rounds$r.err" || exit $?
+    --full --no-cpu-baseline > "$OUT/rounds$r.json" 2> "$OUT/rounds$r.err" || exit $?
   echo "rounds $r: $(python3 -c "import json; d=json.load(open('$OUT/rounds$r.json')); print('fold_ms', d['fold_ms'], 'exposed', d['gather_exposed_ms'], 'ms_per_step', d['ms_per_step'], 'gather_check', d['gather_check'])")"
 done
 for p in 12500000 6250000 3125000 1562500; do

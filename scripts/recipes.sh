@@ -33,7 +33,7 @@ case "$recipe" in
   gpu_suite)
     steps=("pytest_gpu:1100:$T -m gpu tests" "smoke:200:python3 -c 'import __graft_entry__ as g; g.smoke()'") ;;
   bench)
-    steps=("bench_default:500:python3 bench.py") ;;
+    steps=("bench_default:500:python3 bench.py --full") ;;
   bench_lines)
     steps=("bench_lines:1100:scripts/bench_lines.sh") ;;
   prof_c3)
@@ -77,7 +77,7 @@ case "$recipe" in
            "c4_rank_perround:300:python3 bench.py --rccl-world1 $C4R --per-round-launches") ;;
   final)
     steps=("pytest_gpu:1100:$T -m gpu tests" "smoke:200:python3 -c 'import __graft_entry__ as g; g.smoke()'"
-           "bench_default:500:python3 bench.py" "prof_c3:900:scripts/profile_c3.sh $TAG $COMMIT") ;;
+           "bench_default:500:python3 bench.py --full" "prof_c3:900:scripts/profile_c3.sh $TAG $COMMIT") ;;
   step_alone)  # the one launch's cost while it runs alone: fully static steps, one round
     steps=("xi_alone4:300:$XI --config c4 --blocks '' --step-forms product,bf16_step_static_u8c4"
            "xi_alone4_forced:300:$XI --config c4 --blocks '' --forms bf16_bands4_u8c4,bf16_bands4_u8c2"

@@ -130,7 +130,8 @@ def test_bench_times_the_shipped_class(config, impl, extra):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     params = "2000000" if config == "c4" else "500000"
     cmd = [sys.executable, os.path.join(repo, "bench.py"), "--rccl-world1", "--config", config, "--params", params,
-           "--clients", "64", "--steps", "3", "--warmup", "5", "--no-cpu-baseline", "--step-impl", impl, *extra]
+           "--clients", "64", "--steps", "3", "--warmup", "5", "--full", "--no-cpu-baseline", "--step-impl", impl,
+           *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
