@@ -27,7 +27,7 @@ BENCH_LIB_PATH = os.path.join(PKG, "_native", "libfedavg_hip_bench.so")
 HOSTFAST_PATH = os.path.join(PKG, "_native", "_hostfast" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
 HEADER = os.path.join(REPO, "include", "fedavg_hip.h")
 BENCH_HEADER = os.path.join(REPO, "include", "fedavg_hip_bench.h")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 FA_OK, FA_ERR_ARG, FA_ERR_NO_CLIENTS, FA_ERR_SHAPE, FA_ERR_HIP = range(5)
 
@@ -53,6 +53,7 @@ _PROTOS = {
     "fa_accumulate_f32": (_int, [_vp, _vp, _f32, _f32, _int, _i64, _vp]),
     "fa_finalize_f32": (_int, [_vp, _f32, _vp, _i64, _vp]),
     "fa_fedavg_bf16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "fa_fedavg_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_uint16, _vp, _vp]),
     "fa_rounds_create": (_int, [_vp, _int]),
     "fa_rounds_destroy": (_int, [_vp]),
     "fa_fedavg_f32_rounds": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _f32, _vp, _int, _vp, _vp, _vp]),
@@ -122,6 +123,9 @@ _BENCH_PROTOS = {
     "fa_num_bf16_forms": (_int, []),
     "fa_bf16_form_name": (ctypes.c_char_p, [_int]),
     "fa_fedavg_bf16_form": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _int]),
+    "fa_num_f16_forms": (_int, []),
+    "fa_f16_form_name": (ctypes.c_char_p, [_int]),
+    "fa_fedavg_f16_form": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_uint16, _vp, _vp, _int]),
     "fa_fedavg_bf16_variant": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _int]),
     "fa_num_bf16_variants": (_int, []),
     "fa_bf16_variant_name": (ctypes.c_char_p, [_int]),

@@ -252,6 +252,11 @@ int fa_fedavg_bf16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const f
     return bf16_auto(X, N, P, ldx, a, s, divisor, out_f32, out_bf16, stream);
 }
 
+int fa_fedavg_f16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
+                  uint16_t divisor, uint16_t* out, void* stream) {
+    return f16_auto(X, N, P, ldx, a, s, divisor, out, stream);
+}
+
 // ---- one launch per exchange step (struct fa_rounds: peer_exchange.hpp) ------
 
 int fa_rounds_create(fa_rounds** r, int device) {
@@ -392,7 +397,9 @@ int fa_set_autotune(int mode) { return g_tuner.set_mode(mode); }
 int fa_autotune_pending(void) { return g_tuner.pending(); }
 
 const char* fa_fold_form(int kind, int64_t N, int64_t P, int64_t ldx, int scored, void* stream) {
-    if ((kind != FA_FOLD_F32 && kind != FA_FOLD_BF16 && kind != FA_FOLD_F32_ROWS) || N < 1 || P < 1) return "";
+    if ((kind != FA_FOLD_F32 && kind != FA_FOLD_BF16 && kind != FA_FOLD_F32_ROWS && kind != FA_FOLD_F16) || N < 1 ||
+        P < 1)
+        return "";
     StreamDevice on_stream_device(stream);
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) {
@@ -400,7 +407,8 @@ const char* fa_fold_form(int kind, int64_t N, int64_t P, int64_t ldx, int scored
         return "";
     }
     const int policy = kind == FA_FOLD_F32 ? (int)pick_f32(N, P)
-                       : kind == FA_FOLD_F32_ROWS ? (int)pick_ptrs(N, P) : (int)pick_bf16(N, P);
+                       : kind == FA_FOLD_F32_ROWS ? (int)pick_ptrs(N, P)
+                       : kind == FA_FOLD_F16    ? (int)pick_f16(N, P) : (int)pick_bf16(N, P);
     const int tuned = g_tuner.set_mode(-1) ? g_tuner.chosen(dev, kind, N, policy, P, ldx, scored != 0) : -2;
     if (tuned == -1) return "";
     return tune_form_name(kind, tuned >= 0 ? tuned : policy);

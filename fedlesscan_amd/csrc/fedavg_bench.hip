@@ -589,6 +589,21 @@ int fa_fedavg_bf16_form(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, co
     launch_bf16_form((Bf16Form)form, (hipStream_t)stream, X, N, P, ldx, a, s, divisor, out_f32, out_bf16);
     return check_launch("fa_fedavg_bf16_form");
 }
+int fa_num_f16_forms(void) { return kNumBf16Forms; }
+const char* fa_f16_form_name(int form) {
+    return (form >= 0 && form < kNumBf16Forms) ? f16_form_name((Bf16Form)form) : "";
+}
+int fa_fedavg_f16_form(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
+                       uint16_t divisor, uint16_t* out, void* stream, int form) {
+    if (form < 0 || form >= kNumBf16Forms) return fail(FA_ERR_ARG, "unknown f16 form %d", form);
+    int rc = check_common(N, P, ldx, X, a, out);
+    if (rc) return rc;
+    if (P == 0) { g_err[0] = 0; return FA_OK; }
+    if (!aligned16(X) || (ldx % 8) || !aligned16(out)) return fail(FA_ERR_ARG, "the vector forms need 16-B rows");
+    StreamDevice on_stream_device(stream);
+    launch_f16_form((Bf16Form)form, (hipStream_t)stream, X, N, P, ldx, a, s, half_bits_to_float(divisor), out);
+    return check_launch("fa_fedavg_f16_form");
+}
 const char* fa_variant_name(int variant) {
     return (variant >= 0 && variant < kNumVariants) ? kVariants[variant] : "";
 }

@@ -1528,6 +1528,159 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_bf16_gs(
 }
 
 // ---------------------------------------------------------------------------
+// float16: the reference's own arithmetic (numpy keeps a float16 layer float16
+// under Python-number weights), so every product, sum and the quotient round to
+// binary16.  The octet structure of the bf16 fold with packed-half arithmetic:
+// the 16-byte load IS the operand (8 halves in 4 registers, no unpack), the
+// accumulator is 4 packed registers per octet, v_pk_mul_f16 / v_pk_add_f16 do
+// two columns each (-ffp-contract=off keeps them apart).  The quotient is the
+// IEEE float32 divide of the exactly converted operands, rounded once to half:
+// float32 carries 24 >= 2 * 11 + 2 bits, so that double rounding equals the
+// correctly rounded binary16 quotient (numpy computes it the same way).  The
+// divisor arrives as a float32 kernel argument (the half's exact value), which
+// also keeps the compiler from narrowing the divide to its own half expansion.
+// ---------------------------------------------------------------------------
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ _Float16 h_bits(uint16_t b) { return __builtin_bit_cast(_Float16, b); }
+__device__ __forceinline__ uint16_t bits_h(_Float16 h) { return __builtin_bit_cast(uint16_t, h); }
+// Factor i of a binary16 factor array, through the scalar cache.  gfx950 has no
+// 16-bit scalar load, and a 16-bit vector load puts a wave-uniform value on the
+// row loads' counter (measured: the fold then ran 4-27 % behind the bf16 fold,
+// whose float32 factors are scalar loads).  So: the aligned dword that holds
+// the half -- the same 4-byte word, hence the same page and allocation granule
+// as the half itself -- and the half picked from it.  The factors are inputs
+// no launch writes, so the dword is read as constant memory: a scalar load
+// wherever it stands (behind a scheduling barrier the compiler otherwise falls
+// back to a vector load).
+typedef __attribute__((address_space(4))) const uint32_t cu32;
+__device__ __forceinline__ _Float16 factor_h(const uint16_t* __restrict__ a, int64_t i) {
+    const uint16_t* q = a + i;
+    const uint32_t w = *(cu32*)reinterpret_cast<const uint32_t*>(__builtin_align_down(q, 4));
+    return h_bits((uint16_t)(__builtin_is_aligned(q, 4) ? w : (w >> 16)));
+}
+__device__ __forceinline__ f16x8 ld_h8(const u32x4* p) { return __builtin_bit_cast(f16x8, __builtin_nontemporal_load(p)); }
+
+template <bool SCORED>
+__device__ __forceinline__ f16x8 term_h8(f16x8 x, _Float16 a, _Float16 s) {
+    f16x8 t = x * a;
+    if constexpr (SCORED) t = t * s;
+    return t;
+}
+template <bool SCORED>
+__device__ __forceinline__ _Float16 term_h1(_Float16 x, _Float16 a, _Float16 s) {
+    _Float16 t = x * a;
+    if constexpr (SCORED) t = t * s;
+    return t;
+}
+__device__ __forceinline__ f16x8 div_h8(f16x8 acc, float d) {
+    return __builtin_convertvector(__builtin_convertvector(acc, f32x8) / d, f16x8);
+}
+__device__ __forceinline__ _Float16 div_h1(_Float16 acc, float d) { return (_Float16)((float)acc / d); }
+
+// One column of a float16 fold (the P % 8 tail lane and the scalar kernel)
+template <bool SCORED>
+__device__ __forceinline__ uint16_t fold_column_f16(const uint16_t* __restrict__ X, int64_t N, int64_t ldx,
+                                                    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
+                                                    float divisor) {
+    _Float16 acc = term_h1<SCORED>(h_bits(X[0]), factor_h(a, 0), SCORED ? factor_h(s, 0) : (_Float16)1);
+    for (int64_t i = 1; i < N; ++i)
+        acc = acc + term_h1<SCORED>(h_bits(X[i * ldx]), factor_h(a, i), SCORED ? factor_h(s, i) : (_Float16)1);
+    return bits_h(div_h1(acc, divisor));
+}
+
+template <int U, int C, bool SCORED>
+__device__ __forceinline__ void fold_octets_f16(const u32x4* __restrict__ p, int64_t ldo, int64_t N,
+                                                const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
+                                                float divisor, u32x4* __restrict__ out) {
+    f16x8 acc[C];
+    {
+        const _Float16 a0 = factor_h(a, 0), s0 = SCORED ? factor_h(s, 0) : (_Float16)1;
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = term_h8<SCORED>(ld_h8(p + c * kBlock), a0, s0);
+    }
+    int64_t i = 1;
+    for (; i + U <= N; i += U) {
+        u32x4 v[U][C];
+        octets_ld<U, C>(v, p, i, ldo);
+        // 2 rows x 8 octets (and the deep unrolls, as the bf16 fold): every
+        // load of the group issued before the first add, the factors' scalar
+        // loads behind them.  Left to itself the scheduler interleaved the
+        // short packed-half adds and their waits with the row loads of this
+        // form (256 x 100M: 4.7 TB/s, 6.8 with the barrier).  The 8-row forms
+        // keep the compiler's schedule: behind a barrier their eight factor
+        // loads wait one after another (1024 x 67K: 0.116 against 0.093 ms)
+        if constexpr (U >= 16 || (U == 2 && C == 8)) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const _Float16 ai = factor_h(a, i + u), si = SCORED ? factor_h(s, i + u) : (_Float16)1;
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(__builtin_bit_cast(f16x8, v[u][c]), ai, si);
+        }
+    }
+    for (; i < N; ++i) {
+        const _Float16 ai = factor_h(a, i), si = SCORED ? factor_h(s, i) : (_Float16)1;
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(ld_h8(p + i * ldo + c * kBlock), ai, si);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) st16(out + c * kBlock, __builtin_bit_cast(u32x4, div_h8(acc[c], divisor)));
+}
+
+// float16 rows: the tiling of bf16_tile (C octets per lane spaced kBlock apart,
+// the trailing P % 8 columns on the lane with o0 == P / 8), one float16 output.
+template <int U, int C, bool SCORED>
+__device__ __forceinline__ void f16_tile(int64_t bid, const uint16_t* __restrict__ X, int64_t N, int64_t P,
+                                         int64_t ldx, const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
+                                         float divisor, uint16_t* __restrict__ out) {
+    const int64_t no = P >> 3;  // full octets
+    const int64_t ldo = ldx >> 3;
+    const int64_t o0 = bid * (kBlock * C) + threadIdx.x;
+    const u32x4* X8 = reinterpret_cast<const u32x4*>(X);
+    u32x4* O8 = reinterpret_cast<u32x4*>(out);
+    if (o0 + (int64_t)(C - 1) * kBlock < no) {
+        fold_octets_f16<U, C, SCORED>(X8 + o0, ldo, N, a, s, divisor, O8 + o0);
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const int64_t o = o0 + (int64_t)c * kBlock;
+        if (o < no) fold_octets_f16<U, 1, SCORED>(X8 + o, ldo, N, a, s, divisor, O8 + o);
+    }
+    const int64_t tb = no / (kBlock * C), tl = (no % (kBlock * C)) % kBlock;
+    if ((P & 7) && bid == tb && (int64_t)threadIdx.x == tl)
+        for (int64_t col = no * 8; col < P; ++col) out[col] = fold_column_f16<SCORED>(X + col, N, ldx, a, s, divisor);
+}
+
+template <int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f16_v8(
+    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
+    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
+    f16_tile<U, C, SCORED>(blockIdx.x, X, N, P, ldx, a, s, divisor, out);
+}
+
+// grid-stride over octet tiles, as k_fedavg_bf16_gs
+template <int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f16_gs(
+    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
+    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out,
+    int64_t ntiles) {
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        f16_tile<U, C, SCORED>(bid, X, N, P, ldx, a, s, divisor, out);
+}
+
+// float16, one column per lane: any alignment / pitch
+template <bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f16_scalar(
+    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
+    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P) return;
+    out[c] = fold_column_f16<SCORED>(X + c, N, ldx, a, s, divisor);
+}
+
+// ---------------------------------------------------------------------------
 // One launch per exchange step (round 4, fa_fedavg_*_rounds).  Per-round
 // dynamic launches pay a tile-time of tail per round (the last tiles of a
 // round run on a few blocks while the others idle; measured: 256 x the C4
@@ -2056,6 +2209,24 @@ inline const char* bf16_form_name(Bf16Form f) {
     }
     return "";
 }
+// The float16 fold runs the same octet forms (same bytes per row, same tiling)
+// under names of its own.
+inline const char* f16_form_name(Bf16Form f) {
+    switch (f) {
+        case Bf16Form::kV8U2C8: return "f16_tile_u2c8";
+        case Bf16Form::kV8U4C4: return "f16_tile_u4c4";
+        case Bf16Form::kV8U8C2: return "f16_tile_u8c2";
+        case Bf16Form::kV8U8C1: return "f16_tile_u8c1";
+        case Bf16Form::kBandsU8C4: return "f16_bands4_u8c4";
+        case Bf16Form::kBandsU8C2: return "f16_bands4_u8c2";
+        case Bf16Form::kBandsU2C8: return "f16_bands2_u2c8";
+        case Bf16Form::kBandsU4C4: return "f16_bands4_u4c4";
+        case Bf16Form::kBandsU16C2: return "f16_bands4_u16c2";
+        case Bf16Form::kGsBalU8C2: return "f16_gsbal_u8c2";
+        case Bf16Form::kGs1U8C4: return "f16_gs1_u8c4";
+    }
+    return "";
+}
 
 // Column tile of the LDS fold for 32K-256K params: the launch is ~2-8 blocks
 // per CU, so how evenly the blocks fill the CUs decides the time (a scan over
@@ -2330,6 +2501,43 @@ void launch_bf16_bands(hipStream_t st, int passes, const uint16_t* X, int64_t N,
         if (c0 >= P) break;
         const int64_t pb = (P - c0) < band_tiles * to * 8 ? (P - c0) : band_tiles * to * 8;
         launch_bf16_gs<U, C>(st, -1, X + c0, N, pb, ldx, a, s, d, out ? out + c0 : nullptr, outb ? outb + c0 : nullptr);
+    }
+}
+
+// float16 grid-stride launch and its column-band form (as the bf16 pair above)
+template <int U, int C>
+void launch_f16_gs(hipStream_t st, int per_cu, const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
+                   const uint16_t* a, const uint16_t* s, float d, uint16_t* out) {
+    const int64_t per_block = (int64_t)kBlock * C, units = (P >> 3) + ((P & 7) ? 1 : 0);
+    const int64_t tiles = (units + per_block - 1) / per_block;
+    int64_t g = (int64_t)(per_cu > 0 ? per_cu : -per_cu) * cu_count();
+    if (g > tiles) g = tiles;
+    if (per_cu < 0) {
+        const int64_t passes = (tiles + g - 1) / g;
+        g = (tiles + passes - 1) / passes;
+    }
+    if (s)
+        hipLaunchKernelGGL((k_fedavg_f16_gs<U, C, true>), dim3((unsigned)g), dim3(kBlock), 0, st, X, N, P, ldx, a, s,
+                           d, out, tiles);
+    else
+        hipLaunchKernelGGL((k_fedavg_f16_gs<U, C, false>), dim3((unsigned)g), dim3(kBlock), 0, st, X, N, P, ldx, a,
+                           s, d, out, tiles);
+}
+
+template <int U, int C>
+void launch_f16_bands(hipStream_t st, int passes, const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
+                      const uint16_t* a, const uint16_t* s, float d, uint16_t* out) {
+    const int64_t to = (int64_t)kBlock * C;  // octets per tile
+    const int64_t units = (P >> 3) + ((P & 7) ? 1 : 0);
+    const int64_t tiles = (units + to - 1) / to;
+    const int64_t per_band = (int64_t)passes * cu_count();
+    const int64_t nb = (tiles + per_band - 1) / per_band;
+    const int64_t band_tiles = (tiles + nb - 1) / nb;
+    for (int64_t b = 0; b < nb; ++b) {
+        const int64_t c0 = b * band_tiles * to * 8;
+        if (c0 >= P) break;
+        const int64_t pb = (P - c0) < band_tiles * to * 8 ? (P - c0) : band_tiles * to * 8;
+        launch_f16_gs<U, C>(st, -1, X + c0, N, pb, ldx, a, s, d, out + c0);
     }
 }
 
@@ -2767,14 +2975,18 @@ inline int launch_ptrs_form(PtrsForm f, hipStream_t st, const float* const* xi, 
 }
 
 // The tuner (tuner.hpp): a measured form per shape.
-constexpr int kTuneF32 = 1, kTuneBf16 = 2, kTunePtrs = 3;
+// (float16 folds are a kind of their own: their records carry f16_* form names,
+// so a bf16 decision is never read for a float16 shape or the other way round)
+constexpr int kTuneF32 = 1, kTuneBf16 = 2, kTunePtrs = 3, kTuneF16 = 4;
 inline const char* tune_form_name(int kind, int form) {
     if (kind == kTunePtrs) return ptrs_form_name((PtrsForm)form);
+    if (kind == kTuneF16) return f16_form_name((Bf16Form)form);
     return kind == kTuneF32 ? f32_pick_name((F32Pick)form) : bf16_form_name((Bf16Form)form);
 }
 // a form's index from its name (the tuner's cache file and fa_tune_import)
 inline int tune_form_from_name(int kind, const char* name) {
-    const int n = kind == kTuneF32 ? kNumF32Picks : kind == kTuneBf16 ? kNumBf16Forms : kind == kTunePtrs ? kNumPtrsForms : 0;
+    const int n = kind == kTuneF32 ? kNumF32Picks : (kind == kTuneBf16 || kind == kTuneF16) ? kNumBf16Forms
+                  : kind == kTunePtrs ? kNumPtrsForms : 0;
     for (int f = 0; f < n; ++f)
         if (strcmp(tune_form_name(kind, f), name) == 0) return f;
     return -1;
@@ -3092,6 +3304,93 @@ inline int bf16_auto(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const
                     return FA_OK;
                 });
     return check_launch("fedavg_bf16");
+}
+
+// The exact float32 value of a binary16 bit pattern (host side: the divisor
+// travels to the kernels as the float32 it converts to).
+inline float half_bits_to_float(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
+    uint32_t u;
+    if (e == 0x1Fu) {
+        u = sign | 0x7F800000u | (m << 13);
+    } else if (e != 0) {
+        u = sign | ((e + 112u) << 23) | (m << 13);
+    } else if (m == 0) {
+        u = sign;
+    } else {  // subnormal half: m * 2^-24, normal in float32
+        int sh = 0;
+        uint32_t mm = m;
+        while (!(mm & 0x400u)) { mm <<= 1; ++sh; }
+        u = sign | ((uint32_t)(113 - sh) << 23) | ((mm & 0x3FFu) << 13);
+    }
+    float f;
+    memcpy(&f, &u, sizeof f);
+    return f;
+}
+
+// The policy's float16 form by shape: a float16 row has the bytes of a bf16
+// row and the octet forms tile alike, so the static policy starts from the
+// bf16 one (DESIGN.md 5 float16); the tuner measures float16 shapes under
+// their own kind.
+inline Bf16Form pick_f16(int64_t N, int64_t P) { return pick_bf16(N, P); }
+
+inline void launch_f16_form(Bf16Form f, hipStream_t st, const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
+                            const uint16_t* a, const uint16_t* s, float divisor, uint16_t* out) {
+#define FA_HF(U, C)                                                                                         \
+    {                                                                                                       \
+        const int64_t per_block = (int64_t)kBlock * (C), units = (P >> 3) + ((P & 7) ? 1 : 0);            \
+        const dim3 grid((unsigned)((units + per_block - 1) / per_block));                                   \
+        if (s)                                                                                              \
+            hipLaunchKernelGGL((k_fedavg_f16_v8<U, C, true>), grid, dim3(kBlock), 0, st, X, N, P, ldx, a, s, \
+                               divisor, out);                                                               \
+        else                                                                                                \
+            hipLaunchKernelGGL((k_fedavg_f16_v8<U, C, false>), grid, dim3(kBlock), 0, st, X, N, P, ldx, a,  \
+                               s, divisor, out);                                                            \
+    }
+    switch (f) {
+        case Bf16Form::kV8U2C8: FA_HF(2, 8); break;
+        case Bf16Form::kV8U4C4: FA_HF(4, 4); break;
+        case Bf16Form::kV8U8C2: FA_HF(8, 2); break;
+        case Bf16Form::kV8U8C1: FA_HF(8, 1); break;
+        case Bf16Form::kBandsU8C4: launch_f16_bands<8, 4>(st, 4, X, N, P, ldx, a, s, divisor, out); break;
+        case Bf16Form::kBandsU8C2: launch_f16_bands<8, 2>(st, 4, X, N, P, ldx, a, s, divisor, out); break;
+        case Bf16Form::kBandsU2C8: launch_f16_bands<2, 8>(st, 2, X, N, P, ldx, a, s, divisor, out); break;
+        case Bf16Form::kBandsU4C4: launch_f16_bands<4, 4>(st, 4, X, N, P, ldx, a, s, divisor, out); break;
+        case Bf16Form::kBandsU16C2: launch_f16_bands<16, 2>(st, 4, X, N, P, ldx, a, s, divisor, out); break;
+        case Bf16Form::kGsBalU8C2: launch_f16_gs<8, 2>(st, -1, X, N, P, ldx, a, s, divisor, out); break;
+        case Bf16Form::kGs1U8C4: launch_f16_gs<8, 4>(st, 1, X, N, P, ldx, a, s, divisor, out); break;
+    }
+#undef FA_HF
+}
+
+// The product float16 fold (binary16 products, sums and quotient, in row order).
+inline int f16_auto(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
+                    uint16_t divisor, uint16_t* out, void* stream) {
+    int rc = check_common(N, P, ldx, X, a, out);
+    if (rc) return rc;
+    if (P == 0) { g_err[0] = 0; return FA_OK; }
+    hipStream_t st = (hipStream_t)stream;
+    StreamDevice on_stream_device(stream);
+    const float d = half_bits_to_float(divisor);
+    if (!(aligned16(X) && (ldx % 8 == 0) && aligned16(out))) {
+        if (s)
+            hipLaunchKernelGGL(k_fedavg_f16_scalar<true>, grid_for(P), dim3(kBlock), 0, st, X, N, P, ldx, a, s, d, out);
+        else
+            hipLaunchKernelGGL(k_fedavg_f16_scalar<false>, grid_for(P), dim3(kBlock), 0, st, X, N, P, ldx, a, s, d, out);
+        return check_launch("k_fedavg_f16_scalar");
+    }
+    const Bf16Form policy = pick_f16(N, P);
+    if (overlaps(out, (size_t)P * 2, X, ((size_t)(N - 1) * ldx + P) * 2)) {
+        launch_f16_form(policy, st, X, N, P, ldx, a, s, d, out);  // in place: one launch
+        return check_launch("fedavg_f16");
+    }
+    g_tuner.run(kTuneF16, N, P, ldx, s != nullptr, (int)policy, (double)N * (double)P * 2.0, st,
+                [&](std::vector<int>& c) { bf16_candidates(N, P, (int)policy, c); },
+                [&](int form) {
+                    launch_f16_form((Bf16Form)form, st, X, N, P, ldx, a, s, d, out);
+                    return FA_OK;
+                });
+    return check_launch("fedavg_f16");
 }
 
 }  // namespace

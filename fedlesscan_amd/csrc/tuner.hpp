@@ -637,7 +637,7 @@ class Tuner {
             const int kind = std::get<1>(e.key);
             char line[1024];
             int k = snprintf(line, sizeof(line), "fedavg tuner: %s N=%lld P=%lld ldx=%lld%s batch=%d -> %s |",
-                             kind == 1 ? "f32" : kind == 2 ? "bf16" : "f32 rows", (long long)e.N,
+                             kind == 1 ? "f32" : kind == 2 ? "bf16" : kind == 4 ? "f16" : "f32 rows", (long long)e.N,
                              (long long)std::get<4>(e.key), (long long)std::get<5>(e.key),
                              std::get<6>(e.key) ? " scored" : "", e.batch, form_name(kind, e.chosen));
             for (int c = 0; c < n && k > 0 && k < (int)sizeof(line); ++c)

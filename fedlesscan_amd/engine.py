@@ -32,7 +32,8 @@ from .aggregator.exceptions import InvalidParameterShapeError
 _TORCH_TO_NP = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32,
                 torch.int64: np.int64, torch.float16: np.float16}
 _NP_TO_TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
-                np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64}
+                np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64,
+                np.dtype(np.float16): torch.float16}
 ROW_ALIGN = 64  # elements; row pitch multiple of 256 B for fp32
 
 
@@ -244,7 +245,8 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
 
     `total` overrides the divisor sum (used when zip() truncated the rows but
     the reference still divides by the sum of every weight).  Returns `out`
-    ([P] tensor in the result dtype).  bf16 input: want_bf16=True returns
+    ([P] tensor in the result dtype; float16 rows under Python-number factors
+    give float16, every operation rounded to binary16 as numpy does).  bf16 input: want_bf16=True returns
     (out_f32, out_bf16); out_bf16= (a [P] bfloat16 tensor) receives the RNE
     copy in place -- without out it is the only output (no fp32 result is
     stored, ABI 5) and is returned alone, with out the pair is returned.
@@ -296,6 +298,21 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
         out = out if out is not None else torch.empty(P, dtype=torch.float64, device=dev)
         name = "fa_fedavg_i32" if in_dt == np.int32 else "fa_fedavg_i64"
         _lib.call(name, X.data_ptr(), N, P, ldx, a.data_ptr(), f.div, out.data_ptr(), st)
+        return out
+    if dt == np.float16:
+        # float16 rows under weak (Python-number) factors stay float16 in numpy:
+        # binary16 products, sums and quotient (fa_fedavg_f16)
+        if torch.cuda.is_current_stream_capturing():
+            raise InvalidParameterShapeError("the float16 fold does not run under stream capture "
+                                             "(the captured factor fill carries float32 factors only)")
+        if out is None:
+            out = torch.empty(P, dtype=torch.float16, device=dev)
+        elif not (out.is_cuda and out.dtype == torch.float16 and out.is_contiguous() and out.numel() >= P):
+            raise ValueError(f"out must be a contiguous CUDA float16 tensor of >= {P} elements")
+        f = Factors(weights, scores, dt, total=total)
+        a, s = f.to(dev)
+        _lib.call("fa_fedavg_f16", X.data_ptr(), N, P, ldx, a.data_ptr(), _ptr(s),
+                  int(np.asarray(f.div, dtype=np.float16).view(np.uint16)), out.data_ptr(), st)
         return out
     if dt not in (np.float32, np.float64):
         raise InvalidParameterShapeError(f"unsupported result dtype {dt} (input {in_dt})")

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 6
+#define FA_ABI_VERSION 7
 
 enum fa_status {
     FA_OK = 0,
@@ -113,6 +113,25 @@ int fa_finalize_f32(const float* acc, float divisor, float* out, int64_t P, void
 int fa_fedavg_bf16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
                    const float* a, const float* s, float divisor,
                    float* out_f32, uint16_t* out_bf16, void* stream);
+
+/* float16 updates (ABI 7).  The reference folds whatever dtype the clients
+ * send: np.multiply(layer, n) with a Python-number weight keeps a float16 layer
+ * float16 (NEP 50), so fed_avg_aggregator.py:31-41 and
+ * stall_aware_aggregation.py:52-66 multiply, add and divide in binary16.  The
+ * halves travel as their bit patterns; a, s [device, N halves] and divisor are
+ * the factors already rounded to binary16 (s == NULL for FedAvg); out [P]:
+ *   t_i = fl16(fl16(x_i * a_i) * s_i)       (FedAvg: t_i = fl16(x_i * a_i))
+ *   acc = t_0;  acc = fl16(acc + t_i), i = 1..N-1 in client order
+ *   out = fl16(acc / divisor)
+ * Every operation is IEEE binary16 round-to-nearest-even with subnormals kept
+ * and no FMA; factors that overflowed to inf stay inf, as in the reference.
+ * NaN positions match numpy's, NaN sign and payload are unspecified.  Same
+ * argument checks and status codes as fa_fedavg_f32.  16-B aligned X and out
+ * with ldx % 8 == 0 take the vector forms (a measured form per shape, kind
+ * FA_FOLD_F16), anything else one column per lane; out may overlap X. */
+int fa_fedavg_f16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
+                  const uint16_t* a, const uint16_t* s, uint16_t divisor,
+                  uint16_t* out, void* stream);
 
 /* ---- one launch per exchange step (ABI 3) -----------------------------------
  * At N > 1 a rank folds its columns in `rounds` slots and all-gathers each
@@ -252,10 +271,10 @@ int fa_fedavg_bf16_rounds_hostf(fa_rounds* r, const uint16_t* X, int64_t N, int6
                                 float* out_f32, uint16_t* out_bf16,
                                 int rounds, const int64_t* offsets, const int64_t* out_offsets, void* stream);
 
-/* Measured form choice.  Every kernel form of the fp32, bf16 and row-table
- * folds computes the same bits; which is fastest depends on how a shape's
+/* Measured form choice.  Every kernel form of the fp32, bf16, float16 and
+ * row-table folds computes the same bits; which is fastest depends on how a shape's
  * tiles fall on the CUs.  For plain one-shot folds (fa_fedavg_f32, _bf16,
- * _f32_ptrs_aligned and their _hostf forms) the FIRST call of a new (device,
+ * _f16, _f32_ptrs_aligned and the _hostf forms) the FIRST call of a new (device,
  * kind, N, P, ldx, scored) shape runs every candidate form on the caller's
  * data and stream (an untimed launch each, then two timed passes of batched
  * launches between events), and once those events have completed -- read
@@ -278,6 +297,7 @@ enum fa_fold_kind {
     FA_FOLD_F32 = 1,      /* fa_fedavg_f32 (_hostf)                     */
     FA_FOLD_BF16 = 2,     /* fa_fedavg_bf16 (_hostf)                    */
     FA_FOLD_F32_ROWS = 3, /* fa_fedavg_f32_ptrs_aligned (_hostf), ldx = P */
+    FA_FOLD_F16 = 4,      /* fa_fedavg_f16                              */
 };
 int fa_set_autotune(int mode);
 int fa_autotune_pending(void);

@@ -68,6 +68,10 @@ int fa_num_bf16_forms(void);
 const char* fa_bf16_form_name(int form);
 int fa_fedavg_bf16_form(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const float* a, const float* s,
                         float divisor, float* out_f32, uint16_t* out_bf16, void* stream, int form);
+int fa_num_f16_forms(void);
+const char* fa_f16_form_name(int form);
+int fa_fedavg_f16_form(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
+                       uint16_t divisor, uint16_t* out, void* stream, int form);
 /* Same for the bf16 fold (variant 0 = fa_fedavg_bf16). */
 int fa_fedavg_bf16_variant(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
                            const float* a, const float* s, float divisor,
