@@ -54,6 +54,9 @@ _PROTOS = {
     "fa_finalize_f32": (_int, [_vp, _f32, _vp, _i64, _vp]),
     "fa_fedavg_bf16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp]),
     "fa_fedavg_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_uint16, _vp, _vp]),
+    "fa_fedavg_bf16_ptrs": (_int, [_vp, _i64, _i64, _vp, _vp, _f32, _int, _vp, _vp, _vp]),
+    "fa_fedavg_bf16_ptrs_hostf": (_int, [_vp, _i64, _i64, _vp, _vp, _f32, _int, _vp, _vp, _vp]),
+    "fa_fedavg_f16_ptrs": (_int, [_vp, _i64, _i64, _vp, _vp, ctypes.c_uint16, _int, _vp, _vp]),
     "fa_rounds_create": (_int, [_vp, _int]),
     "fa_rounds_destroy": (_int, [_vp]),
     "fa_fedavg_f32_rounds": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _f32, _vp, _int, _vp, _vp, _vp]),
@@ -126,6 +129,10 @@ _BENCH_PROTOS = {
     "fa_num_f16_forms": (_int, []),
     "fa_f16_form_name": (ctypes.c_char_p, [_int]),
     "fa_fedavg_f16_form": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_uint16, _vp, _vp, _int]),
+    "fa_num_rows16_forms": (_int, []),
+    "fa_rows16_form_name": (ctypes.c_char_p, [_int]),
+    "fa_fedavg_bf16_ptrs_form": (_int, [_vp, _i64, _i64, _vp, _vp, _f32, _int, _vp, _vp, _vp, _int]),
+    "fa_fedavg_f16_ptrs_form": (_int, [_vp, _i64, _i64, _vp, _vp, ctypes.c_uint16, _int, _vp, _vp, _int]),
     "fa_fedavg_bf16_variant": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _int]),
     "fa_num_bf16_variants": (_int, []),
     "fa_bf16_variant_name": (ctypes.c_char_p, [_int]),

@@ -257,6 +257,16 @@ int fa_fedavg_f16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const ui
     return f16_auto(X, N, P, ldx, a, s, divisor, out, stream);
 }
 
+int fa_fedavg_bf16_ptrs(const uint16_t* const* xi, int64_t N, int64_t P, const float* a, const float* s,
+                        float divisor, int rows_aligned, float* out_f32, uint16_t* out_bf16, void* stream) {
+    return bf16_rows_fold(xi, N, P, a, s, divisor, rows_aligned, out_f32, out_bf16, stream);
+}
+
+int fa_fedavg_f16_ptrs(const uint16_t* const* xi, int64_t N, int64_t P, const uint16_t* a, const uint16_t* s,
+                       uint16_t divisor, int rows_aligned, uint16_t* out, void* stream) {
+    return f16_rows_fold(xi, N, P, a, s, divisor, rows_aligned, out, stream);
+}
+
 // ---- one launch per exchange step (struct fa_rounds: peer_exchange.hpp) ------
 
 int fa_rounds_create(fa_rounds** r, int device) {
@@ -521,6 +531,13 @@ int fa_fedavg_bf16_hostf(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, c
                          float divisor, float* out_f32, uint16_t* out_bf16, void* stream) {
     return with_host_factors(a, s, N, stream, [&](const float* ad, const float* sd) {
         return bf16_auto(X, N, P, ldx, ad, sd, divisor, out_f32, out_bf16, stream);
+    });
+}
+
+int fa_fedavg_bf16_ptrs_hostf(const uint16_t* const* xi, int64_t N, int64_t P, const float* a, const float* s,
+                              float divisor, int rows_aligned, float* out_f32, uint16_t* out_bf16, void* stream) {
+    return with_host_factors(a, s, N, stream, [&](const float* ad, const float* sd) {
+        return bf16_rows_fold(xi, N, P, ad, sd, divisor, rows_aligned, out_f32, out_bf16, stream);
     });
 }
 

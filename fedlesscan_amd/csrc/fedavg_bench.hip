@@ -604,6 +604,19 @@ int fa_fedavg_f16_form(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, con
     launch_f16_form((Bf16Form)form, (hipStream_t)stream, X, N, P, ldx, a, s, half_bits_to_float(divisor), out);
     return check_launch("fa_fedavg_f16_form");
 }
+int fa_num_rows16_forms(void) { return kNumRows16Forms; }
+const char* fa_rows16_form_name(int form) {
+    return (form >= 0 && form < kNumRows16Forms) ? rows16_form_name((Rows16Form)form) : "";
+}
+int fa_fedavg_bf16_ptrs_form(const uint16_t* const* xi, int64_t N, int64_t P, const float* a, const float* s,
+                             float divisor, int rows_aligned, float* out_f32, uint16_t* out_bf16, void* stream,
+                             int form) {
+    return bf16_rows_fold(xi, N, P, a, s, divisor, rows_aligned, out_f32, out_bf16, stream, form < 0 ? -1 : form);
+}
+int fa_fedavg_f16_ptrs_form(const uint16_t* const* xi, int64_t N, int64_t P, const uint16_t* a, const uint16_t* s,
+                            uint16_t divisor, int rows_aligned, uint16_t* out, void* stream, int form) {
+    return f16_rows_fold(xi, N, P, a, s, divisor, rows_aligned, out, stream, form < 0 ? -1 : form);
+}
 const char* fa_variant_name(int variant) {
     return (variant >= 0 && variant < kNumVariants) ? kVariants[variant] : "";
 }

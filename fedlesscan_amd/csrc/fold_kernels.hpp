@@ -1527,6 +1527,137 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_bf16_gs(
         bf16_tile<U, C, SCORED>(bid, X, N, P, ldx, a, s, divisor, out, outb);
 }
 
+// bf16 list-of-rows form with every row 16-B aligned (fa_fedavg_bf16_ptrs,
+// rows_aligned != 0): fold_octets with row i's base read from xi[i] (a
+// wave-uniform scalar load) instead of p + i * ldo; o = the lane's first octet.
+// Same unpack, terms, adds, divide and stores, hence the same bits as the
+// stacked fold over the same rows.  Functions of their own beside the stacked
+// ones (as fold_quads_rows): the stacked kernels keep their generated code.
+// The bases are read as global-memory pointers: through a generic pointer the
+// row loads would be flat loads, which also count on the scalar loads' counter
+// (every wait for a factor would then wait for the rows in flight).
+typedef __attribute__((address_space(1))) const uint16_t gu16;
+typedef __attribute__((address_space(1))) const u32x4 gu32x4;
+
+template <int U, int C, bool SCORED>
+__device__ __forceinline__ void fold_octets_rows(const uint16_t* const* __restrict__ xi, int64_t o, int64_t N,
+                                                 const float* __restrict__ a, const float* __restrict__ s,
+                                                 float divisor, float* __restrict__ out,
+                                                 uint16_t* __restrict__ outb) {
+    f32x4 ev[C], od[C];
+    {
+        const gu32x4* r = (const gu32x4*)xi[0] + o;
+        const float a0 = a[0], s0 = SCORED ? s[0] : 1.0f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            f32x4 e, d;
+            unpack_bf16x8(__builtin_nontemporal_load(r + c * kBlock), e, d);
+            ev[c] = term4<SCORED>(e, a0, s0);
+            od[c] = term4<SCORED>(d, a0, s0);
+        }
+    }
+    int64_t i = 1;
+    for (; i + U <= N; i += U) {
+        u32x4 v[U][C];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const gu32x4* r = (const gu32x4*)xi[i + u] + o;
+#pragma unroll
+            for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
+        }
+        // deep unrolls: every load of the group issued before the first add
+        if constexpr (U >= 16) __builtin_amdgcn_sched_barrier(0);
+        octets_add<U, C, SCORED>(ev, od, v, a, s, i);
+    }
+    for (; i < N; ++i) {
+        const gu32x4* r = (const gu32x4*)xi[i] + o;
+        const float ai = a[i], si = SCORED ? s[i] : 1.0f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            f32x4 e, d;
+            unpack_bf16x8(__builtin_nontemporal_load(r + c * kBlock), e, d);
+            ev[c] = add4(ev[c], term4<SCORED>(e, ai, si));
+            od[c] = add4(od[c], term4<SCORED>(d, ai, si));
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const f32x4 e = div4(ev[c], divisor), d = div4(od[c], divisor);
+        const int64_t oc = o + (int64_t)c * kBlock;
+        if (out) {
+            f32x4* o4 = reinterpret_cast<f32x4*>(out) + 2 * oc;
+            st16(o4, __builtin_bit_cast(u32x4, f32x4{e.x, d.x, e.y, d.y}));
+            st16(o4 + 1, __builtin_bit_cast(u32x4, f32x4{e.z, d.z, e.w, d.w}));
+        }
+        if (outb) {
+            u32x4 b;
+            b.x = (uint32_t)f2bf_rne(e.x) | ((uint32_t)f2bf_rne(d.x) << 16);
+            b.y = (uint32_t)f2bf_rne(e.y) | ((uint32_t)f2bf_rne(d.y) << 16);
+            b.z = (uint32_t)f2bf_rne(e.z) | ((uint32_t)f2bf_rne(d.z) << 16);
+            b.w = (uint32_t)f2bf_rne(e.w) | ((uint32_t)f2bf_rne(d.w) << 16);
+            st16(reinterpret_cast<u32x4*>(outb) + oc, b);
+        }
+    }
+}
+
+// grid-stride over octet tiles (the tiling of bf16_tile: C octets per lane
+// spaced kBlock apart, a partial last tile octet by octet, the trailing P % 8
+// columns on the lane bf16_tile picks)
+template <int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_bf16_rows_gs(
+    const uint16_t* const* __restrict__ xi, int64_t N, int64_t P, const float* __restrict__ a,
+    const float* __restrict__ s, float divisor, float* __restrict__ out, uint16_t* __restrict__ outb,
+    int64_t ntiles) {
+    const int64_t no = P >> 3;  // full octets
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+        const int64_t o0 = bid * (kBlock * C) + threadIdx.x;
+        if (o0 + (int64_t)(C - 1) * kBlock < no) {
+            fold_octets_rows<U, C, SCORED>(xi, o0, N, a, s, divisor, out, outb);
+            continue;
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const int64_t o = o0 + (int64_t)c * kBlock;
+            if (o < no) fold_octets_rows<U, 1, SCORED>(xi, o, N, a, s, divisor, out, outb);
+        }
+        const int64_t tb = no / (kBlock * C), tl = (no % (kBlock * C)) % kBlock;
+        if ((P & 7) && bid == tb && (int64_t)threadIdx.x == tl) {
+            for (int64_t col = no * 8; col < P; ++col) {
+                float acc = term1<SCORED>(bf2f(((const gu16*)xi[0])[col]), a[0], SCORED ? s[0] : 1.0f);
+                for (int64_t i = 1; i < N; ++i)
+                    acc = acc + term1<SCORED>(bf2f(((const gu16*)xi[i])[col]), a[i], SCORED ? s[i] : 1.0f);
+                acc = acc / divisor;
+                if (out) out[col] = acc;
+                if (outb) outb[col] = f2bf_rne(acc);
+            }
+        }
+    }
+}
+
+// bf16 list-of-rows form, rows at any 2-B offset: lane = one column, row i's
+// base a wave-uniform load from the table, 8 rows of loads ahead of the ordered
+// adds (as k_fold_f32_rows_scalar); the arithmetic of the P % 8 tail above.
+template <bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_bf16_rows_scalar(
+    const uint16_t* const* __restrict__ xi, int64_t N, int64_t P, const float* __restrict__ a,
+    const float* __restrict__ s, float divisor, float* __restrict__ out, uint16_t* __restrict__ outb) {
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P) return;
+    float acc = term1<SCORED>(bf2f(((const gu16*)xi[0])[c]), a[0], SCORED ? s[0] : 1.0f);
+    int64_t i = 1;
+    for (; i + 8 <= N; i += 8) {
+        uint16_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load((const gu16*)xi[i + u] + c);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc = acc + term1<SCORED>(bf2f(v[u]), a[i + u], SCORED ? s[i + u] : 1.0f);
+    }
+    for (; i < N; ++i) acc = acc + term1<SCORED>(bf2f(((const gu16*)xi[i])[c]), a[i], SCORED ? s[i] : 1.0f);
+    acc = acc / divisor;
+    if (out) out[c] = acc;
+    if (outb) outb[c] = f2bf_rne(acc);
+}
+
 // ---------------------------------------------------------------------------
 // float16: the reference's own arithmetic (numpy keeps a float16 layer float16
 // under Python-number weights), so every product, sum and the quotient round to
@@ -1678,6 +1809,116 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f16_scalar(
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= P) return;
     out[c] = fold_column_f16<SCORED>(X + c, N, ldx, a, s, divisor);
+}
+
+// float16 list-of-rows form with every row 16-B aligned (fa_fedavg_f16_ptrs,
+// rows_aligned != 0): fold_octets_f16 with row i's base read from xi[i] (a
+// wave-uniform scalar load); the packed-half arithmetic, the float32 divisor
+// and the scheduling-barrier rule of that function, hence its bits.
+__device__ __forceinline__ f16x8 ld_h8g(const gu32x4* p) { return __builtin_bit_cast(f16x8, __builtin_nontemporal_load(p)); }
+
+template <int U, int C, bool SCORED>
+__device__ __forceinline__ void fold_octets_f16_rows(const uint16_t* const* __restrict__ xi, int64_t o, int64_t N,
+                                                     const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
+                                                     float divisor, u32x4* __restrict__ out) {
+    f16x8 acc[C];
+    {
+        const gu32x4* r = (const gu32x4*)xi[0] + o;
+        const _Float16 a0 = factor_h(a, 0), s0 = SCORED ? factor_h(s, 0) : (_Float16)1;
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = term_h8<SCORED>(ld_h8g(r + c * kBlock), a0, s0);
+    }
+    int64_t i = 1;
+    for (; i + U <= N; i += U) {
+        u32x4 v[U][C];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const gu32x4* r = (const gu32x4*)xi[i + u] + o;
+#pragma unroll
+            for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
+        }
+        // as fold_octets_f16: 2 rows x 8 octets and the deep unrolls issue every
+        // load of the group before the first add; the 8-row forms keep the
+        // compiler's schedule
+        if constexpr (U >= 16 || (U == 2 && C == 8)) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const _Float16 ai = factor_h(a, i + u), si = SCORED ? factor_h(s, i + u) : (_Float16)1;
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(__builtin_bit_cast(f16x8, v[u][c]), ai, si);
+        }
+    }
+    for (; i < N; ++i) {
+        const gu32x4* r = (const gu32x4*)xi[i] + o;
+        const _Float16 ai = factor_h(a, i), si = SCORED ? factor_h(s, i) : (_Float16)1;
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(ld_h8g(r + c * kBlock), ai, si);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) st16(out + o + c * kBlock, __builtin_bit_cast(u32x4, div_h8(acc[c], divisor)));
+}
+
+// One column of a float16 row-table fold (the P % 8 tail lane): fold_column_f16
+// with the rows' own bases
+template <bool SCORED>
+__device__ __forceinline__ uint16_t fold_column_f16_rows(const uint16_t* const* __restrict__ xi, int64_t col,
+                                                         int64_t N, const uint16_t* __restrict__ a,
+                                                         const uint16_t* __restrict__ s, float divisor) {
+    _Float16 acc = term_h1<SCORED>(h_bits(((const gu16*)xi[0])[col]), factor_h(a, 0),
+                                   SCORED ? factor_h(s, 0) : (_Float16)1);
+    for (int64_t i = 1; i < N; ++i)
+        acc = acc + term_h1<SCORED>(h_bits(((const gu16*)xi[i])[col]), factor_h(a, i),
+                                    SCORED ? factor_h(s, i) : (_Float16)1);
+    return bits_h(div_h1(acc, divisor));
+}
+
+// grid-stride over octet tiles, the tiling of f16_tile
+template <int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f16_rows_gs(
+    const uint16_t* const* __restrict__ xi, int64_t N, int64_t P, const uint16_t* __restrict__ a,
+    const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out, int64_t ntiles) {
+    const int64_t no = P >> 3;  // full octets
+    u32x4* O8 = reinterpret_cast<u32x4*>(out);
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+        const int64_t o0 = bid * (kBlock * C) + threadIdx.x;
+        if (o0 + (int64_t)(C - 1) * kBlock < no) {
+            fold_octets_f16_rows<U, C, SCORED>(xi, o0, N, a, s, divisor, O8);
+            continue;
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const int64_t o = o0 + (int64_t)c * kBlock;
+            if (o < no) fold_octets_f16_rows<U, 1, SCORED>(xi, o, N, a, s, divisor, O8);
+        }
+        const int64_t tb = no / (kBlock * C), tl = (no % (kBlock * C)) % kBlock;
+        if ((P & 7) && bid == tb && (int64_t)threadIdx.x == tl)
+            for (int64_t col = no * 8; col < P; ++col) out[col] = fold_column_f16_rows<SCORED>(xi, col, N, a, s, divisor);
+    }
+}
+
+// float16 list-of-rows form, rows at any 2-B offset: one column per lane, 8
+// rows of loads ahead of the ordered adds, the arithmetic of fold_column_f16
+template <bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f16_rows_scalar(
+    const uint16_t* const* __restrict__ xi, int64_t N, int64_t P, const uint16_t* __restrict__ a,
+    const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P) return;
+    _Float16 acc = term_h1<SCORED>(h_bits(((const gu16*)xi[0])[c]), factor_h(a, 0),
+                                   SCORED ? factor_h(s, 0) : (_Float16)1);
+    int64_t i = 1;
+    for (; i + 8 <= N; i += 8) {
+        uint16_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load((const gu16*)xi[i + u] + c);
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            acc = acc + term_h1<SCORED>(h_bits(v[u]), factor_h(a, i + u), SCORED ? factor_h(s, i + u) : (_Float16)1);
+    }
+    for (; i < N; ++i)
+        acc = acc + term_h1<SCORED>(h_bits(((const gu16*)xi[i])[c]), factor_h(a, i),
+                                    SCORED ? factor_h(s, i) : (_Float16)1);
+    out[c] = bits_h(div_h1(acc, divisor));
 }
 
 // ---------------------------------------------------------------------------
@@ -3391,6 +3632,133 @@ inline int f16_auto(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const 
                     return FA_OK;
                 });
     return check_launch("fedavg_f16");
+}
+
+// ---- the 16-bit row-table folds (fa_fedavg_bf16_ptrs, fa_fedavg_f16_ptrs) ----
+// Row bases come from a device table.  Every-row-aligned tables take the octet
+// tiling, grid-stride with balanced passes (as launch_bf16_gs(-1)); anything
+// else one column per lane.  The shape policy is fixed, not measured: octets
+// per lane from pick_octets, rows ahead as the stacked policy pairs them.
+enum class Rows16Form { kGsU2C8, kGsU8C4, kGsU8C2, kGsU8C1, kColumn };
+constexpr int kNumRows16Forms = (int)Rows16Form::kColumn + 1;
+inline const char* rows16_form_name(Rows16Form f) {
+    switch (f) {
+        case Rows16Form::kGsU2C8: return "rows16_gsbal_u2c8";
+        case Rows16Form::kGsU8C4: return "rows16_gsbal_u8c4";
+        case Rows16Form::kGsU8C2: return "rows16_gsbal_u8c2";
+        case Rows16Form::kGsU8C1: return "rows16_gsbal_u8c1";
+        case Rows16Form::kColumn: return "rows16_column";
+    }
+    return "";
+}
+
+inline Rows16Form pick_rows16(int64_t N, int64_t P) {
+    switch (pick_octets(N, P)) {
+        case 8: return Rows16Form::kGsU2C8;
+        case 4: return Rows16Form::kGsU8C4;
+        case 2: return Rows16Form::kGsU8C2;
+        default: return Rows16Form::kGsU8C1;
+    }
+}
+
+// tiles of C octets per lane (the column-tail lane's tile included) and the
+// balanced grid over them: at most one block per CU, the fewest blocks that
+// finish in the same number of passes
+template <int C>
+inline void rows16_grid(int64_t P, int64_t& tiles, int64_t& g) {
+    const int64_t per_block = (int64_t)kBlock * C, units = (P >> 3) + ((P & 7) ? 1 : 0);
+    tiles = (units + per_block - 1) / per_block;
+    g = cu_count();
+    if (g > tiles) g = tiles;
+    const int64_t passes = (tiles + g - 1) / g;
+    g = (tiles + passes - 1) / passes;
+}
+
+template <int U, int C>
+void launch_bf16_rows_gs(hipStream_t st, const uint16_t* const* xi, int64_t N, int64_t P, const float* a,
+                         const float* s, float d, float* out, uint16_t* outb) {
+    int64_t tiles, g;
+    rows16_grid<C>(P, tiles, g);
+    if (s)
+        hipLaunchKernelGGL((k_fedavg_bf16_rows_gs<U, C, true>), dim3((unsigned)g), dim3(kBlock), 0, st, xi, N, P, a, s,
+                           d, out, outb, tiles);
+    else
+        hipLaunchKernelGGL((k_fedavg_bf16_rows_gs<U, C, false>), dim3((unsigned)g), dim3(kBlock), 0, st, xi, N, P, a,
+                           s, d, out, outb, tiles);
+}
+
+template <int U, int C>
+void launch_f16_rows_gs(hipStream_t st, const uint16_t* const* xi, int64_t N, int64_t P, const uint16_t* a,
+                        const uint16_t* s, float d, uint16_t* out) {
+    int64_t tiles, g;
+    rows16_grid<C>(P, tiles, g);
+    if (s)
+        hipLaunchKernelGGL((k_fedavg_f16_rows_gs<U, C, true>), dim3((unsigned)g), dim3(kBlock), 0, st, xi, N, P, a, s,
+                           d, out, tiles);
+    else
+        hipLaunchKernelGGL((k_fedavg_f16_rows_gs<U, C, false>), dim3((unsigned)g), dim3(kBlock), 0, st, xi, N, P, a,
+                           s, d, out, tiles);
+}
+
+// form < 0: the policy (rows_aligned picks the octet tiling or the column
+// kernel); form >= 0: that form (the bench library; the octet forms need
+// rows_aligned != 0)
+inline int bf16_rows_fold(const uint16_t* const* xi, int64_t N, int64_t P, const float* a, const float* s,
+                          float divisor, int rows_aligned, float* out_f32, uint16_t* out_bf16, void* stream,
+                          int form = -1) {
+    if (form >= kNumRows16Forms) return fail(FA_ERR_ARG, "unknown 16-bit row-table form %d", form);
+    int rc = check_common(N, P, P, xi, a, bf16_any_out(out_f32, out_bf16));
+    if (rc) return rc;
+    if (P == 0) { g_err[0] = 0; return FA_OK; }
+    if (form < 0) form = (int)(rows_aligned ? pick_rows16(N, P) : Rows16Form::kColumn);
+    if (form != (int)Rows16Form::kColumn && !(rows_aligned && aligned16(out_f32) && aligned16(out_bf16)))
+        return fail(FA_ERR_ARG, "the octet forms of the bf16 row-table fold need 16-B aligned rows and outputs");
+    hipStream_t st = (hipStream_t)stream;
+    StreamDevice on_stream_device(stream);
+    switch ((Rows16Form)form) {
+        case Rows16Form::kGsU2C8: launch_bf16_rows_gs<2, 8>(st, xi, N, P, a, s, divisor, out_f32, out_bf16); break;
+        case Rows16Form::kGsU8C4: launch_bf16_rows_gs<8, 4>(st, xi, N, P, a, s, divisor, out_f32, out_bf16); break;
+        case Rows16Form::kGsU8C2: launch_bf16_rows_gs<8, 2>(st, xi, N, P, a, s, divisor, out_f32, out_bf16); break;
+        case Rows16Form::kGsU8C1: launch_bf16_rows_gs<8, 1>(st, xi, N, P, a, s, divisor, out_f32, out_bf16); break;
+        case Rows16Form::kColumn:
+            if (s)
+                hipLaunchKernelGGL(k_fedavg_bf16_rows_scalar<true>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a, s,
+                                   divisor, out_f32, out_bf16);
+            else
+                hipLaunchKernelGGL(k_fedavg_bf16_rows_scalar<false>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a, s,
+                                   divisor, out_f32, out_bf16);
+            break;
+    }
+    return check_launch("fa_fedavg_bf16_ptrs");
+}
+
+inline int f16_rows_fold(const uint16_t* const* xi, int64_t N, int64_t P, const uint16_t* a, const uint16_t* s,
+                         uint16_t divisor, int rows_aligned, uint16_t* out, void* stream, int form = -1) {
+    if (form >= kNumRows16Forms) return fail(FA_ERR_ARG, "unknown 16-bit row-table form %d", form);
+    int rc = check_common(N, P, P, xi, a, out);
+    if (rc) return rc;
+    if (P == 0) { g_err[0] = 0; return FA_OK; }
+    if (form < 0) form = (int)(rows_aligned ? pick_rows16(N, P) : Rows16Form::kColumn);
+    if (form != (int)Rows16Form::kColumn && !(rows_aligned && aligned16(out)))
+        return fail(FA_ERR_ARG, "the octet forms of the float16 row-table fold need 16-B aligned rows and out");
+    hipStream_t st = (hipStream_t)stream;
+    StreamDevice on_stream_device(stream);
+    const float d = half_bits_to_float(divisor);
+    switch ((Rows16Form)form) {
+        case Rows16Form::kGsU2C8: launch_f16_rows_gs<2, 8>(st, xi, N, P, a, s, d, out); break;
+        case Rows16Form::kGsU8C4: launch_f16_rows_gs<8, 4>(st, xi, N, P, a, s, d, out); break;
+        case Rows16Form::kGsU8C2: launch_f16_rows_gs<8, 2>(st, xi, N, P, a, s, d, out); break;
+        case Rows16Form::kGsU8C1: launch_f16_rows_gs<8, 1>(st, xi, N, P, a, s, d, out); break;
+        case Rows16Form::kColumn:
+            if (s)
+                hipLaunchKernelGGL(k_fedavg_f16_rows_scalar<true>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a, s, d,
+                                   out);
+            else
+                hipLaunchKernelGGL(k_fedavg_f16_rows_scalar<false>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a, s, d,
+                                   out);
+            break;
+    }
+    return check_launch("fa_fedavg_f16_ptrs");
 }
 
 }  // namespace

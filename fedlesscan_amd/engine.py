@@ -2,8 +2,8 @@
 
 Layering
   engine.fold_stacked(X, weights, scores)   X: CUDA tensor [N, P] (row pitch = X.stride(0))
-  engine.fold_rows(rows, weights, scores)   N separately allocated CUDA rows (pointer list;
-                                            engine.RowSet prepares a reusable row set)
+  engine.fold_rows(rows, weights, scores)   N separately allocated CUDA rows (pointer list: fp32,
+                                            bf16, float16; engine.RowSet prepares a reusable row set)
   engine.aggregate_layers(params, weights)  host or device per-client layer lists -> per-layer outputs
 
 The scalar factors are formed on the host exactly as numpy forms them in the
@@ -480,7 +480,8 @@ def wait_round(state: ctypes.c_void_p, k: int, stream: torch.cuda.Stream) -> Non
 
 
 def _equal_stride_view(rows, host_ptrs: np.ndarray, P: int) -> Optional[torch.Tensor]:
-    """[N, P] view when the fp32 rows sit in ONE storage at a constant forward pitch.
+    """[N, P] view when the rows sit in ONE storage at a constant forward pitch
+    (a whole number of elements of the rows' dtype).
 
     A device-resident simulation usually hands over `X[i]` rows of one stacked
     tensor (or equal-size slices of one buffer): then the stacked fold reads
@@ -494,18 +495,24 @@ def _equal_stride_view(rows, host_ptrs: np.ndarray, P: int) -> Optional[torch.Te
     N = len(rows)
     if N < 2 or P == 0:
         return None
+    esize = rows[0].element_size()
     step = int(host_ptrs[1] - host_ptrs[0])
-    if step < P * 4 or step % 4:
+    if step < P * esize or step % esize:
         return None
     if (np.diff(host_ptrs) != step).any():
         return None
     base, last = rows[0], rows[-1]
     if last.untyped_storage().data_ptr() != base.untyped_storage().data_ptr():
         return None
-    return base.as_strided((N, P), (step // 4, 1))
+    return base.as_strided((N, P), (step // esize, 1))
 
 
 _dtype_of = operator.attrgetter("dtype")
+# dtypes the library folds through a device table of row pointers
+_ROW_TABLE_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+# process-wide route counters (diagnostics, as StreamingFold.stats): 16-bit folds
+# that ran through a row table, layer groups copied into a stacked matrix
+stats = {"rows16_folds": 0, "stacked_groups": 0}
 
 
 class RowSet:
@@ -518,7 +525,9 @@ class RowSet:
         tensor) become one [N, P] strided view: the stacked fold, no table;
       - other fp32 rows get a device table of row pointers for
         fa_fedavg_f32_ptrs_aligned (every row 16-B aligned) or
-        fa_fedavg_f32_ptrs (any alignment).
+        fa_fedavg_f32_ptrs (any alignment);
+      - other bfloat16 / float16 rows get the same table for
+        fa_fedavg_bf16_ptrs / fa_fedavg_f16_ptrs (`aligned` picks the kernels).
     fold_rows(rowset, weights) then costs the factor upload and the kernel.
     The RowSet keeps the tensors alive; their CONTENTS may change between
     folds, their storage may not (re-create the RowSet after reallocating)."""
@@ -544,7 +553,7 @@ class RowSet:
         self.ptrs = None
         self.host_ptrs = None
         self.aligned = False
-        if dt == torch.float32 and P > 0:
+        if dt in _ROW_TABLE_DTYPES and P > 0:
             host_ptrs = self.host_ptrs = np.fromiter(map(torch.Tensor.data_ptr, rows), dtype=np.int64, count=N)
             self.view = _equal_stride_view(rows, host_ptrs, P)
             if self.view is None:
@@ -557,26 +566,114 @@ class RowSet:
             return False
         lo = t.data_ptr()
         hi = lo + t.numel() * t.element_size()
-        return bool(np.any((self.host_ptrs < hi) & (lo < self.host_ptrs + self.P * 4)))
+        return bool(np.any((self.host_ptrs < hi) & (lo < self.host_ptrs + self.P * self.rows[0].element_size())))
 
     def stacked(self) -> torch.Tensor:
-        """The rows copied into one [N, P] tensor (the non-fp32 fallbacks)."""
+        """The rows copied into one [N, P] tensor (the fallbacks without a row-table fold)."""
         return torch.stack([r.reshape(-1) for r in self.rows])
 
 
+def _check_out(name: str, t: Optional[torch.Tensor], dt: torch.dtype, P: int) -> None:
+    if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= P):
+        raise ValueError(f"{name} must be a contiguous CUDA {dt} tensor of >= {P} elements")
+
+
+def _fold_rows_bf16(rs: "RowSet", weights, scores, out, total, want_bf16, out_bf16):
+    """bf16 rows through the row table (fa_fedavg_bf16_ptrs): the outputs and
+    the factors of fold_stacked's bf16 branch, no stacking copy."""
+    dev, P = rs.device, rs.P
+    _check_out("out", out, torch.float32, P)
+    _check_out("out_bf16", out_bf16, torch.bfloat16, P)
+    f = Factors.weak_f32(weights, scores, total) or Factors(weights, scores, np.dtype(np.float32), total=total)
+    # an output over a client row: the table lives in device memory, the library
+    # cannot see the alias.  Fold into a fresh buffer, then copy.
+    dst, dstb = out, out_bf16
+    if out is not None and rs.overlaps(out):
+        out = None
+    outb = None if (out_bf16 is not None and rs.overlaps(out_bf16)) else out_bf16
+    if outb is None and (want_bf16 or out_bf16 is not None):
+        outb = torch.empty(P, dtype=torch.bfloat16, device=dev)
+    if out is None and (dst is not None or outb is None or want_bf16):
+        out = torch.empty(P, dtype=torch.float32, device=dev)
+    aligned = rs.aligned and (out is None or out.data_ptr() % 16 == 0) and (outb is None or outb.data_ptr() % 16 == 0)
+    st = stream_ptr(dev)
+    if torch.cuda.is_current_stream_capturing():
+        a, s = _captured_factors(f, dev)
+        _lib.call("fa_fedavg_bf16_ptrs", rs.ptrs.data_ptr(), rs.N, P, a.data_ptr(), _ptr(s), float(f.div),
+                  int(aligned), _ptr(out), _ptr(outb), st)
+    else:
+        _lib.call("fa_fedavg_bf16_ptrs_hostf", rs.ptrs.data_ptr(), rs.N, P, *f.host(), float(f.div),
+                  int(aligned), _ptr(out), _ptr(outb), st)
+    stats["rows16_folds"] += 1
+    if dst is not None and dst is not out:
+        dst.reshape(-1)[:P].copy_(out)
+        out = dst
+    if dstb is not None and dstb is not outb:
+        dstb.reshape(-1)[:P].copy_(outb)
+        outb = dstb
+    if want_bf16:
+        return out, outb
+    if out_bf16 is not None:
+        return outb if out is None else (out, outb)
+    return out
+
+
+def _fold_rows_f16(rs: "RowSet", weights, scores, out, total):
+    """float16 rows whose result stays float16 through the row table
+    (fa_fedavg_f16_ptrs): the factors of fold_stacked's float16 branch."""
+    dev, P = rs.device, rs.P
+    if torch.cuda.is_current_stream_capturing():
+        raise InvalidParameterShapeError("the float16 fold does not run under stream capture "
+                                         "(the captured factor fill carries float32 factors only)")
+    _check_out("out", out, torch.float16, P)
+    dst = out
+    if out is not None and rs.overlaps(out):
+        out = None
+    if out is None:
+        out = torch.empty(P, dtype=torch.float16, device=dev)
+    f = Factors(weights, scores, np.dtype(np.float16), total=total)
+    a, s = f.to(dev)
+    aligned = rs.aligned and out.data_ptr() % 16 == 0
+    _lib.call("fa_fedavg_f16_ptrs", rs.ptrs.data_ptr(), rs.N, P, a.data_ptr(), _ptr(s),
+              int(np.asarray(f.div, dtype=np.float16).view(np.uint16)), int(aligned), out.data_ptr(),
+              stream_ptr(dev))
+    stats["rows16_folds"] += 1
+    if dst is not None and dst is not out:
+        dst.reshape(-1)[:P].copy_(out)
+        return dst
+    return out
+
+
 def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
-              out: Optional[torch.Tensor] = None, total=None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, total=None, want_bf16: bool = False,
+              out_bf16: Optional[torch.Tensor] = None):
     """The fold over separately allocated 1-D CUDA rows (no stacking copy for
-    fp32).  `rows` is a RowSet (prepared once, reusable) or a sequence of
-    tensors (a RowSet is built for this call)."""
+    fp32, bfloat16 and float16 rows whose result stays float16).  `rows` is a
+    RowSet (prepared once, reusable) or a sequence of tensors (a RowSet is
+    built for this call).  want_bf16 / out_bf16: as fold_stacked (bf16 rows)."""
     rs = rows if isinstance(rows, RowSet) else RowSet(rows)
     if len(weights) != rs.N or (scores is not None and len(scores) != rs.N):
         raise InvalidParameterShapeError(f"{rs.N} rows but {len(weights)} weights"
                                          + ("" if scores is None else f" / {len(scores)} scores"))
+    if out_bf16 is not None and rs.dtype != torch.bfloat16:
+        raise InvalidParameterShapeError("out_bf16 is for bfloat16 rows")
+    if rs.dtype == torch.bfloat16:
+        if rs.view is not None or rs.P == 0:
+            # rows of one allocation at a fixed pitch: the stacked fold, no pointer table
+            X = rs.view if rs.view is not None else rs.stacked()
+            return fold_stacked(X, weights, scores, out=out, total=total, want_bf16=want_bf16, out_bf16=out_bf16)
+        return _fold_rows_bf16(rs, weights, scores, out, total, want_bf16, out_bf16)
+    if (rs.dtype == torch.float16 and rs.view is None and rs.P > 0
+            and result_dtype(np.dtype(np.float16), weights, scores, total) == np.float16):
+        return _fold_rows_f16(rs, weights, scores, out, total)
     fw = Factors.weak_f32(weights, scores, total) if rs.dtype == torch.float32 else None
     if fw is None and (rs.dtype != torch.float32
                        or result_dtype(np.dtype(np.float32), weights, scores, total) != np.float32):
-        return fold_stacked(rs.stacked(), weights, scores, out=out, total=total)
+        # no row-table fold for this dtype / these factors (float16 rows under
+        # numpy-scalar weights promote): the stacked fold, over the rows' own
+        # storage when they sit at a fixed pitch, else over a stacked copy
+        X = rs.view if rs.view is not None else rs.stacked()
+        return fold_stacked(X, weights, scores, out=out, total=total)
     if rs.view is not None or rs.P == 0:
         # rows of one allocation at a fixed pitch: the stacked fold, no pointer table
         X = rs.view if rs.view is not None else rs.stacked()
@@ -625,6 +722,21 @@ def _layer_meta(parameters, n_eff):
         shapes.append(shp)
         dtypes.append(dt)
     return L, shapes, dtypes
+
+
+def _rows_route(dt, fp32_result: bool, w, sc, total, where: torch.device, dev) -> bool:
+    """Does a group of device layers of dtype dt fold per layer through
+    fold_rows' row tables (no stacked copy)?  fp32 layers whose result stays
+    fp32; bf16 layers (always float32 factors); float16 layers whose result
+    stays float16.  The 16-bit groups only where the layers already lie on the
+    device the fold was asked for (the stacked copy is what moves them)."""
+    if dt == torch.float32:
+        return fp32_result
+    d = torch.device(dev)
+    here = where.type == d.type and where.index == (d.index if d.index is not None else torch.cuda.current_device())
+    if dt == torch.bfloat16:
+        return here
+    return dt == torch.float16 and here and result_dtype(np.dtype(np.float16), w, sc, total) == np.float16
 
 
 def _multi(devices) -> Optional[list]:
@@ -684,10 +796,12 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
                     off += n
                 continue
             res = _stream_group(parameters, n_eff, lis, P, w, sc, sum(total_weights), dev)
-        elif on_device and dtypes[lis[0]] == torch.float32 and fp32_result and all(
+        elif on_device and _rows_route(dtypes[lis[0]], fp32_result, w, sc, sum(total_weights),
+                                       parameters[0][lis[0]].device, dev) and all(
                 parameters[i][li].is_contiguous() for i in range(n_eff) for li in lis):
-            # device fp32 layers: fold each layer straight from the clients' own
-            # tensors through a row-pointer list -- no stacking copy
+            # device fp32 / bf16 layers, and float16 layers whose result stays
+            # float16: fold each layer straight from the clients' own tensors
+            # through a row-pointer list -- no stacking copy
             for li in lis:
                 rows = [parameters[i][li].reshape(-1) for i in range(n_eff)]
                 outs[li] = fold_rows(rows, w, sc, total=sum(total_weights)).reshape(shapes[li])
@@ -826,6 +940,7 @@ def _stream_group_multi(parameters, n, lis, P, w, sc, total, devices) -> np.ndar
 
 def _stack_group(parameters, n, lis, sizes, P, dev, on_device) -> torch.Tensor:
     ldx = ((P + ROW_ALIGN - 1) // ROW_ALIGN) * ROW_ALIGN
+    stats["stacked_groups"] += 1
     if on_device:
         ref = parameters[0][lis[0]]
         X = torch.empty((n, ldx), dtype=ref.dtype, device=dev)

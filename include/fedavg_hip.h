@@ -133,6 +133,27 @@ int fa_fedavg_f16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
                   const uint16_t* a, const uint16_t* s, uint16_t divisor,
                   uint16_t* out, void* stream);
 
+/* The 16-bit folds over N separately allocated client rows (new symbols, ABI
+ * still 7): xi is a [device] array of N [device] pointers, each to P bf16 /
+ * binary16 elements -- the list-of-arrays form the reference passes
+ * (fed_avg_aggregator.py:32-35), folded where the rows lie, with no stacking
+ * copy.  rows_aligned != 0 is the caller's promise that every row and every
+ * given output is 16-B aligned and takes the octet kernels (a fixed form per
+ * shape, not measured); with 0 rows and outputs may sit at any 2-B offset and
+ * one lane folds a column.  Bit for bit the result of fa_fedavg_bf16 /
+ * fa_fedavg_f16 over the same rows stacked, with either kernel.  Argument
+ * checks and status codes as fa_fedavg_f32_ptrs and the stacked 16-bit folds
+ * (both bf16 outputs NULL -> FA_ERR_ARG; rows_aligned != 0 with an output off
+ * 16-B alignment -> FA_ERR_ARG).  The table lives in device memory, so the
+ * library cannot see an alias: no output may overlap a row -- as the
+ * reference, which returns new arrays. */
+int fa_fedavg_bf16_ptrs(const uint16_t* const* xi, int64_t N, int64_t P,
+                        const float* a, const float* s, float divisor, int rows_aligned,
+                        float* out_f32, uint16_t* out_bf16, void* stream);
+int fa_fedavg_f16_ptrs(const uint16_t* const* xi, int64_t N, int64_t P,
+                       const uint16_t* a, const uint16_t* s, uint16_t divisor, int rows_aligned,
+                       uint16_t* out, void* stream);
+
 /* ---- one launch per exchange step (ABI 3) -----------------------------------
  * At N > 1 a rank folds its columns in `rounds` slots and all-gathers each
  * slot while the next one folds (fedlesscan_amd/sharding.py).  Folding each
@@ -254,6 +275,12 @@ int fa_fedavg_f32_ptrs_hostf(const float* const* xi, int64_t N, int64_t P,
 int fa_fedavg_bf16_hostf(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
                          const float* a, const float* s, float divisor,
                          float* out_f32, uint16_t* out_bf16, void* stream);
+/* fa_fedavg_bf16_ptrs (the list-of-arrays form, fed_avg_aggregator.py:32-35)
+ * with a and s in [host] memory, staged like the entries above: the bits of
+ * fa_fedavg_bf16 over the same rows stacked; no output may overlap a row. */
+int fa_fedavg_bf16_ptrs_hostf(const uint16_t* const* xi, int64_t N, int64_t P,
+                              const float* a, const float* s, float divisor, int rows_aligned,
+                              float* out_f32, uint16_t* out_bf16, void* stream);
 /* The _hostf entries refuse a capturing stream (FA_ERR_ARG, ABI 6): a graph
  * would have to own the staged copy.  Under capture, write the factors into
  * memory the graph owns (PyTorch: a tensor allocated inside the capture) with

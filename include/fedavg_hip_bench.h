@@ -72,6 +72,17 @@ int fa_num_f16_forms(void);
 const char* fa_f16_form_name(int form);
 int fa_fedavg_f16_form(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
                        uint16_t divisor, uint16_t* out, void* stream, int form);
+/* The 16-bit row-table folds (fa_fedavg_bf16_ptrs / fa_fedavg_f16_ptrs) with
+ * one form by index: the octet forms (rows16_gsbal_u*c*: rows_aligned != 0 and
+ * 16-B aligned outputs, else FA_ERR_ARG) and the column form (any alignment);
+ * form -1 runs what the product entry runs for rows_aligned. */
+int fa_num_rows16_forms(void);
+const char* fa_rows16_form_name(int form);
+int fa_fedavg_bf16_ptrs_form(const uint16_t* const* xi, int64_t N, int64_t P, const float* a, const float* s,
+                             float divisor, int rows_aligned, float* out_f32, uint16_t* out_bf16, void* stream,
+                             int form);
+int fa_fedavg_f16_ptrs_form(const uint16_t* const* xi, int64_t N, int64_t P, const uint16_t* a, const uint16_t* s,
+                            uint16_t divisor, int rows_aligned, uint16_t* out, void* stream, int form);
 /* Same for the bf16 fold (variant 0 = fa_fedavg_bf16). */
 int fa_fedavg_bf16_variant(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
                            const float* a, const float* s, float divisor,
