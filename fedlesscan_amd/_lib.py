@@ -54,6 +54,7 @@ _PROTOS = {
     "fa_finalize_f32": (_int, [_vp, _f32, _vp, _i64, _vp]),
     "fa_fedavg_bf16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp]),
     "fa_fedavg_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_uint16, _vp, _vp]),
+    "fa_fold_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, ctypes.c_uint16, _int, _vp, _vp]),
     "fa_fedavg_bf16_ptrs": (_int, [_vp, _i64, _i64, _vp, _vp, _f32, _int, _vp, _vp, _vp]),
     "fa_fedavg_bf16_ptrs_hostf": (_int, [_vp, _i64, _i64, _vp, _vp, _f32, _int, _vp, _vp, _vp]),
     "fa_fedavg_f16_ptrs": (_int, [_vp, _i64, _i64, _vp, _vp, ctypes.c_uint16, _int, _vp, _vp]),
@@ -102,6 +103,10 @@ _PROTOS = {
     "fa_ingest_add": (_int, [_vp, _vp, _vp, _i64, _f32, _f32, _int]),
     "fa_ingest_finish": (_int, [_vp, _f32]),
     "fa_ingest_destroy": (_int, [_vp]),
+    "fa_ingest_create_f16": (_int, [_vp, _i64, _i64, _int, _int]),
+    "fa_ingest_begin_f16": (_int, [_vp, _vp, _vp, _i64]),
+    "fa_ingest_add_f16": (_int, [_vp, _vp, _vp, _i64, ctypes.c_uint16, ctypes.c_uint16, _int]),
+    "fa_ingest_finish_f16": (_int, [_vp, ctypes.c_uint16]),
 }
 
 # libfedavg_hip_bench.so (include/fedavg_hip_bench.h)

@@ -257,6 +257,11 @@ int fa_fedavg_f16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const ui
     return f16_auto(X, N, P, ldx, a, s, divisor, out, stream);
 }
 
+int fa_fold_f16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
+                const uint16_t* acc_in, uint16_t divisor, int finalize, uint16_t* out, void* stream) {
+    return f16_fold(X, N, P, ldx, a, s, acc_in, divisor, finalize, out, stream);
+}
+
 int fa_fedavg_bf16_ptrs(const uint16_t* const* xi, int64_t N, int64_t P, const float* a, const float* s,
                         float divisor, int rows_aligned, float* out_f32, uint16_t* out_bf16, void* stream) {
     return bf16_rows_fold(xi, N, P, a, s, divisor, rows_aligned, out_f32, out_bf16, stream);

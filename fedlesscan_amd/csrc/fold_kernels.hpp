@@ -1811,6 +1811,127 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f16_scalar(
     out[c] = fold_column_f16<SCORED>(X + c, N, ldx, a, s, divisor);
 }
 
+// ---------------------------------------------------------------------------
+// float16 chunked fold (fa_fold_f16): fold_octets_f16 / fold_column_f16 with
+// the ACC / FIN switches of the fp32 fold_quads, as functions of their own so
+// that the stacked kernels above keep their code.
+//   ACC: the fold continues from acc_in (halves; may alias out: a lane reads
+//        its own octets before it writes them); !ACC: acc = t_0, not 0 + t_0,
+//        so a column of -0.0 stays -0.0.
+//   FIN: out = fl16(acc / divisor) (div_h8); !FIN: out = acc as halves.  Every
+//        add already rounds to binary16, so the halves carried from one chunk
+//        to the next are the accumulator itself: any cut of the rows gives the
+//        bits of one fa_fedavg_f16 over all of them.
+// The same packed-half multiply and add, the factor_h factor reads and the
+// non-temporal row loads.  The partial accumulator is stored with plain stores
+// (the next chunk's fold reads it back), the final result non-temporally.
+// ---------------------------------------------------------------------------
+template <bool FIN>
+__device__ __forceinline__ void st_h8(u32x4* out, f16x8 acc, float divisor) {
+    if constexpr (FIN) st16(out, __builtin_bit_cast(u32x4, div_h8(acc, divisor)));
+    else *out = __builtin_bit_cast(u32x4, acc);
+}
+
+template <int U, int C, bool SCORED, bool ACC, bool FIN>
+__device__ __forceinline__ void fold_octets_f16_chunk(const u32x4* __restrict__ p, int64_t ldo, int64_t N,
+                                                      const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
+                                                      const u32x4* acc_in, float divisor, u32x4* out) {
+    f16x8 acc[C];
+    int64_t i = 0;
+    if constexpr (ACC) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = __builtin_bit_cast(f16x8, acc_in[c * kBlock]);
+    } else {
+        const _Float16 a0 = factor_h(a, 0), s0 = SCORED ? factor_h(s, 0) : (_Float16)1;
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = term_h8<SCORED>(ld_h8(p + c * kBlock), a0, s0);
+        i = 1;
+    }
+    for (; i + U <= N; i += U) {
+        u32x4 v[U][C];
+        octets_ld<U, C>(v, p, i, ldo);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const _Float16 ai = factor_h(a, i + u), si = SCORED ? factor_h(s, i + u) : (_Float16)1;
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(__builtin_bit_cast(f16x8, v[u][c]), ai, si);
+        }
+    }
+    for (; i < N; ++i) {
+        const _Float16 ai = factor_h(a, i), si = SCORED ? factor_h(s, i) : (_Float16)1;
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(ld_h8(p + i * ldo + c * kBlock), ai, si);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) st_h8<FIN>(out + c * kBlock, acc[c], divisor);
+}
+
+// One column of the chunked fold (the P % 8 tail lane and the scalar kernel)
+template <bool SCORED, bool ACC, bool FIN>
+__device__ __forceinline__ uint16_t fold_column_f16_chunk(const uint16_t* __restrict__ X, int64_t N, int64_t ldx,
+                                                          const uint16_t* __restrict__ a,
+                                                          const uint16_t* __restrict__ s, const uint16_t* acc_in,
+                                                          float divisor) {
+    _Float16 acc;
+    int64_t i = 0;
+    if constexpr (ACC) {
+        acc = h_bits(*acc_in);
+    } else {
+        acc = term_h1<SCORED>(h_bits(X[0]), factor_h(a, 0), SCORED ? factor_h(s, 0) : (_Float16)1);
+        i = 1;
+    }
+    for (; i < N; ++i)
+        acc = acc + term_h1<SCORED>(h_bits(X[i * ldx]), factor_h(a, i), SCORED ? factor_h(s, i) : (_Float16)1);
+    return bits_h(FIN ? div_h1(acc, divisor) : acc);
+}
+
+// Grid-stride over octet tiles (the tiling of f16_tile: C octets per lane spaced
+// kBlock apart, a partial last tile octet by octet, the P % 8 columns on the
+// lane with o0 == P / 8), balanced passes set by the launch.
+template <int U, int C, bool SCORED, bool ACC, bool FIN>
+__global__ __launch_bounds__(kBlock) void k_fold_f16_gs(
+    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
+    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
+    const uint16_t* acc_in, float divisor, uint16_t* out, int64_t ntiles) {  // acc_in may alias out
+    const int64_t no = P >> 3;  // full octets
+    const int64_t ldo = ldx >> 3;
+    const u32x4* X8 = reinterpret_cast<const u32x4*>(X);
+    const u32x4* A8 = reinterpret_cast<const u32x4*>(acc_in);
+    u32x4* O8 = reinterpret_cast<u32x4*>(out);
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+        const int64_t o0 = bid * (kBlock * C) + threadIdx.x;
+        if (o0 + (int64_t)(C - 1) * kBlock < no) {
+            fold_octets_f16_chunk<U, C, SCORED, ACC, FIN>(X8 + o0, ldo, N, a, s, ACC ? A8 + o0 : nullptr, divisor,
+                                                          O8 + o0);
+            continue;
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const int64_t o = o0 + (int64_t)c * kBlock;
+            if (o < no)
+                fold_octets_f16_chunk<U, 1, SCORED, ACC, FIN>(X8 + o, ldo, N, a, s, ACC ? A8 + o : nullptr, divisor,
+                                                              O8 + o);
+        }
+        const int64_t tb = no / (kBlock * C), tl = (no % (kBlock * C)) % kBlock;
+        if ((P & 7) && bid == tb && (int64_t)threadIdx.x == tl)
+            for (int64_t col = no * 8; col < P; ++col)
+                out[col] = fold_column_f16_chunk<SCORED, ACC, FIN>(X + col, N, ldx, a, s, ACC ? acc_in + col : nullptr,
+                                                                   divisor);
+    }
+}
+
+// chunked fold, one column per lane: rows, accumulator or output at any 2-B
+// offset, any pitch
+template <bool SCORED, bool ACC, bool FIN>
+__global__ __launch_bounds__(kBlock) void k_fold_f16_scalar(
+    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
+    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
+    const uint16_t* acc_in, float divisor, uint16_t* out) {  // acc_in may alias out
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P) return;
+    out[c] = fold_column_f16_chunk<SCORED, ACC, FIN>(X + c, N, ldx, a, s, ACC ? acc_in + c : nullptr, divisor);
+}
+
 // float16 list-of-rows form with every row 16-B aligned (fa_fedavg_f16_ptrs,
 // rows_aligned != 0): fold_octets_f16 with row i's base read from xi[i] (a
 // wave-uniform scalar load); the packed-half arithmetic, the float32 divisor
@@ -3632,6 +3753,73 @@ inline int f16_auto(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const 
                     return FA_OK;
                 });
     return check_launch("fedavg_f16");
+}
+
+// The float16 chunked fold (fa_fold_f16).  One form, fixed by shape, no tuner
+// kind: the chunks the ingest pipe sends have 1 to a few dozen rows over the
+// whole model width, so the loads in flight have to come from the columns, not
+// from a long row run: 2 octets per lane with 4 rows ahead (8 x 16 B per lane,
+// 8 KiB of every row per tile), grid-stride with balanced passes, at most one
+// block per CU.  A 1M-parameter model is then 245 tiles, one pass on 256 CUs;
+// 4 or 8 octets per lane would leave most CUs without a tile at that width
+// (DESIGN.md 5 float16).  Rows, accumulator or output off 16-B alignment, or a
+// pitch that is no multiple of 8: one column per lane.
+constexpr int kFoldF16U = 4, kFoldF16C = 2;
+
+template <bool SC, bool ACC, bool FIN>
+void launch_fold_f16(hipStream_t st, bool vec, const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
+                     const uint16_t* a, const uint16_t* s, const uint16_t* acc_in, float d, uint16_t* out) {
+    if (!vec) {
+        hipLaunchKernelGGL((k_fold_f16_scalar<SC, ACC, FIN>), grid_for(P), dim3(kBlock), 0, st, X, N, P, ldx, a, s,
+                           acc_in, d, out);
+        return;
+    }
+    // tiles incl. the column-tail lane's; the fewest blocks (at most one per
+    // CU) that finish in the same number of passes
+    const int64_t per_block = (int64_t)kBlock * kFoldF16C, units = (P >> 3) + ((P & 7) ? 1 : 0);
+    const int64_t tiles = (units + per_block - 1) / per_block;
+    int64_t g = cu_count();
+    if (g > tiles) g = tiles;
+    const int64_t passes = (tiles + g - 1) / g;
+    g = (tiles + passes - 1) / passes;
+    hipLaunchKernelGGL((k_fold_f16_gs<kFoldF16U, kFoldF16C, SC, ACC, FIN>), dim3((unsigned)g), dim3(kBlock), 0, st,
+                       X, N, P, ldx, a, s, acc_in, d, out, tiles);
+}
+
+inline int f16_fold(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
+                    const uint16_t* acc_in, uint16_t divisor, int finalize, uint16_t* out, void* stream) {
+    if (!(acc_in && N == 0)) {
+        int rc = check_common(N, P, ldx, X, a, out);
+        if (rc) return rc;
+    } else if (P < 0) {
+        return fail(FA_ERR_ARG, "negative size (N=0, P=%lld)", (long long)P);
+    } else if (P > 0 && !out) {
+        return fail(FA_ERR_ARG, "null out pointer");
+    }
+    if (P == 0) { g_err[0] = 0; return FA_OK; }
+    hipStream_t st = (hipStream_t)stream;
+    {
+        // the factors are halves and fa_factors_fill, the captured staging,
+        // carries float32 only: a graph could not own this fold's factors
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone)
+            return fail(FA_ERR_ARG, "fa_fold_f16 does not run under graph capture");
+    }
+    StreamDevice on_stream_device(stream);
+    const float d = half_bits_to_float(divisor);
+    const bool sc = s != nullptr, acc = acc_in != nullptr, fin = finalize != 0;
+    const bool vec = (N == 0 || aligned16(X)) && (ldx % 8 == 0) && aligned16(out) && (!acc || aligned16(acc_in));
+#define FA_FH(SC, ACC, FIN) launch_fold_f16<SC, ACC, FIN>(st, vec, X, N, P, ldx, a, s, acc_in, d, out)
+    if (sc) {
+        if (acc) { if (fin) FA_FH(true, true, true); else FA_FH(true, true, false); }
+        else     { if (fin) FA_FH(true, false, true); else FA_FH(true, false, false); }
+    } else {
+        if (acc) { if (fin) FA_FH(false, true, true); else FA_FH(false, true, false); }
+        else     { if (fin) FA_FH(false, false, true); else FA_FH(false, false, false); }
+    }
+#undef FA_FH
+    return check_launch("fa_fold_f16");
 }
 
 // ---- the 16-bit row-table folds (fa_fedavg_bf16_ptrs, fa_fedavg_f16_ptrs) ----

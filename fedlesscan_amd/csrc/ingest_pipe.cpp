@@ -1,7 +1,8 @@
 // ingest_pipe.cpp — native streaming ingest for libfedavg_hip.so:
 // client rows in host memory -> packed into page-locked slots by a persistent
 // worker pool -> one DMA per slot on a copy stream -> the in-order chunked fold
-// (fa_fold_f32) on the caller's compute stream.
+// (fa_fold_f32, or fa_fold_f16 for a float16 pipe) on the caller's compute
+// stream.
 //
 // Reference path replaced: the strategies' aggregate() materialises every
 // decoded client (fed_avg_aggregator.py:64-92, stall_aware_aggregation.py:
@@ -12,7 +13,10 @@
 // one before (GPU) all overlap.  Slots are filled and folded strictly in row
 // order with the accumulator carried across them, so the result is
 // bit-identical to one fa_fedavg_f32 over all rows (the property fa_fold_f32
-// documents).
+// documents).  A pipe has an element kind: float32 rows with float factors and
+// a float accumulator, or binary16 rows (the *_f16 entries) with binary16
+// factors and accumulator; everything else -- slots, ramps, packing, the
+// issuer, abandon and reuse -- is shared and counts in bytes.
 //
 // Threads: the caller's thread (add / finish, which block only for
 // backpressure: a slot is refilled after its fold has completed), one issuer
@@ -116,11 +120,13 @@ constexpr int64_t kTaskBytes = 1 << 20;  // one copy task: >= 1 MiB keeps the po
 
 enum class SlotState { kFree, kFilling, kQueued, kIssued };
 
+enum Kind { kF32 = 0, kF16 = 1 };
+
 struct Slot {
-    float* host = nullptr;      // [R][ldx] page-locked
-    float* dev = nullptr;       // [R][ldx]
-    float* fac_host = nullptr;  // [2][R] page-locked: a, then s (the head of the slot's one allocation)
-    float* fac_dev = nullptr;   // [2][R]
+    uint8_t* host = nullptr;      // [R][ldx] elements, page-locked
+    uint8_t* dev = nullptr;       // [R][ldx]
+    uint8_t* fac_host = nullptr;  // [2][R] factors, page-locked: a, then s (the head of the slot's one allocation)
+    uint8_t* fac_dev = nullptr;   // [2][R]
     hipEvent_t h2d_done = nullptr, fold_done = nullptr;
     SlotState state = SlotState::kFree;
     int64_t rows = 0;
@@ -138,13 +144,15 @@ struct QueueItem {
 
 struct fa_ingest {
     int64_t P = 0, ldx = 0, R = 0;
-    int64_t fac_pad = 0;  // floats of factors (2R) rounded up to 64: the rows stay 256-B aligned
+    int kind = kF32;
+    int64_t elem = 4;       // bytes of a row element, and of a factor
+    int64_t fac_bytes = 0;  // the factors (2R elements) rounded up to 256 B: the rows stay 256-B aligned
     int K = 0, device = 0;
     std::vector<Slot> slots;
     hipStream_t copy[2] = {nullptr, nullptr};  // chunks alternate between two copy streams
     int64_t issued = 0;                         // chunks issued (issuer thread)
     // per round
-    float* acc = nullptr;
+    void* acc = nullptr;  // float* or, for a float16 pipe, uint16_t*
     hipStream_t compute = nullptr;
     int cur = 0;
     int64_t rows = 0;
@@ -153,6 +161,7 @@ struct fa_ingest {
     bool started = false;  // acc holds a partial fold (issuer side)
     int scored = -1;       // -1 unknown, 0 FedAvg, 1 stall-aware
     float divisor = 0.f;
+    uint16_t divisor_h = 0;  // a float16 pipe's divisor (binary16 bits)
     // issuer
     std::thread issuer;
     std::mutex mu;
@@ -184,7 +193,11 @@ int hip_err(fa_ingest* p, const char* what, hipError_t e) {
 // issuer thread, in queue (= row) order.
 int issue(fa_ingest* p, const QueueItem& it) {
     if (it.slot < 0) {  // every row was in earlier slots: divide only
-        return fa_fold_f32(nullptr, 0, p->P, p->ldx, nullptr, nullptr, p->acc, p->divisor, 1, p->acc, p->compute);
+        if (p->kind == kF16)
+            return fa_fold_f16(nullptr, 0, p->P, p->ldx, nullptr, nullptr, (const uint16_t*)p->acc, p->divisor_h, 1,
+                               (uint16_t*)p->acc, p->compute);
+        return fa_fold_f32(nullptr, 0, p->P, p->ldx, nullptr, nullptr, (const float*)p->acc, p->divisor, 1,
+                           (float*)p->acc, p->compute);
     }
     Slot& S = p->slots[it.slot];
     {
@@ -199,14 +212,22 @@ int issue(fa_ingest* p, const QueueItem& it) {
     // started ~17 us after the previous one ended (profiles/r03_e2e_trace/);
     // the fold of each chunk still waits for exactly its own transfer.
     hipStream_t cs = p->copy[p->issued++ & 1];
-    hipError_t e = hipMemcpyAsync(S.fac_dev, S.fac_host, (size_t)(p->fac_pad + S.rows * p->ldx) * sizeof(float),
+    hipError_t e = hipMemcpyAsync(S.fac_dev, S.fac_host, (size_t)(p->fac_bytes + S.rows * p->ldx * p->elem),
                                   hipMemcpyHostToDevice, cs);
     if (e == hipSuccess) e = hipEventRecord(S.h2d_done, cs);
     if (e == hipSuccess) e = hipStreamWaitEvent(p->compute, S.h2d_done, 0);
     if (e != hipSuccess) return hip_err(p, "ingest H2D", e);
-    const int rc = fa_fold_f32(S.dev, S.rows, p->P, p->ldx, S.fac_dev, S.has_s ? S.fac_dev + p->R : nullptr,
-                               p->started ? p->acc : nullptr, it.final_chunk ? p->divisor : 0.f,
-                               it.final_chunk ? 1 : 0, p->acc, p->compute);
+    const uint8_t* sdev = S.has_s ? S.fac_dev + p->R * p->elem : nullptr;
+    int rc;
+    if (p->kind == kF16)
+        rc = fa_fold_f16((const uint16_t*)S.dev, S.rows, p->P, p->ldx, (const uint16_t*)S.fac_dev,
+                         (const uint16_t*)sdev, p->started ? (const uint16_t*)p->acc : nullptr,
+                         it.final_chunk ? p->divisor_h : (uint16_t)0, it.final_chunk ? 1 : 0, (uint16_t*)p->acc,
+                         p->compute);
+    else
+        rc = fa_fold_f32((const float*)S.dev, S.rows, p->P, p->ldx, (const float*)S.fac_dev, (const float*)sdev,
+                         p->started ? (const float*)p->acc : nullptr, it.final_chunk ? p->divisor : 0.f,
+                         it.final_chunk ? 1 : 0, (float*)p->acc, p->compute);
     if (rc != FA_OK) return set_err(p, rc, std::string("ingest fold: ") + fa_last_error());
     p->started = true;
     e = hipEventRecord(S.fold_done, p->compute);
@@ -290,11 +311,7 @@ int report(fa_ingest* p) {
     return fa_internal_fail(p->err, p->errmsg.c_str());
 }
 
-}  // namespace
-
-extern "C" {
-
-int fa_ingest_create(fa_ingest** out, int64_t P, int64_t chunk_bytes, int slots, int device) {
+int create_pipe(fa_ingest** out, int64_t P, int64_t chunk_bytes, int slots, int device, int kind) {
     if (!out || P <= 0 || chunk_bytes <= 0 || slots < 2 || slots > 64 || device < 0)
         return fa_internal_fail(FA_ERR_ARG, "fa_ingest_create: bad arguments");
     *out = nullptr;
@@ -305,21 +322,23 @@ int fa_ingest_create(fa_ingest** out, int64_t P, int64_t chunk_bytes, int slots,
     }
     fa_ingest* p = new fa_ingest();
     p->P = P;
-    p->ldx = (P + 63) / 64 * 64;  // 256-B row pitch: the vector folds
-    p->R = std::max<int64_t>(1, chunk_bytes / (p->ldx * (int64_t)sizeof(float)));
+    p->kind = kind;
+    p->elem = kind == kF16 ? 2 : 4;
+    p->ldx = (P + 63) / 64 * 64;  // a row pitch of 64 elements (256 / 128 B): the vector folds
+    p->R = std::max<int64_t>(1, chunk_bytes / (p->ldx * p->elem));
     p->K = slots;
-    p->fac_pad = (2 * p->R + 63) / 64 * 64;
+    p->fac_bytes = (2 * p->R * p->elem + 255) / 256 * 256;
     p->device = device;
     p->slots = std::vector<Slot>(slots);
     hipError_t e = hipStreamCreateWithFlags(&p->copy[0], hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->copy[1], hipStreamNonBlocking);
     for (Slot& S : p->slots) {
-        const size_t rowbytes = (size_t)(p->R * p->ldx) * sizeof(float), facbytes = (size_t)p->fac_pad * sizeof(float);
+        const size_t rowbytes = (size_t)(p->R * p->ldx * p->elem), facbytes = (size_t)p->fac_bytes;
         if (e == hipSuccess) e = hipHostMalloc((void**)&S.fac_host, facbytes + rowbytes, hipHostMallocDefault);
         if (e == hipSuccess) e = hipMalloc((void**)&S.fac_dev, facbytes + rowbytes);
         if (e == hipSuccess) {
-            S.host = S.fac_host + p->fac_pad;  // rows start 256-B aligned after the factors
-            S.dev = S.fac_dev + p->fac_pad;
+            S.host = S.fac_host + p->fac_bytes;  // rows start 256-B aligned after the factors
+            S.dev = S.fac_dev + p->fac_bytes;
         }
         if (e == hipSuccess) e = hipEventCreateWithFlags(&S.h2d_done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&S.fold_done, hipEventDisableTiming);
@@ -339,10 +358,14 @@ int fa_ingest_create(fa_ingest** out, int64_t P, int64_t chunk_bytes, int slots,
     return FA_OK;
 }
 
-int fa_ingest_rows_per_chunk(const fa_ingest* p) { return p ? (int)p->R : 0; }
+int wrong_kind(const char* entry) {
+    return fa_internal_fail(FA_ERR_ARG, (std::string(entry) + ": the pipe was created for the other element kind "
+                                                              "(float32 / float16 entries do not mix)").c_str());
+}
 
-int fa_ingest_begin(fa_ingest* p, float* acc, void* stream, int64_t expected_rows) {
+int begin_round(fa_ingest* p, void* acc, void* stream, int64_t expected_rows, int kind) {
     if (!p || !acc || expected_rows < 0) return fa_internal_fail(FA_ERR_ARG, "fa_ingest_begin: bad arguments");
+    if (p->kind != kind) return wrong_kind("fa_ingest_begin");
     {  // a round abandoned half-way (an error in add, or no finish) may still
        // have chunks queued and copies running, and a slot half filled: they
        // drain first (the issuer stops issuing once the round has failed), and
@@ -374,9 +397,11 @@ int fa_ingest_begin(fa_ingest* p, float* acc, void* stream, int64_t expected_row
     return FA_OK;
 }
 
-int fa_ingest_add(fa_ingest* p, const void* const* srcs, const int64_t* sizes, int64_t n, float a, float s,
-                  int has_s) {
+// a, s: the row's factors as p->elem bytes each (s is read only with has_s)
+int add_row(fa_ingest* p, const void* const* srcs, const int64_t* sizes, int64_t n, const void* a, const void* s,
+            int has_s, int kind) {
     if (!p || n < 0 || (n > 0 && (!srcs || !sizes))) return fa_internal_fail(FA_ERR_ARG, "fa_ingest_add: bad arguments");
+    if (p->kind != kind) return wrong_kind("fa_ingest_add");
     if (p->scored >= 0 && p->scored != (has_s ? 1 : 0))
         return fa_internal_fail(FA_ERR_SHAPE, "either every row has a score or none does");
     int64_t total = 0;
@@ -384,8 +409,9 @@ int fa_ingest_add(fa_ingest* p, const void* const* srcs, const int64_t* sizes, i
         if (sizes[i] < 0 || (sizes[i] && !srcs[i])) return fa_internal_fail(FA_ERR_ARG, "fa_ingest_add: bad piece");
         total += sizes[i];
     }
-    if (total != p->P * (int64_t)sizeof(float))
-        return fa_internal_fail(FA_ERR_SHAPE, "fa_ingest_add: row bytes != P * 4");
+    if (total != p->P * p->elem)
+        return fa_internal_fail(FA_ERR_SHAPE, kind == kF16 ? "fa_ingest_add: row bytes != P * 2"
+                                                           : "fa_ingest_add: row bytes != P * 4");
     if (int rc = report(p)) return rc;
     p->scored = has_s ? 1 : 0;
     Slot& S = p->slots[p->cur];
@@ -403,12 +429,15 @@ int fa_ingest_add(fa_ingest* p, const void* const* srcs, const int64_t* sizes, i
     }
     const int64_t r = S.rows++;
     S.has_s = has_s != 0;
-    S.fac_host[r] = a;
-    S.fac_host[p->R + r] = has_s ? s : 1.0f;
+    const float one_f = 1.0f;
+    const uint16_t one_h = 0x3C00u;  // binary16 1.0
+    memcpy(S.fac_host + r * p->elem, a, (size_t)p->elem);
+    memcpy(S.fac_host + (p->R + r) * p->elem,
+           has_s ? s : (kind == kF16 ? (const void*)&one_h : (const void*)&one_f), (size_t)p->elem);
     // copy tasks of 1 MiB, split across pieces and inside large pieces; 256 KiB
     // while the round's first chunks ramp up (the first DMA waits for them)
     const int64_t task_bytes = p->chunks <= 2 ? kTaskBytes / 4 : kTaskBytes;
-    uint8_t* dst = reinterpret_cast<uint8_t*>(S.host + r * p->ldx);
+    uint8_t* dst = S.host + r * p->ldx * p->elem;
     int64_t off = 0;
     struct Part { const uint8_t* src; uint8_t* dst; int64_t n; };
     std::vector<Part> batch;
@@ -445,10 +474,12 @@ int fa_ingest_add(fa_ingest* p, const void* const* srcs, const int64_t* sizes, i
     return FA_OK;
 }
 
-int fa_ingest_finish(fa_ingest* p, float divisor) {
+int finish_round(fa_ingest* p, float divisor, uint16_t divisor_h, int kind) {
     if (!p) return fa_internal_fail(FA_ERR_ARG, "fa_ingest_finish: bad arguments");
+    if (p->kind != kind) return wrong_kind("fa_ingest_finish");
     if (p->rows == 0) return fa_internal_fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
     p->divisor = divisor;  // read by the issuer for the final item, which is queued below
+    p->divisor_h = divisor_h;
     Slot& S = p->slots[p->cur];
     if (S.state == SlotState::kFilling && S.rows > 0) {
         enqueue(p, p->cur, true);
@@ -465,6 +496,38 @@ int fa_ingest_finish(fa_ingest* p, float divisor) {
     }
     return report(p);
 }
+
+}  // namespace
+
+extern "C" {
+
+int fa_ingest_create(fa_ingest** out, int64_t P, int64_t chunk_bytes, int slots, int device) {
+    return create_pipe(out, P, chunk_bytes, slots, device, kF32);
+}
+int fa_ingest_create_f16(fa_ingest** out, int64_t P, int64_t chunk_bytes, int slots, int device) {
+    return create_pipe(out, P, chunk_bytes, slots, device, kF16);
+}
+
+int fa_ingest_rows_per_chunk(const fa_ingest* p) { return p ? (int)p->R : 0; }
+
+int fa_ingest_begin(fa_ingest* p, float* acc, void* stream, int64_t expected_rows) {
+    return begin_round(p, acc, stream, expected_rows, kF32);
+}
+int fa_ingest_begin_f16(fa_ingest* p, uint16_t* acc, void* stream, int64_t expected_rows) {
+    return begin_round(p, acc, stream, expected_rows, kF16);
+}
+
+int fa_ingest_add(fa_ingest* p, const void* const* srcs, const int64_t* sizes, int64_t n, float a, float s,
+                  int has_s) {
+    return add_row(p, srcs, sizes, n, &a, &s, has_s, kF32);
+}
+int fa_ingest_add_f16(fa_ingest* p, const void* const* srcs, const int64_t* sizes, int64_t n, uint16_t a, uint16_t s,
+                      int has_s) {
+    return add_row(p, srcs, sizes, n, &a, &s, has_s, kF16);
+}
+
+int fa_ingest_finish(fa_ingest* p, float divisor) { return finish_round(p, divisor, 0, kF32); }
+int fa_ingest_finish_f16(fa_ingest* p, uint16_t divisor) { return finish_round(p, 0.f, divisor, kF16); }
 
 int fa_ingest_destroy(fa_ingest* p) {
     if (!p) return FA_OK;

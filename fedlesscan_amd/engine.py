@@ -314,6 +314,10 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
         _lib.call("fa_fedavg_f16", X.data_ptr(), N, P, ldx, a.data_ptr(), _ptr(s),
                   int(np.asarray(f.div, dtype=np.float16).view(np.uint16)), out.data_ptr(), st)
         return out
+    if in_dt == np.float16 and dt == np.float32:
+        terms = _mixed_f16_terms(weights, scores, sum(weights) if total is None else total)
+        if terms is not None:  # Python-number and numpy-scalar weights mixed: numpy widens part-way
+            return _fold_f16_mixed(X, N, P, ldx, weights, scores, total, terms, out)
     if dt not in (np.float32, np.float64):
         raise InvalidParameterShapeError(f"unsupported result dtype {dt} (input {in_dt})")
     if in_dt != dt:
@@ -340,6 +344,101 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
         a, s = f.to(dev)
         _lib.call("fa_fedavg_f64", X.data_ptr(), N, P, ldx, a.data_ptr(), _ptr(s), float(f.div),
                   out.data_ptr(), st)
+    return out
+
+
+_WEAK = (bool, int, float)
+
+
+def _mixed_f16_terms(weights: Sequence, scores: Optional[Sequence], total) -> Optional[list]:
+    """float16 rows whose weights mix Python numbers with numpy scalars: the
+    dtype numpy gives each row's term, or None when the plain promoted fold is
+    already numpy's (every term of one dtype) or the mix is not one this handles.
+
+    numpy types every product on its own: `layer * n_i` stays float16 under a
+    Python number (weak, NEP 50) and takes np.result_type(float16, n_i.dtype)
+    under a numpy scalar; reduce(np.add) then runs in float16 up to the first
+    float32 term and in float32 from there on, a later float16 term still
+    being rounded to float16 before it is added.  Handled: Python-number
+    scores (or none), every term float16 or float32 with both present, a total
+    that leaves the quotient float32."""
+    f16, f32 = np.dtype(np.float16), np.dtype(np.float32)
+    if scores is not None and not all(type(x) in _WEAK for x in scores):
+        return None
+    terms = []
+    for w in weights:
+        d = f16 if type(w) in _WEAK else (np.result_type(f16, w.dtype) if isinstance(w, np.generic) else None)
+        if d not in (f16, f32):
+            return None
+        terms.append(d)
+    if f16 not in terms or f32 not in terms:
+        return None
+    if type(total) not in _WEAK and not (isinstance(total, np.generic) and np.result_type(f32, total.dtype) == f32):
+        return None
+    return terms
+
+
+def _fold_f16_mixed(X: torch.Tensor, N: int, P: int, ldx: int, weights, scores, total, terms, out):
+    """numpy's fold of float16 rows under mixed weights (_mixed_f16_terms), bit
+    for bit, from the kernels the uniform folds use:
+      rows ahead of the first float32 term   fa_fold_f16, unfinalised: the float16 running sum,
+                                             widened exactly to start the float32 accumulator
+      a run of float32 terms                 the rows widened exactly, fa_fold_f32 continuing the accumulator
+      a run of float16 terms after that      each term from fa_fold_f16 (one row, unfinalised), widened
+                                             exactly, added in row order by fa_fold_f32 with factor 1
+      the quotient                           fa_fold_f32, divide only, by fl32(total)
+    A few launches per run: this serves odd inputs, not a hot path."""
+    if torch.cuda.is_current_stream_capturing():
+        raise InvalidParameterShapeError("the float16 fold does not run under stream capture "
+                                         "(the captured factor fill carries float32 factors only)")
+    dev, st = X.device, stream_ptr(X.device)
+    f16, f32 = np.dtype(np.float16), np.dtype(np.float32)
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=dev)
+    total = sum(weights) if total is None else total
+    pad = np.zeros(2 + (N & 1), np.float16)  # the half factors end on a 4-byte word inside the staged block
+    halves = lambda v: np.concatenate([round_scalars(v, f16), pad])
+    parts = [halves(weights), round_scalars(weights, f32), np.ones(N, np.float32)]
+    if scores is not None:
+        parts += [halves(scores), round_scalars(scores, f32)]
+    staged = stage_factors(parts, dev)
+    a16, a32, one32 = staged[:3]
+    s16, s32 = (staged[3], staged[4]) if scores is not None else (None, None)
+    L = _lib.load()
+
+    def at(t, i, size):
+        return None if t is None else t.data_ptr() + size * i
+
+    def fold16(i, n, dst):  # float16 terms of rows [i, i + n), summed in float16, not divided
+        _lib.check(L.fa_fold_f16(X.data_ptr() + 2 * i * ldx, n, P, ldx, at(a16, i, 2), at(s16, i, 2), None, 0, 0,
+                                 dst.data_ptr(), st), "fa_fold_f16")
+
+    def fold32(Y, n, a, s, started):  # continue the float32 accumulator over the rows of Y
+        _lib.check(L.fa_fold_f32(Y.data_ptr(), n, P, Y.stride(0) if n > 1 else max(P, 1), a, s,
+                                 out.data_ptr() if started else None, 0.0, 0, out.data_ptr(), st), "fa_fold_f32")
+
+    i = terms.index(f32)
+    if i > 0:
+        head = torch.empty(P, dtype=torch.float16, device=dev)
+        fold16(0, i, head)
+        out[:P].copy_(head)  # exact widening
+    started = i > 0
+    while i < N:
+        j = i
+        while j < N and terms[j] == terms[i]:
+            j += 1
+        if terms[i] == f32:
+            Y = X[i:j, :P].to(torch.float32).contiguous()
+            fold32(Y, j - i, at(a32, i, 4), at(s32, i, 4), started)
+        else:
+            T = torch.empty((j - i, P), dtype=torch.float16, device=dev)
+            for r in range(i, j):
+                fold16(r, 1, T[r - i])
+            fold32(T.to(torch.float32), j - i, one32.data_ptr(), None, started)
+        started = True
+        i = j
+    _lib.check(L.fa_fold_f32(None, 0, P, P, None, None, out.data_ptr(), float(np.float32(total)), 1, out.data_ptr(),
+                             st), "fa_fold_f32(finalize)")
     return out
 
 
@@ -786,7 +885,13 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
         sizes = [int(np.prod(shapes[li])) if len(shapes[li]) else 1 for li in lis]
         P = sum(sizes)
         fp32_result = result_dtype(np.dtype(np.float32), total_weights, sc) == np.float32
-        if (not on_device and P > 0 and dtypes[lis[0]] == np.float32 and fp32_result):
+        if (not on_device and P > 0 and dtypes[lis[0]] == np.float16 and f16_stream_enabled() and
+                result_dtype(np.dtype(np.float16), total_weights, sc) == np.float16):
+            # host float16 rows whose result stays float16: the same pipe with
+            # 2-byte rows, binary16 factors and the chunked binary16 fold
+            # (fa_fold_f16), on one GPU
+            res = _stream_group(parameters, n_eff, lis, P, w, sc, sum(total_weights), dev, np.float16)
+        elif (not on_device and P > 0 and dtypes[lis[0]] == np.float32 and fp32_result):
             # host fp32 rows: pipelined pinned-chunk H2D + in-order chunked fold (bit-identical)
             if multi is not None:  # one column bucket per GPU, result assembled in pinned host memory
                 flat = _stream_group_multi(parameters, n_eff, lis, P, w, sc, sum(total_weights), multi)
@@ -832,10 +937,28 @@ def _py_scalar(x) -> bool:
     return type(x) in (int, float)  # weak scalars: fp32 layers stay fp32 (NEP 50)
 
 
-def _fast_row(layers, shapes) -> bool:
-    """A row the streaming path can take: float32 numpy layers shaped like row 0."""
+def f16_stream_enabled() -> bool:
+    """Host float16 rows stream through the ingest pipe unless
+    FEDAVG_F16_STREAM=0 (read per call), which keeps the materialised route:
+    every row stacked into one pinned matrix, one H2D, one fa_fedavg_f16."""
+    return os.environ.get("FEDAVG_F16_STREAM", "1") != "0"
+
+
+def _stream_dtype(layers) -> Optional[np.dtype]:
+    """The dtype a row streams in: float32 or float16 when every layer is a
+    numpy array of that one dtype; None otherwise (mixed or other dtypes)."""
+    dts = {x.dtype for x in layers if isinstance(x, np.ndarray)}
+    if len(dts) != 1 or not all(isinstance(x, np.ndarray) for x in layers):
+        return None
+    dt = dts.pop()
+    return dt if dt in (np.float32, np.float16) else None
+
+
+def _fast_row(layers, shapes, dtype=np.float32) -> bool:
+    """A row the streaming path can take: numpy layers of `dtype` (row 0's:
+    float32 or float16) shaped like row 0."""
     return (len(layers) == len(shapes) and
-            all(isinstance(x, np.ndarray) and x.dtype == np.float32 and x.shape == shp
+            all(isinstance(x, np.ndarray) and x.dtype == dtype and x.shape == shp
                 for x, shp in zip(layers, shapes)))
 
 
@@ -848,7 +971,9 @@ def aggregate_decoded(items, scores: Optional[Sequence] = None, device: Optional
     (fed_avg_aggregator.py:64-92).  Here each host float32 row enters the
     pipelined StreamingFold as soon as it is decoded, so decoding row i+1
     overlaps the DMA of row i.  Same rows, same order, same factors: the result
-    is bit-identical.  Anything else (other dtypes, a row shaped unlike row 0,
+    is bit-identical.  Rows whose layers are all float16 stream the same way
+    through a float16 pipe (one GPU; FEDAVG_F16_STREAM=0 turns that off).
+    Anything else (other or mixed dtypes, a row shaped or typed unlike row 0,
     weights that are not Python scalars, device tensors, nothing to fold)
     drains the iterator and runs aggregate_layers over every row, which is
     exactly the materialised path.  zip() truncation is kept: rows beyond
@@ -870,7 +995,10 @@ def aggregate_decoded(items, scores: Optional[Sequence] = None, device: Optional
     rows, weights = [first[0]], [first[1]]
     shapes = [getattr(x, "shape", None) for x in first[0]]
     n_fold = len(scores) if scores is not None else None
-    fast = (len(shapes) > 0 and _fast_row(first[0], shapes) and _py_scalar(first[1]) and
+    dt = _stream_dtype(first[0]) if len(shapes) > 0 else None
+    if dt == np.float16 and (multi is not None or not f16_stream_enabled()):
+        dt = None  # float16 rows stream on one GPU only
+    fast = (dt is not None and _fast_row(first[0], shapes, dt) and _py_scalar(first[1]) and
             (scores is None or (len(scores) > 0 and all(_py_scalar(x) for x in scores))))
     P = sum(int(np.prod(shp)) if len(shp) else 1 for shp in shapes) if fast else 0
     if fast and P > 0:
@@ -882,7 +1010,7 @@ def aggregate_decoded(items, scores: Optional[Sequence] = None, device: Optional
         else:
             from .ingest import make_streaming_fold
             sf = make_streaming_fold(P, device or default_device(), STREAM_CHUNK_BYTES, direct=DIRECT_DMA,
-                                     expected_rows=n_exp)
+                                     expected_rows=n_exp, dtype=dt)
         sf.add(list(first[0]), first[1], None if scores is None else scores[0])
         for layers, w in it:
             rows.append(layers)
@@ -892,7 +1020,7 @@ def aggregate_decoded(items, scores: Optional[Sequence] = None, device: Optional
                 break
             if n_fold is not None and i >= n_fold:
                 continue
-            if not _fast_row(layers, shapes):
+            if not _fast_row(layers, shapes, dt):
                 break
             sf.add(list(layers), w, None if scores is None else scores[i])
         else:
@@ -921,10 +1049,10 @@ def to_host(t: torch.Tensor) -> np.ndarray:
     return host.numpy()
 
 
-def _stream_group(parameters, n, lis, P, w, sc, total, dev) -> torch.Tensor:
+def _stream_group(parameters, n, lis, P, w, sc, total, dev, dtype=np.float32) -> torch.Tensor:
     from .ingest import chunk_class, make_streaming_fold
-    sf = make_streaming_fold(P, dev, chunk_class(max(1, n) * 4 * P, STREAM_CHUNK_BYTES), direct=DIRECT_DMA,
-                             expected_rows=n)
+    sf = make_streaming_fold(P, dev, chunk_class(max(1, n) * np.dtype(dtype).itemsize * P, STREAM_CHUNK_BYTES),
+                             direct=DIRECT_DMA, expected_rows=n, dtype=dtype)
     for i in range(n):
         sf.add([parameters[i][li] for li in lis], w[i], None if sc is None else sc[i])
     return sf.finish(total=total)

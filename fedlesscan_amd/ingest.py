@@ -18,6 +18,11 @@ by default: on MI355X hosts the 16-thread pack fully overlaps the DMA, and one
 copy per chunk beat one copy per layer; it pays where host memcpy
 bandwidth, not PCIe, is the limit.
 
+float16 rows take the native pipe only (NativeStreamingFold(dtype=float16):
+2-byte rows, binary16 factors, a float16 accumulator, fa_fold_f16), bit-identical
+to one fa_fedavg_f16 over all rows (tests/test_gpu_f16_ingest.py); the
+Python-driven StreamingFold stays float32-only.
+
 Memory: `slots` pinned + `slots` device chunks of chunk_rows x P floats (2 by
 default; FEDAVG_STREAM_SLOTS overrides) and one [P] accumulator, independent of
 the number of clients.  More, smaller chunks shorten the exposed tail of a
@@ -221,7 +226,7 @@ class StreamingFold:
 class _PipeCache:
     """Native ingest pipes (fa_ingest_*) kept across rounds: a pipe owns
     page-locked and device chunks and an issuer thread, so it is created once
-    per (device, P, chunk size, slots) and reused; a pipe serves one round at a
+    per (device, P, chunk size, slots, dtype) and reused; a pipe serves one round at a
     time (a concurrent round gets its own), and at most MAX idle pipes are
     kept per process."""
 
@@ -239,9 +244,10 @@ class _PipeCache:
                 if not pipes:
                     del self.idle[key]
                 return p
-        dev, P, chunk_bytes, slots = key
+        dev, P, chunk_bytes, slots, dtype = key
         h = ctypes.c_void_p()
-        _lib.call("fa_ingest_create", ctypes.byref(h), P, chunk_bytes, slots, dev)
+        _lib.call("fa_ingest_create_f16" if dtype == "float16" else "fa_ingest_create", ctypes.byref(h), P,
+                  chunk_bytes, slots, dev)
         return h
 
     def put(self, key, pipe):
@@ -264,32 +270,48 @@ class _PipeCache:
 _pipes = _PipeCache()
 
 
+def _half_bits(v) -> int:
+    """The binary16 bit pattern numpy rounds the scalar v to (round_scalars, as
+    engine.Factors forms a float16 fold's factors and divisor; overflow gives inf)."""
+    return int(round_scalars([v], np.float16).view(np.uint16)[0])
+
+
 class NativeStreamingFold:
     """StreamingFold on the native pipe (libfedavg_hip.so fa_ingest_*): the
     same add(row, weight, score) / finish(total) contract and bit-identical
     result, with the packing done by the library's copy workers and the DMA and
     fold issued by its own thread, so add() returns as soon as the row's copies
     are queued and decoding the next row overlaps everything else.  The rows'
-    arrays are kept alive until finish() (the workers read them)."""
+    arrays are kept alive until finish() (the workers read them).
+
+    dtype: float32 (default) or float16.  A float16 fold takes float16 rows,
+    keeps a float16 accumulator and rounds every factor and the divisor to
+    binary16 with round_scalars, as engine.fold_stacked forms them for
+    fa_fedavg_f16 (a factor that overflows stays inf), so the result is the
+    reference's own binary16 fold, bit for bit (fa_fold_f16)."""
 
     stats = {"rows": 0}
 
     def __init__(self, P: int, device: Optional[torch.device] = None, chunk_bytes: int = 16 << 20,
-                 slots: int = 4, expected_rows: int = 0):
+                 slots: int = 4, expected_rows: int = 0, dtype=np.float32):
         if P <= 0:
             raise InvalidParameterShapeError("StreamingFold needs P > 0")
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.float32, np.float16):
+            raise InvalidParameterShapeError(f"StreamingFold takes float32 or float16 rows, not {self.dtype}")
+        self.f16 = self.dtype == np.float16
         self.P = P
         self.dev = device or torch.device("cuda", torch.cuda.current_device())
         if self.dev.index is None:
             self.dev = torch.device("cuda", torch.cuda.current_device())
-        self.key = (self.dev.index, P, int(chunk_bytes), int(slots))
+        self.key = (self.dev.index, P, int(chunk_bytes), int(slots), self.dtype.name)
         self.pipe = _pipes.get(self.key)
-        self.acc = torch.empty(P, dtype=torch.float32, device=self.dev)
+        self.acc = torch.empty(P, dtype=torch.float16 if self.f16 else torch.float32, device=self.dev)
         self.L = _lib.load()
         try:
-            _lib.check(self.L.fa_ingest_begin(self.pipe, self.acc.data_ptr(),
-                                              torch.cuda.current_stream(self.dev).cuda_stream,
-                                              max(0, int(expected_rows))), "fa_ingest_begin")
+            begin = self.L.fa_ingest_begin_f16 if self.f16 else self.L.fa_ingest_begin
+            _lib.check(begin(self.pipe, self.acc.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream,
+                             max(0, int(expected_rows))), "fa_ingest_begin")
         except BaseException:
             _pipes.drop(self.pipe)
             self.pipe = None
@@ -311,16 +333,25 @@ class NativeStreamingFold:
         arrs = []
         for layer in pieces:
             arr = np.ascontiguousarray(layer)
-            if arr.dtype != np.float32:
+            if arr.dtype != self.dtype:
                 self._fail()
-                raise InvalidParameterShapeError(f"StreamingFold takes float32 rows, got {arr.dtype}")
+                raise InvalidParameterShapeError(f"StreamingFold takes {self.dtype} rows, got {arr.dtype}")
             arrs.append(arr)
         n = len(arrs)
         ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
         sizes = (ctypes.c_int64 * n)(*[a.nbytes for a in arrs])
-        a = float(np.float32(weight))  # fl32(n_i): numpy's rounding of the Python scalar
-        s = 1.0 if score is None else float(np.float32(score))
-        rc = self.L.fa_ingest_add(self.pipe, ptrs, sizes, n, a, s, 0 if score is None else 1)
+        if self.f16:
+            try:  # fl16(n_i), fl16(score): the bits Factors hands fa_fedavg_f16
+                a = _half_bits(weight)
+                s = 0x3C00 if score is None else _half_bits(score)
+            except BaseException:
+                self._fail()
+                raise
+            rc = self.L.fa_ingest_add_f16(self.pipe, ptrs, sizes, n, a, s, 0 if score is None else 1)
+        else:
+            a = float(np.float32(weight))  # fl32(n_i): numpy's rounding of the Python scalar
+            s = 1.0 if score is None else float(np.float32(score))
+            rc = self.L.fa_ingest_add(self.pipe, ptrs, sizes, n, a, s, 0 if score is None else 1)
         if rc:
             err = _lib.last_error()
             self._fail()
@@ -338,8 +369,16 @@ class NativeStreamingFold:
         if self.rows == 0:
             self._fail()
             _lib.check(_lib.FA_ERR_NO_CLIENTS, "StreamingFold.finish")
-        div = float(np.float32(sum(self.weights) if total is None else total))
-        rc = self.L.fa_ingest_finish(self.pipe, div)
+        total = sum(self.weights) if total is None else total
+        if self.f16:
+            try:
+                div = _half_bits(total)
+            except BaseException:
+                self._fail()
+                raise
+            rc = self.L.fa_ingest_finish_f16(self.pipe, div)
+        else:
+            rc = self.L.fa_ingest_finish(self.pipe, float(np.float32(total)))
         if rc:
             err = _lib.last_error()
             self._fail()
@@ -384,12 +423,16 @@ def chunk_class(nbytes: int, cap: int) -> int:
     return min(c, cap)
 
 
-def make_streaming_fold(P: int, device, chunk_bytes: int, direct: bool = False, expected_rows: int = 0):
-    """The ingest for P-float rows on `device`: the native pipe, or the
+def make_streaming_fold(P: int, device, chunk_bytes: int, direct: bool = False, expected_rows: int = 0,
+                        dtype=np.float32):
+    """The ingest for P-element rows on `device`: the native pipe, or the
     Python-driven StreamingFold for the direct-DMA route (page-locked
     documents) or when FEDAVG_NATIVE_INGEST=0.  expected_rows: the round's row
     count when the caller knows it (the native pipe then shrinks its last
-    chunks)."""
+    chunks).  dtype float16 always takes the native pipe: the Python-driven
+    StreamingFold is float32-only."""
+    if np.dtype(dtype) == np.float16:
+        return NativeStreamingFold(P, device, chunk_bytes, STREAM_SLOTS or 3, expected_rows, dtype=np.float16)
     if NATIVE_INGEST and not direct:
         return NativeStreamingFold(P, device, chunk_bytes, STREAM_SLOTS or 3, expected_rows)
     return StreamingFold(P, chunk_rows=max(1, chunk_bytes // (4 * P)), device=device, direct=direct,

@@ -133,6 +133,30 @@ int fa_fedavg_f16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
                   const uint16_t* a, const uint16_t* s, uint16_t divisor,
                   uint16_t* out, void* stream);
 
+/* Chunked binary16 fold (new symbol, ABI still 7): fa_fold_f32's contract in
+ * the arithmetic of fa_fedavg_f16, the building block of streaming ingest for
+ * float16 models (the reference's aggregate() on float16 results,
+ * fed_avg_aggregator.py:57-92, stall_aware_aggregation.py:82-117, folds them
+ * in binary16: NEP 50).  acc_in and out are halves:
+ *   acc_in == NULL : acc = t_0 (not 0 + t_0: a column of -0.0 stays -0.0)
+ *   acc_in != NULL : acc = fl16(acc_in[p] + t_0), then t_1, ... in row order
+ *   finalize != 0  : out = fl16(acc / divisor), the float32 divide of the
+ *                    exactly converted operands rounded once; else out = acc
+ *   N == 0 with acc_in: only the divide (or, without finalize, a copy)
+ * acc_in may alias out.  Every add rounds to binary16 already, so the halves
+ * carried between calls are the whole accumulator: folding the rows in any
+ * cuts is bit-identical to one fa_fedavg_f16 over all of them.  Argument
+ * checks and status codes as fa_fedavg_f16 (N == 0 without acc_in ->
+ * FA_ERR_NO_CLIENTS); a capturing stream -> FA_ERR_ARG (no captured staging
+ * carries binary16 factors).  One form fixed by shape (2 octets per lane, 4
+ * rows ahead, balanced grid-stride passes); X, acc_in or out off 16-B alignment
+ * or ldx % 8 != 0: one column per lane.  The kernels read the aligned 4-byte
+ * word that holds each factor: a and s must each end on a 4-byte boundary
+ * inside their allocation. */
+int fa_fold_f16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
+                const uint16_t* a, const uint16_t* s, const uint16_t* acc_in,
+                uint16_t divisor, int finalize, uint16_t* out, void* stream);
+
 /* The 16-bit folds over N separately allocated client rows (new symbols, ABI
  * still 7): xi is a [device] array of N [device] pointers, each to P bf16 /
  * binary16 elements -- the list-of-arrays form the reference passes
@@ -417,7 +441,8 @@ int fa_copy_peer(void* dst, int dst_device, const void* src, int src_device, int
  * sends each full chunk with one DMA on the pipe's copy stream and folds it on
  * the round's compute stream with fa_fold_f32, chunks in row order, the
  * accumulator carried across them: bit-identical to fa_fedavg_f32 over all
- * rows.  A chunk slot is refilled only after its fold has completed.
+ * rows.  A chunk slot is refilled only after its fold has completed.  (These
+ * entries are the float32 pipe; the float16 pipe's entries follow them.)
  *   fa_ingest_create:  allocate a pipe for models of P floats on `device`
  *   fa_ingest_begin:   start a round folding into acc [device, P] on `stream`;
  *                      expected_rows = the round's row count if known (0: not):
@@ -445,6 +470,24 @@ int fa_ingest_add(fa_ingest* pipe, const void* const* srcs, const int64_t* sizes
                   int has_s);
 int fa_ingest_finish(fa_ingest* pipe, float divisor);
 int fa_ingest_destroy(fa_ingest* pipe);
+/* The same pipe for float16 models (new symbols, ABI still 7): the reference's
+ * aggregate() folds float16 results in binary16 (fed_avg_aggregator.py:57-92
+ * over NEP 50 weak weights).  A pipe created with fa_ingest_create_f16 takes
+ * rows of P halves (pitch P rounded up to 64 halves, chunk_bytes / (pitch * 2)
+ * rows per chunk), the factors a, s and the divisor as binary16 bit patterns
+ * (already rounded as numpy rounds them; inf stays inf), keeps its factor
+ * block in halves ahead of the rows in the chunk's one DMA (padded so the rows
+ * stay 256-B aligned) and folds into acc [device, P halves] with fa_fold_f16:
+ * bit-identical to fa_fedavg_f16 over all rows.  Pieces of a row may hold any
+ * whole number of halves.  Ramps, the halving tail, abandon and reuse, and the
+ * error paths are those of the float32 pipe; fa_ingest_rows_per_chunk and
+ * fa_ingest_destroy serve both kinds.  A float32 entry on a float16 pipe, or
+ * the reverse, returns FA_ERR_ARG and leaves the pipe as it was. */
+int fa_ingest_create_f16(fa_ingest** pipe, int64_t P, int64_t chunk_bytes, int slots, int device);
+int fa_ingest_begin_f16(fa_ingest* pipe, uint16_t* acc, void* stream, int64_t expected_rows);
+int fa_ingest_add_f16(fa_ingest* pipe, const void* const* srcs, const int64_t* sizes, int64_t n, uint16_t a,
+                      uint16_t s, int has_s);
+int fa_ingest_finish_f16(fa_ingest* pipe, uint16_t divisor);
 
 /* ---- host-side ingest (no GPU): NPZ wire format -> pinned staging ----------
  * Client blobs are uncompressed NPZ archives (NpzWeightsSerializer,

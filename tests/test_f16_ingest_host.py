@@ -1,0 +1,149 @@
+"""CPU-side tests of the float16 ingest route's host pieces: the chunked
+binary16 fold and the float16 pipe entries exist with the declared signatures,
+the ABI number stays 7, their argument checks answer before anything touches
+the GPU, and engine.aggregate_decoded's fast-row rule tells float32, float16
+and mixed rows apart.  No GPU compute (tests/test_gpu_f16_fold.py and
+tests/test_gpu_f16_ingest.py have it)."""
+import ctypes
+
+import numpy as np
+
+from fedlesscan_amd import _lib, engine
+from test_rows16_host import _ctypes_of, _declaration
+
+U16P, CU16P = "uint16_t*", "const uint16_t*"
+ENTRIES = {
+    "fa_fold_f16": ("int", [CU16P, "int64_t", "int64_t", "int64_t", CU16P, CU16P, CU16P, "uint16_t", "int", U16P,
+                            "void*"]),
+    "fa_ingest_create_f16": ("int", ["fa_ingest* *", "int64_t", "int64_t", "int", "int"]),
+    "fa_ingest_begin_f16": ("int", ["fa_ingest*", U16P, "void*", "int64_t"]),
+    "fa_ingest_add_f16": ("int", ["fa_ingest*", "const void* const*", "const int64_t*", "int64_t", "uint16_t",
+                                  "uint16_t", "int"]),
+    "fa_ingest_finish_f16": ("int", ["fa_ingest*", "uint16_t"]),
+}
+
+
+def _norm(params):
+    return [p.replace("* *", "**").replace(" ", "") for p in params]
+
+
+def test_entries_exist_with_the_declared_signatures():
+    L = _lib.load()
+    assert L.fa_abi_version() == _lib.ABI_VERSION == 7  # new symbols only
+    declared = _lib.header_functions()
+    for name, (ret, params) in ENTRIES.items():
+        assert name in declared and hasattr(L, name), name
+        dret, dparams = _declaration(_lib.HEADER, name)
+        assert dret == ret and _norm(dparams) == _norm(params), (name, dparams)
+        res, args = _lib._PROTOS[name]
+        assert res is ctypes.c_int and args == _ctypes_of(params), name
+    # the float32 entries keep their signatures
+    assert _declaration(_lib.HEADER, "fa_ingest_add")[1][4:] == ["float", "float", "int"]
+    assert _declaration(_lib.HEADER, "fa_ingest_finish")[1] == ["fa_ingest*", "float"]
+    assert _declaration(_lib.HEADER, "fa_ingest_begin")[1][1] == "float*"
+
+
+def test_fold_argument_checks_answer_on_the_host():
+    """The codes of fa_fedavg_f16, before anything touches the GPU; N == 0 is
+    an error only without an accumulator to finalise."""
+    L = _lib.load()
+    buf = (ctypes.c_uint8 * 256)()
+    p = (ctypes.addressof(buf) + 15) & ~15
+    one = 0x3C00
+    assert L.fa_fold_f16(p, 0, 8, 8, p, None, None, one, 1, p, None) == _lib.FA_ERR_NO_CLIENTS
+    msg = _lib.last_error()
+    L.fa_fedavg_f16(p, 0, 8, 8, p, None, one, p, None)
+    assert msg == _lib.last_error()  # the same message for the same mistake
+    assert L.fa_fold_f16(None, 2, 8, 8, p, None, None, one, 1, p, None) == _lib.FA_ERR_ARG
+    assert "null" in _lib.last_error()
+    assert L.fa_fold_f16(p, 2, 8, 8, None, None, None, one, 1, p, None) == _lib.FA_ERR_ARG
+    assert L.fa_fold_f16(p, 2, 8, 8, p, None, None, one, 1, None, None) == _lib.FA_ERR_ARG
+    assert L.fa_fold_f16(p, 2, 8, 8, p, None, p, one, 0, None, None) == _lib.FA_ERR_ARG
+    assert L.fa_fold_f16(None, 0, 8, 8, None, None, p, one, 1, None, None) == _lib.FA_ERR_ARG  # divide only, no out
+    assert L.fa_fold_f16(None, 0, -8, 8, None, None, p, one, 1, p, None) == _lib.FA_ERR_ARG
+    assert L.fa_fold_f16(p, -1, 8, 8, p, None, None, one, 1, p, None) == _lib.FA_ERR_ARG
+    assert L.fa_fold_f16(p, 2, -8, 8, p, None, None, one, 1, p, None) == _lib.FA_ERR_ARG
+    assert L.fa_fold_f16(p, 2, 8, 7, p, None, None, one, 1, p, None) == _lib.FA_ERR_SHAPE  # pitch < P
+    # P == 0: nothing to do, nothing launched
+    assert L.fa_fold_f16(p, 2, 0, 0, p, None, None, one, 1, p, None) == _lib.FA_OK
+    assert L.fa_fold_f16(None, 0, 0, 0, None, None, p, one, 1, None, None) == _lib.FA_OK
+
+
+def test_pipe_argument_checks_answer_on_the_host():
+    L = _lib.load()
+    h = ctypes.c_void_p()
+    buf = (ctypes.c_uint8 * 64)()
+    p = ctypes.addressof(buf)
+    assert L.fa_ingest_create_f16(None, 8, 1 << 20, 2, 0) == _lib.FA_ERR_ARG
+    assert L.fa_ingest_create_f16(ctypes.byref(h), 0, 1 << 20, 2, 0) == _lib.FA_ERR_ARG
+    assert L.fa_ingest_create_f16(ctypes.byref(h), 8, 0, 2, 0) == _lib.FA_ERR_ARG
+    assert L.fa_ingest_create_f16(ctypes.byref(h), 8, 1 << 20, 1, 0) == _lib.FA_ERR_ARG
+    assert L.fa_ingest_create_f16(ctypes.byref(h), 8, 1 << 20, 2, -1) == _lib.FA_ERR_ARG
+    assert not h.value
+    assert L.fa_ingest_begin_f16(None, p, None, 0) == _lib.FA_ERR_ARG
+    assert L.fa_ingest_add_f16(None, None, None, 0, 0x3C00, 0x3C00, 0) == _lib.FA_ERR_ARG
+    assert L.fa_ingest_finish_f16(None, 0x3C00) == _lib.FA_ERR_ARG
+    assert L.fa_ingest_rows_per_chunk(None) == 0 and L.fa_ingest_destroy(None) == _lib.FA_OK
+
+
+def _layers(*dts):
+    return [np.zeros((3, 2) if i == 0 else (5,), dt) for i, dt in enumerate(dts)]
+
+
+def test_fast_row_rule(monkeypatch):
+    """A row streams when its layers are all float32 or all float16, shaped like
+    row 0 and of row 0's dtype; mixed rows and other dtypes do not."""
+    f32, f16 = np.dtype(np.float32), np.dtype(np.float16)
+    assert engine._stream_dtype(_layers(f32, f32)) == f32
+    assert engine._stream_dtype(_layers(f16, f16)) == f16
+    assert engine._stream_dtype(_layers(f16, f32)) is None
+    assert engine._stream_dtype(_layers(np.float64, np.float64)) is None
+    assert engine._stream_dtype(_layers(np.int32, np.int32)) is None
+    assert engine._stream_dtype([np.zeros(3, f16), [0.0, 1.0]]) is None  # not an array
+    shapes = [(3, 2), (5,)]
+    assert engine._fast_row(_layers(f32, f32), shapes)  # the float32 default is unchanged
+    assert engine._fast_row(_layers(f32, f32), shapes, f32) and not engine._fast_row(_layers(f32, f32), shapes, f16)
+    assert engine._fast_row(_layers(f16, f16), shapes, f16) and not engine._fast_row(_layers(f16, f16), shapes, f32)
+    assert not engine._fast_row(_layers(f16, f32), shapes, f16) and not engine._fast_row(_layers(f16, f32), shapes, f32)
+    assert not engine._fast_row([np.zeros((3, 2), f16), np.zeros(6, f16)], shapes, f16)  # shaped unlike row 0
+    assert not engine._fast_row(_layers(f16), shapes, f16)  # a layer short
+    # the switch is read per call
+    monkeypatch.delenv("FEDAVG_F16_STREAM", raising=False)
+    assert engine.f16_stream_enabled()
+    monkeypatch.setenv("FEDAVG_F16_STREAM", "0")
+    assert not engine.f16_stream_enabled()
+    monkeypatch.setenv("FEDAVG_F16_STREAM", "1")
+    assert engine.f16_stream_enabled()
+    # weights: Python numbers only, as for float32 (a numpy scalar promotes the fold)
+    assert engine._py_scalar(3) and engine._py_scalar(0.5) and not engine._py_scalar(np.float16(3))
+
+
+def test_half_bits_are_numpys_roundings():
+    """The float16 pipe's factors are round_scalars' binary16 roundings: the
+    bits fold_stacked hands fa_fedavg_f16, inf where the value overflows."""
+    from fedlesscan_amd.ingest import _half_bits
+    with np.errstate(all="ignore"):
+        for v in (1, 40, 2049, 65519, 65520, 70000, 0.1, 1 / 3, 6e-8, 0, True):
+            f = engine.Factors([v], None, np.dtype(np.float16))
+            assert _half_bits(v) == int(f.a.view(np.uint16)[0]) == int(np.float16(v).view(np.uint16)), v
+        assert _half_bits(70000) == 0x7C00 and _half_bits(2049) == 0x6800 and _half_bits(65519) == 0x7BFF
+
+
+def test_mixed_weight_terms_follow_numpys_promotion():
+    """Which mixes of Python-number and numpy-scalar weights the float16 fold
+    types row by row, checked against the dtypes numpy itself gives."""
+    f16, f32 = np.dtype(np.float16), np.dtype(np.float32)
+    x = np.ones(3, np.float16)
+    for w in ([3, 4, np.float32(5), 6], [np.float32(3), 4], [3, np.int16(4)], [3, np.uint8(4), np.float32(2)]):
+        terms = engine._mixed_f16_terms(w, None, sum(w))
+        assert terms == [(x * k).dtype for k in w], w
+        assert (x * w[0] / sum(w)).dtype in (f16, f32) and f32 in terms and f16 in terms
+    # one dtype throughout, or anything reaching float64: the plain promoted fold is numpy's already
+    assert engine._mixed_f16_terms([np.float32(1), np.float32(2)], None, np.float32(3)) is None
+    assert engine._mixed_f16_terms([1, 2], None, 3) is None
+    assert engine._mixed_f16_terms([1, np.float16(2)], None, 3) is None
+    assert engine._mixed_f16_terms([1, np.float64(2)], None, 3) is None
+    assert engine._mixed_f16_terms([1, np.int64(2)], None, 3) is None
+    assert engine._mixed_f16_terms([1, np.float32(2)], None, np.float64(3)) is None
+    assert engine._mixed_f16_terms([1, np.float32(2)], [0.5, np.float32(0.5)], 3) is None  # numpy-scalar scores
+    assert engine._mixed_f16_terms([1, np.float32(2)], [0.5, 0.25], 3) == [f16, f32]

@@ -7,6 +7,9 @@
 // fold of the same rows.  Also: errors mid-round (a short row, mixed scores),
 // a round abandoned with a chunk half filled and the pipe reused (bit-exact),
 // destroy with copies possibly in flight, and finish with no rows.
+// float16 pipes (the *_f16 entries) run the same way against a CPU restatement
+// of fa_fold_f16: plain and scored rounds, an abandoned round then a reused
+// pipe, and calls of the wrong element kind.
 //   tools/ingest_pipe_stress.sh   (builds with -fsanitize=thread, then address,undefined)
 #include <stdint.h>
 #include <stdio.h>
@@ -49,6 +52,76 @@ extern "C" int fa_fold_f32(const float* X, int64_t N, int64_t P, int64_t ldx, co
             acc = acc + t;
         }
         out[p] = finalize ? acc / divisor : acc;
+    }
+    return FA_OK;
+}
+
+// ---- binary16 on the CPU --------------------------------------------------
+// Exact half -> float; float -> half with round-to-nearest-even, subnormals
+// kept.  A product, sum or quotient of two halves computed in float32 and
+// rounded once more to half is the correctly rounded binary16 result (24 >= 2 *
+// 11 + 2 bits), which is how the kernels' arithmetic is defined.
+static float h2f(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
+    uint32_t u;
+    if (e == 0x1Fu) {
+        u = sign | 0x7F800000u | (m << 13);
+    } else if (e != 0) {
+        u = sign | ((e + 112u) << 23) | (m << 13);
+    } else if (m == 0) {
+        u = sign;
+    } else {
+        int sh = 0;
+        uint32_t mm = m;
+        while (!(mm & 0x400u)) { mm <<= 1; ++sh; }
+        u = sign | ((uint32_t)(113 - sh) << 23) | ((mm & 0x3FFu) << 13);
+    }
+    float f;
+    memcpy(&f, &u, sizeof f);
+    return f;
+}
+static uint16_t f2h(float f) {
+    uint32_t u;
+    memcpy(&u, &f, sizeof u);
+    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+    const uint32_t ax = u & 0x7FFFFFFFu;
+    if (ax >= 0x7F800000u) return (uint16_t)(sign | 0x7C00u | (ax > 0x7F800000u ? 0x200u : 0u));  // inf, NaN
+    if (ax >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);  // >= 65520 rounds to inf
+    if (ax < 0x33000000u) return sign;                          // < 2^-25 rounds to zero (2^-25 itself: tie to even)
+    const int e = (int)(ax >> 23) - 127;
+    uint32_t m = (ax & 0x7FFFFFu) | 0x800000u;  // 24-bit significand
+    int shift = e < -14 ? 13 + (-14 - e) : 13;  // bits dropped (subnormal results drop more)
+    const uint32_t keep = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    uint32_t r = keep + ((rem > half || (rem == half && (keep & 1u))) ? 1u : 0u);
+    if (e < -14) return (uint16_t)(sign | r);  // subnormal (r may carry into the smallest normal: same bits)
+    // normal: r has the implicit bit at 0x400 (or 0x800 after a carry)
+    return (uint16_t)(sign | (uint16_t)(((uint32_t)(e + 15 - 1) << 10) + r));
+}
+static uint16_t hmul(uint16_t x, uint16_t y) { return f2h(h2f(x) * h2f(y)); }
+static uint16_t hadd(uint16_t x, uint16_t y) { return f2h(h2f(x) + h2f(y)); }
+static uint16_t hdiv(uint16_t x, uint16_t y) { return f2h(h2f(x) / h2f(y)); }
+
+// CPU restatement of fa_fold_f16 (fedavg_hip.h): binary16 products, sums and quotient in row order
+extern "C" int fa_fold_f16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a,
+                           const uint16_t* s, const uint16_t* acc_in, uint16_t divisor, int finalize, uint16_t* out,
+                           void*) {
+    if (N == 0 && !acc_in) return fa_internal_fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
+    for (int64_t p = 0; p < P; ++p) {
+        uint16_t acc = 0;
+        int64_t i = 0;
+        if (acc_in) {
+            acc = acc_in[p];
+        } else {
+            acc = hmul(X[p], a[0]);
+            if (s) acc = hmul(acc, s[0]);
+            i = 1;
+        }
+        for (; i < N; ++i) {
+            uint16_t t = hmul(X[i * ldx + p], a[i]);
+            if (s) t = hmul(t, s[i]);
+            acc = hadd(acc, t);
+        }
+        out[p] = finalize ? hdiv(acc, divisor) : acc;
     }
     return FA_OK;
 }
@@ -142,9 +215,108 @@ static void worker(int tid, int rounds) {
     }
 }
 
+// float16 rounds: plain and scored (pipe reused), an abandoned round then a
+// clean one, wrong-kind calls on both kinds of pipe
+static void worker_f16(int tid, int rounds) {
+    std::mt19937_64 rng(4321 + tid);
+    for (int r = 0; r < rounds; ++r) {
+        const int64_t P = 1 + rng() % 70000;
+        const int64_t N = 1 + rng() % 33;
+        const int slots = 2 + rng() % 5;
+        const int64_t ldx = (P + 63) / 64 * 64;
+        const int64_t chunk = ldx * 2 * (1 + rng() % 6);
+        std::vector<uint16_t> X(N * P), a(N), s(N);
+        for (auto& v : X) v = f2h((float)((int64_t)(rng() % 2001) - 1000) / 1024.f);
+        float totalf = 0.f;
+        for (int64_t i = 0; i < N; ++i) {
+            const float w = (float)(1 + rng() % 40);
+            totalf += w;  // <= 1320: exact in binary16's integer range up to 2048
+            a[i] = f2h(w);
+            s[i] = f2h((float)(1 + rng() % 11) / 11.f);
+        }
+        const uint16_t total = f2h(totalf);
+        fa_ingest* pipe = nullptr;
+        check(fa_ingest_create_f16(&pipe, P, chunk, slots, tid % 2) == FA_OK, "create f16");
+        check(fa_ingest_rows_per_chunk(pipe) == (int)(chunk / (ldx * 2)), "rows per chunk f16");
+        std::vector<uint16_t> acc(P, 0x7E00u), exp(P);
+        for (int rep = 0; rep < 2; ++rep) {  // plain, then scored, on the same pipe
+            const bool scored = rep == 1;
+            const int64_t guess[4] = {0, N, N + 3, N > 2 ? N - 2 : 1};
+            check(fa_ingest_begin_f16(pipe, acc.data(), nullptr, guess[rng() % 4]) == FA_OK, "begin f16");
+            for (int64_t i = 0; i < N; ++i) {
+                // the row in 1-4 pieces of any whole number of halves (odd counts included)
+                std::vector<const void*> src;
+                std::vector<int64_t> sz;
+                int64_t off = 0;
+                const int parts = 1 + rng() % 4;
+                for (int k = 0; k < parts; ++k) {
+                    const int64_t len = k == parts - 1 ? P - off : (P - off) * (int64_t)(rng() % 100) / 100;
+                    src.push_back(X.data() + i * P + off);
+                    sz.push_back(len * 2);
+                    off += len;
+                }
+                check(fa_ingest_add_f16(pipe, src.data(), sz.data(), (int64_t)src.size(), a[i], s[i], scored) == FA_OK,
+                      "add f16");
+            }
+            check(fa_ingest_finish_f16(pipe, total) == FA_OK, "finish f16");
+            fa_fold_f16(X.data(), N, P, P, a.data(), scored ? s.data() : nullptr, nullptr, total, 1, exp.data(),
+                        nullptr);
+            check(memcmp(exp.data(), acc.data(), P * 2) == 0, "bit-exact f16");
+        }
+        // wrong-kind calls: refused, and the pipe is left as it was
+        const void* src0 = X.data();
+        int64_t full = P * 2, shortb = (P - 1) * 2;
+        std::vector<float> acc32(P);
+        check(fa_ingest_begin(pipe, acc32.data(), nullptr, 0) == FA_ERR_ARG, "f32 begin on an f16 pipe");
+        check(fa_ingest_begin_f16(pipe, acc.data(), nullptr, 0) == FA_OK, "begin f16 2");
+        check(fa_ingest_add(pipe, &src0, &full, 1, 1.f, 1.f, 0) == FA_ERR_ARG, "f32 add on an f16 pipe");
+        check(fa_ingest_finish(pipe, 1.f) == FA_ERR_ARG, "f32 finish on an f16 pipe");
+        // errors mid-round, a chunk half filled, then the pipe reused: the abandoned rows do not join
+        check(fa_ingest_add_f16(pipe, &src0, &full, 1, 0x3C00, 0x3C00, 0) == FA_OK, "add f16 ok");
+        check(fa_ingest_add_f16(pipe, &src0, &shortb, 1, 0x3C00, 0x3C00, 0) == FA_ERR_SHAPE, "short f16 row rejected");
+        check(fa_ingest_add_f16(pipe, &src0, &full, 1, 0x3C00, 0x3800, 1) == FA_ERR_SHAPE, "mixed scores rejected f16");
+        check(fa_ingest_add_f16(pipe, &src0, &full, 1, 0x4700, 0x3C00, 0) == FA_OK, "add f16 ok 2");
+        check(fa_ingest_begin_f16(pipe, acc.data(), nullptr, 0) == FA_OK, "begin f16 after an abandoned round");
+        for (int64_t i = 0; i < N; ++i) {
+            const void* src = X.data() + i * P;
+            check(fa_ingest_add_f16(pipe, &src, &full, 1, a[i], s[i], 0) == FA_OK, "add f16 after abandon");
+        }
+        check(fa_ingest_finish_f16(pipe, total) == FA_OK, "finish f16 after abandon");
+        fa_fold_f16(X.data(), N, P, P, a.data(), nullptr, nullptr, total, 1, exp.data(), nullptr);
+        check(memcmp(exp.data(), acc.data(), P * 2) == 0, "bit-exact f16 after an abandoned round");
+        fa_ingest_destroy(pipe);
+        // the reverse: f16 entries on a float32 pipe
+        fa_ingest* p32 = nullptr;
+        check(fa_ingest_create(&p32, P, chunk * 2, slots, 0) == FA_OK, "create f32");
+        check(fa_ingest_begin_f16(p32, acc.data(), nullptr, 0) == FA_ERR_ARG, "f16 begin on an f32 pipe");
+        check(fa_ingest_begin(p32, acc32.data(), nullptr, 0) == FA_OK, "begin f32");
+        check(fa_ingest_add_f16(p32, &src0, &full, 1, 0x3C00, 0x3C00, 0) == FA_ERR_ARG, "f16 add on an f32 pipe");
+        check(fa_ingest_finish_f16(p32, 0x3C00) == FA_ERR_ARG, "f16 finish on an f32 pipe");
+        check(fa_ingest_finish(p32, 1.f) == FA_ERR_NO_CLIENTS, "empty f32 round after refused calls");
+        fa_ingest_destroy(p32);
+    }
+}
+
+// f2h / h2f against a few known patterns (the restated fold rests on them)
+static void check_half() {
+    check(f2h(1.0f) == 0x3C00 && f2h(-2.0f) == 0xC000 && f2h(65504.f) == 0x7BFF, "f2h normals");
+    check(f2h(65519.99f) == 0x7BFF && f2h(65520.f) == 0x7C00, "f2h overflow threshold");
+    check(f2h(5.9604645e-8f) == 0x0001 && f2h(2.9802322e-8f) == 0x0000 && f2h(2.98024e-8f) == 0x0001, "f2h subnormal");
+    check(f2h(6.097555e-5f) == 0x03FF && f2h(6.1035156e-5f) == 0x0400, "f2h subnormal / normal border");
+    check(f2h(1.00048828125f) == 0x3C00 && f2h(1.00146484375f) == 0x3C02, "f2h ties to even");
+    check(f2h(-0.0f) == 0x8000, "f2h -0");
+    for (uint32_t h = 0; h < 0x10000u; ++h) {
+        const uint16_t b = f2h(h2f((uint16_t)h));
+        const bool nan = (h & 0x7C00u) == 0x7C00u && (h & 0x3FFu);
+        check(nan ? ((b & 0x7C00u) == 0x7C00u && (b & 0x3FFu)) : b == h, "half round trip");
+    }
+}
+
 int main() {
+    check_half();
     std::vector<std::thread> ts;
     for (int t = 0; t < 3; ++t) ts.emplace_back(worker, t, 12);
+    for (int t = 0; t < 2; ++t) ts.emplace_back(worker_f16, t, 8);
     for (auto& t : ts) t.join();
     if (g_fail.load()) {
         fprintf(stderr, "%d failures\n", g_fail.load());
