@@ -11,6 +11,9 @@ reference (fed_avg_aggregator.py:31-41, stall_aware_aggregation.py:52-66):
 Python-scalar weights are *weak* (rounded once to the array dtype), the total
 is a Python ``sum`` (exact for ints), scores are Python floats from a double
 division.  The kernels then fold in client order with separate roundings.
+Which dtype numpy gives every product, running sum and the quotient is decided
+in one place, fold_plan: a fold of one dtype throughout runs in one uniform
+kernel, any other is folded term by term as numpy types it (_fold_general).
 
 There is no CPU fallback anywhere in this module: every output element is
 computed by libfedavg_hip.so on the GPU, or the call raises.
@@ -18,10 +21,11 @@ computed by libfedavg_hip.so on the GPU, or the call raises.
 from __future__ import annotations
 
 import ctypes
+import functools
 import operator
 import os
 import threading
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -53,7 +57,9 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 def result_dtype(in_dtype: np.dtype, weights: Sequence, scores: Optional[Sequence] = None,
                  total=None) -> np.dtype:
-    """dtype numpy gives `reduce(add, [x * n_i (* s_i)]) / sum(n)` (NEP 50 weak Python scalars)."""
+    """dtype numpy gives `reduce(add, [x * n_i (* s_i)]) / sum(n)` (NEP 50 weak Python scalars).
+    The result's dtype only: fold_plan says how numpy gets there.  The routes ask it
+    whether a float32 / float16 fold stays in its dtype (then the plan is uniform too)."""
     in_dtype = np.dtype(in_dtype)
     if in_dtype.kind == "f":
         # Python bool / int / float scalars are weak: a float array keeps its dtype
@@ -70,6 +76,106 @@ def result_dtype(in_dtype: np.dtype, weights: Sequence, scores: Optional[Sequenc
     if dt.kind in "iu" or dt.kind == "b":
         dt = np.result_type(dt, np.float64)  # true_divide of integers
     return dt
+
+
+_WEAK = (bool, int, float)
+_F16, _F32, _F64 = np.dtype(np.float16), np.dtype(np.float32), np.dtype(np.float64)
+_I32_MIN, _I32_END = -2 ** 31, 2 ** 31
+_I63 = 2 ** 63
+
+
+class FoldPlan(NamedTuple):
+    """The dtypes numpy gives every step of `reduce(add, [layer_i * n_i (* s_i)]) / total`.
+
+    prod[i]   dtype of `layer_i * n_i`
+    term[i]   dtype of the finished term (`* s_i` applied; prod[i] without scores)
+    acc[i]    dtype of the running sum once term i is in it (acc[0] is term[0])
+    quot      dtype of the quotient (None when no row is folded)
+    uniform   the one compute dtype of a fold the uniform kernels do -- every
+              row widened once to it, every product, sum and the quotient in it
+              (an integer fold divides into float64) -- else None."""
+    prod: tuple
+    term: tuple
+    acc: tuple
+    quot: Optional[np.dtype]
+    uniform: Optional[np.dtype]
+
+
+def _scalar_key(x):
+    """What decides the dtype numpy gives `array (op) x`, as a hashable key:
+    the type of a weak Python scalar, the dtype of a numpy scalar.  None where
+    the value itself matters (a Python int that some integer dtype cannot hold
+    raises OverflowError, a huge one does on a float array) or for any other
+    object: numpy is then asked with the value."""
+    t = type(x)
+    if t is float or t is bool:
+        return t
+    if t is int:
+        return int if _I32_MIN <= x < _I32_END else None
+    if isinstance(x, np.generic) and x.dtype.kind in "biuf":
+        return x.dtype
+    return None
+
+
+@functools.lru_cache(maxsize=None)
+def _op_dtype_keyed(op, dt, key):
+    x = key(1) if isinstance(key, type) else key.type(1)
+    return op(np.empty(0, dt), x).dtype
+
+
+def _op_dtype(op, dt, x):
+    """dtype of op(array of dtype dt, scalar x): numpy itself, on a zero-length
+    array, so it also raises what numpy raises."""
+    key = _scalar_key(x)
+    if key is not None:
+        return _op_dtype_keyed(op, dt, key)
+    with np.errstate(all="ignore"):  # a Python int beyond a float dtype's range becomes inf, as in the fold
+        return op(np.empty(0, dt), x).dtype
+
+
+@functools.lru_cache(maxsize=None)
+def _add_dtype(a, b):
+    return np.add(np.empty(0, a), np.empty(0, b)).dtype
+
+
+def fold_plan(row_dtypes, weights: Sequence, scores: Optional[Sequence] = None, total=None) -> FoldPlan:
+    """The promotion plan of one fold, asked of numpy on zero-length arrays
+    (NEP 50: every product is typed on its own, a Python number is weak, a
+    numpy scalar is not).  Pure host code.  row_dtypes: one dtype for every
+    row, or one per row (the stream variants put their float64 running model
+    ahead of the clients' rows).  zip() truncation over rows, weights and
+    scores is kept; `total` defaults to the sum of ALL weights.  Raises what
+    the reference's expression raises (OverflowError for a Python int an
+    integer layer cannot hold)."""
+    n = min(len(weights), len(scores) if scores is not None else len(weights))
+    if isinstance(row_dtypes, (list, tuple)):
+        n = min(n, len(row_dtypes))
+        rows = [np.dtype(d) for d in row_dtypes[:n]]
+    else:
+        rows = [np.dtype(row_dtypes)] * n
+    if total is None:
+        total = sum(weights)
+    if n and rows[0].kind == "f" and rows.count(rows[0]) == n:
+        # float rows under weak Python numbers keep their dtype throughout
+        vals = [*weights[:n], total] if scores is None else [*weights[:n], *scores[:n], total]
+        if set(map(type, vals)) <= set(_WEAK) and all(type(v) is not int or -_I63 <= v < _I63 for v in vals):
+            same = (rows[0],) * n
+            return FoldPlan(same, same, same, rows[0], rows[0] if rows[0] in _NP_TO_TORCH else None)
+    prod, term, acc = [], [], []
+    for i in range(n):
+        p = _op_dtype(np.multiply, rows[i], weights[i])
+        t = p if scores is None else _op_dtype(np.multiply, p, scores[i])
+        prod.append(p)
+        term.append(t)
+        acc.append(t if not acc else _add_dtype(acc[-1], t))
+    if not n:
+        return FoldPlan((), (), (), None, None)
+    quot = _op_dtype(np.true_divide, acc[-1], total)
+    c = acc[-1]
+    uniform = c if (c in _NP_TO_TORCH and quot == (c if c.kind == "f" else _F64)
+                    and all(r in _NP_TO_TORCH for r in rows)
+                    and prod.count(c) == n and term.count(c) == n and acc.count(c) == n) else None
+    return FoldPlan(tuple(prod), tuple(term), tuple(acc), quot, uniform)
 
 
 _EXACT_F64 = float(2 ** 53)
@@ -290,13 +396,25 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
         raise InvalidParameterShapeError(f"unsupported dtype {X.dtype}")
     # the common case (float32 layers, Python-number weights) skips the type scan
     fw = Factors.weak_f32(weights, scores, total) if in_dt == np.float32 else None
-    dt = np.dtype(np.float32) if fw is not None else result_dtype(in_dt, weights, scores, total)
-    int_path = in_dt.kind == "i" and scores is None and all(isinstance(w, int) for w in weights)
-    if int_path:
+    if fw is not None:
+        dt = _F32
+    elif N == 0:
+        dt = result_dtype(in_dt, weights, scores, total)
+    else:
+        plan = fold_plan(in_dt, weights, scores, total)
+        dt = plan.uniform
+        if dt is None:  # numpy types this fold term by term: no single kernel is its arithmetic
+            return _fold_general([X], plan, weights, scores, total, out)
+    if dt.kind == "i":
+        # `layer * n` and the running sum stay in the integer dtype and wrap, the
+        # quotient is float64; numpy-scalar weights may widen int32 rows to int64 first
         f = Factors(weights, None, dt, int_weights=True, total=total)
         a, _ = f.to(dev)
+        if in_dt != dt:
+            X = X.to(_NP_TO_TORCH[dt])
+            ldx = X.stride(0) if N > 1 else max(P, 1)
         out = out if out is not None else torch.empty(P, dtype=torch.float64, device=dev)
-        name = "fa_fedavg_i32" if in_dt == np.int32 else "fa_fedavg_i64"
+        name = "fa_fedavg_i32" if dt == np.int32 else "fa_fedavg_i64"
         _lib.call(name, X.data_ptr(), N, P, ldx, a.data_ptr(), f.div, out.data_ptr(), st)
         return out
     if dt == np.float16:
@@ -314,10 +432,6 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
         _lib.call("fa_fedavg_f16", X.data_ptr(), N, P, ldx, a.data_ptr(), _ptr(s),
                   int(np.asarray(f.div, dtype=np.float16).view(np.uint16)), out.data_ptr(), st)
         return out
-    if in_dt == np.float16 and dt == np.float32:
-        terms = _mixed_f16_terms(weights, scores, sum(weights) if total is None else total)
-        if terms is not None:  # Python-number and numpy-scalar weights mixed: numpy widens part-way
-            return _fold_f16_mixed(X, N, P, ldx, weights, scores, total, terms, out)
     if dt not in (np.float32, np.float64):
         raise InvalidParameterShapeError(f"unsupported result dtype {dt} (input {in_dt})")
     if in_dt != dt:
@@ -347,99 +461,162 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
     return out
 
 
-_WEAK = (bool, int, float)
+def _cast_scalars(values: Sequence, dt: np.dtype) -> np.ndarray:
+    """The scalars as numpy converts them to the dtype of the operation they enter."""
+    if dt.kind == "i":
+        return np.array([int(v) for v in values], dtype=dt)
+    return round_scalars(values, dt)
 
 
-def _mixed_f16_terms(weights: Sequence, scores: Optional[Sequence], total) -> Optional[list]:
-    """float16 rows whose weights mix Python numbers with numpy scalars: the
-    dtype numpy gives each row's term, or None when the plain promoted fold is
-    already numpy's (every term of one dtype) or the mix is not one this handles.
-
-    numpy types every product on its own: `layer * n_i` stays float16 under a
-    Python number (weak, NEP 50) and takes np.result_type(float16, n_i.dtype)
-    under a numpy scalar; reduce(np.add) then runs in float16 up to the first
-    float32 term and in float32 from there on, a later float16 term still
-    being rounded to float16 before it is added.  Handled: Python-number
-    scores (or none), every term float16 or float32 with both present, a total
-    that leaves the quotient float32."""
-    f16, f32 = np.dtype(np.float16), np.dtype(np.float32)
-    if scores is not None and not all(type(x) in _WEAK for x in scores):
-        return None
-    terms = []
-    for w in weights:
-        d = f16 if type(w) in _WEAK else (np.result_type(f16, w.dtype) if isinstance(w, np.generic) else None)
-        if d not in (f16, f32):
-            return None
-        terms.append(d)
-    if f16 not in terms or f32 not in terms:
-        return None
-    if type(total) not in _WEAK and not (isinstance(total, np.generic) and np.result_type(f32, total.dtype) == f32):
-        return None
-    return terms
-
-
-def _fold_f16_mixed(X: torch.Tensor, N: int, P: int, ldx: int, weights, scores, total, terms, out):
-    """numpy's fold of float16 rows under mixed weights (_mixed_f16_terms), bit
-    for bit, from the kernels the uniform folds use:
-      rows ahead of the first float32 term   fa_fold_f16, unfinalised: the float16 running sum,
-                                             widened exactly to start the float32 accumulator
-      a run of float32 terms                 the rows widened exactly, fa_fold_f32 continuing the accumulator
-      a run of float16 terms after that      each term from fa_fold_f16 (one row, unfinalised), widened
-                                             exactly, added in row order by fa_fold_f32 with factor 1
-      the quotient                           fa_fold_f32, divide only, by fl32(total)
-    A few launches per run: this serves odd inputs, not a hot path."""
+def _fold_general(segs: List[torch.Tensor], plan: FoldPlan, weights: Sequence, scores: Optional[Sequence],
+                  total, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """numpy's fold where it types the terms one by one (plan.uniform is None:
+    strong and weak scalars mixed, numpy-scalar scores, integer rows under
+    scores, rows of several dtypes, a strong total), bit for bit, from the
+    kernels the uniform folds use.  segs: the rows in order, as [k, P]
+    matrices of one dtype each.  Over each run of rows that share a plan entry:
+      product   in prod[i]: the rows widened once (exact; an integer to float64
+                rounds as numpy's cast does).  Where it is narrower than what
+                follows it is formed alone -- one unfinalised one-row launch of
+                fa_fold_f16 / fa_fold_f32 per row, a wrapping torch integer
+                multiply for integer rows -- and widened exactly
+      score     likewise in term[i]
+      sum       in acc[i]: fa_fold_f16 / fa_fold_f32 continue the accumulator
+                (widened exactly where the dtype grows) over the run, with the
+                factors that are still to be applied, or factor 1 over finished
+                terms (x * 1 is exact).  An integer sum wraps, so its order is
+                free: a torch integer sum.  float64 has no accumulate entry but
+                nothing is wider: from the first float64 sum on, the widened
+                accumulator and every later term are rows of one matrix that
+                fa_fedavg_f64 folds once, in order, with the true divisor
+      quotient  in plan.quot, by the total rounded to it.
+    A few launches per run of rows: this serves odd inputs, not a hot path."""
     if torch.cuda.is_current_stream_capturing():
-        raise InvalidParameterShapeError("the float16 fold does not run under stream capture "
-                                         "(the captured factor fill carries float32 factors only)")
-    dev, st = X.device, stream_ptr(X.device)
-    f16, f32 = np.dtype(np.float16), np.dtype(np.float32)
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=dev)
+        raise InvalidParameterShapeError("a fold that numpy types term by term (mixed scalar kinds or row dtypes) "
+                                         "does not run under stream capture")
+    dts = {*plan.prod, *plan.term, *plan.acc, plan.quot}
+    if not dts <= set(_NP_TO_TORCH) or any(x.dtype not in _TORCH_TO_NP for x in segs):
+        raise InvalidParameterShapeError(f"unsupported dtype mix: rows {sorted({str(x.dtype) for x in segs})}, "
+                                         f"terms and sums {sorted(map(str, dts))}")
+    dev, P, Q = segs[0].device, segs[0].shape[1], plan.quot
+    st = stream_ptr(dev)
     total = sum(weights) if total is None else total
-    pad = np.zeros(2 + (N & 1), np.float16)  # the half factors end on a 4-byte word inside the staged block
-    halves = lambda v: np.concatenate([round_scalars(v, f16), pad])
-    parts = [halves(weights), round_scalars(weights, f32), np.ones(N, np.float32)]
-    if scores is not None:
-        parts += [halves(scores), round_scalars(scores, f32)]
-    staged = stage_factors(parts, dev)
-    a16, a32, one32 = staged[:3]
-    s16, s32 = (staged[3], staged[4]) if scores is not None else (None, None)
+    div = Q.type(total)
+    res = torch.empty(P, dtype=_NP_TO_TORCH[Q], device=dev)
+    if out is not None:
+        _check_out("out", out, res.dtype, P)
     L = _lib.load()
+    ones = lambda k, dt: np.ones(k, dt)
 
-    def at(t, i, size):
-        return None if t is None else t.data_ptr() + size * i
+    def factors(dt, a, s):
+        if dt == _F16:  # the half factors end on a 4-byte word inside the staged block
+            pad = np.zeros(2 + (len(a) & 1), np.float16)
+            a, s = np.concatenate([a, pad]), (None if s is None else np.concatenate([s, pad]))
+        staged = stage_factors([a] if s is None else [a, s], dev)
+        return staged[0], (staged[1] if s is not None else None)
 
-    def fold16(i, n, dst):  # float16 terms of rows [i, i + n), summed in float16, not divided
-        _lib.check(L.fa_fold_f16(X.data_ptr() + 2 * i * ldx, n, P, ldx, at(a16, i, 2), at(s16, i, 2), None, 0, 0,
-                                 dst.data_ptr(), st), "fa_fold_f16")
+    def pitch(Y):
+        return Y.stride(0) if Y.shape[0] > 1 else max(P, 1)
 
-    def fold32(Y, n, a, s, started):  # continue the float32 accumulator over the rows of Y
-        _lib.check(L.fa_fold_f32(Y.data_ptr(), n, P, Y.stride(0) if n > 1 else max(P, 1), a, s,
-                                 out.data_ptr() if started else None, 0.0, 0, out.data_ptr(), st), "fa_fold_f32")
-
-    i = terms.index(f32)
-    if i > 0:
-        head = torch.empty(P, dtype=torch.float16, device=dev)
-        fold16(0, i, head)
-        out[:P].copy_(head)  # exact widening
-    started = i > 0
-    while i < N:
-        j = i
-        while j < N and terms[j] == terms[i]:
-            j += 1
-        if terms[i] == f32:
-            Y = X[i:j, :P].to(torch.float32).contiguous()
-            fold32(Y, j - i, at(a32, i, 4), at(s32, i, 4), started)
+    def fold(Y, dt, a, s, acc):  # acc (+)= the terms fl(fl(Y_r * a_r) * s_r) in row order, all in dt (16/32 bit)
+        dst = acc if acc is not None else torch.empty(P, dtype=Y.dtype, device=dev)
+        ad, sd = factors(dt, a, s)
+        if dt == _F16:
+            _lib.check(L.fa_fold_f16(Y.data_ptr(), Y.shape[0], P, pitch(Y), ad.data_ptr(), _ptr(sd), _ptr(acc), 0, 0,
+                                     dst.data_ptr(), st), "fa_fold_f16")
         else:
-            T = torch.empty((j - i, P), dtype=torch.float16, device=dev)
-            for r in range(i, j):
-                fold16(r, 1, T[r - i])
-            fold32(T.to(torch.float32), j - i, one32.data_ptr(), None, started)
-        started = True
-        i = j
-    _lib.check(L.fa_fold_f32(None, 0, P, P, None, None, out.data_ptr(), float(np.float32(total)), 1, out.data_ptr(),
-                             st), "fa_fold_f32(finalize)")
-    return out
+            _lib.check(L.fa_fold_f32(Y.data_ptr(), Y.shape[0], P, pitch(Y), ad.data_ptr(), _ptr(sd), _ptr(acc), 0.0, 0,
+                                     dst.data_ptr(), st), "fa_fold_f32")
+        return dst
+
+    def products(Y, dt, a):  # [k, P]: fl(Y_r * a_r) in dt, every row on its own
+        if dt.kind == "i":
+            return Y * torch.from_numpy(a).to(dev)[:, None]  # wraps as numpy's integer multiply
+        k, esz = Y.shape[0], dt.itemsize
+        T = torch.empty((k, P), dtype=Y.dtype, device=dev)
+        ad, _ = factors(dt, a, None)
+        for r in range(k):
+            x, d, f = Y.data_ptr() + r * Y.stride(0) * esz, T.data_ptr() + r * P * esz, ad.data_ptr() + r * esz
+            if dt == _F64:
+                _lib.check(L.fa_fedavg_f64(x, 1, P, max(P, 1), f, None, 1.0, d, st), "fa_fedavg_f64")
+            elif dt == _F32:
+                _lib.check(L.fa_fold_f32(x, 1, P, max(P, 1), f, None, None, 0.0, 0, d, st), "fa_fold_f32")
+            else:
+                _lib.check(L.fa_fold_f16(x, 1, P, max(P, 1), f, None, None, 0, 0, d, st), "fa_fold_f16")
+        return T
+
+    if P == 0:
+        return res if out is None else out
+    acc, acc_dt = None, None
+    tail: list = []  # from the first float64 sum on: (rows [k, P] float64, a, s or None)
+    i = 0
+    for X in segs:
+        r0 = 0
+        while r0 < X.shape[0]:
+            sig = (plan.prod[i], plan.term[i], plan.acc[i])
+            r1 = r0 + 1
+            while r1 < X.shape[0] and (plan.prod[i + r1 - r0], plan.term[i + r1 - r0], plan.acc[i + r1 - r0]) == sig:
+                r1 += 1
+            k = r1 - r0
+            d1, d2, D = sig
+            w = weights[i:i + k]
+            sc = None if scores is None else scores[i:i + k]
+            if acc is not None and acc_dt != D:
+                if D == _F64:
+                    tail.append((acc.to(torch.float64)[None, :], ones(1, _F64), None))
+                    acc = None
+                else:
+                    acc = acc.to(_NP_TO_TORCH[D])
+            acc_dt = D
+            Y = X[r0:r1].to(_NP_TO_TORCH[d1])
+            if d1 == d2 == D:
+                a, s = _cast_scalars(w, D), (None if sc is None else _cast_scalars(sc, D))
+            else:
+                Y = products(Y, d1, _cast_scalars(w, d1))
+                if d2 == D:  # the score multiply belongs to the sum's dtype
+                    a = ones(k, D) if sc is None else _cast_scalars(sc, D)
+                else:  # the finished term is narrower than the running sum
+                    if sc is not None:
+                        Y = products(Y.to(_NP_TO_TORCH[d2]), d2, _cast_scalars(sc, d2))
+                    a = ones(k, D)
+                Y, s = Y.to(_NP_TO_TORCH[D]), None
+            if D == _F64:
+                tail.append((Y, a, s))
+            elif D.kind == "i":
+                t = Y * torch.from_numpy(a).to(dev)[:, None]
+                if s is not None:
+                    t = t * torch.from_numpy(s).to(dev)[:, None]
+                t = t.sum(0, dtype=Y.dtype)  # a sum that wraps has no order
+                acc = t if acc is None else acc + t
+            else:
+                acc = fold(Y, D, a, s, acc)
+            i += k
+            r0 = r1
+    if tail:
+        Y = tail[0][0] if len(tail) == 1 else torch.cat([t[0] for t in tail])
+        a = np.concatenate([t[1] for t in tail])
+        s = None
+        if any(t[2] is not None for t in tail):
+            s = np.concatenate([t[2] if t[2] is not None else ones(len(t[1]), _F64) for t in tail])
+        ad, sd = factors(_F64, a, s)
+        _lib.check(L.fa_fedavg_f64(Y.data_ptr(), Y.shape[0], P, pitch(Y), ad.data_ptr(), _ptr(sd), float(div),
+                                   res.data_ptr(), st), "fa_fedavg_f64")
+    else:
+        acc = acc.to(res.dtype)
+        if Q == _F16:
+            _lib.check(L.fa_fold_f16(None, 0, P, P, None, None, acc.data_ptr(), int(div.view(np.uint16)), 1,
+                                     res.data_ptr(), st), "fa_fold_f16(finalize)")
+        elif Q == _F32:
+            _lib.check(L.fa_fold_f32(None, 0, P, P, None, None, acc.data_ptr(), float(div), 1, res.data_ptr(), st),
+                       "fa_fold_f32(finalize)")
+        else:
+            ad, _ = factors(_F64, ones(1, _F64), None)
+            _lib.check(L.fa_fedavg_f64(acc.data_ptr(), 1, P, P, ad.data_ptr(), None, float(div), res.data_ptr(), st),
+                       "fa_fedavg_f64(finalize)")
+    if out is not None:
+        out.reshape(-1)[:P].copy_(res)
+        return out
+    return res
 
 
 _rounds_states: dict = {}
@@ -810,16 +987,17 @@ def _layer_meta(parameters, n_eff):
     for li in range(L):
         ref = parameters[0][li]
         shp = tuple(ref.shape)
-        dt = ref.dtype
+        dt, mixed = ref.dtype, False
         for ci in range(1, n_eff):
             x = parameters[ci][li]
             if tuple(x.shape) != shp:
                 raise InvalidParameterShapeError(
                     f"layer {li}: client {ci} has shape {tuple(x.shape)}, client 0 has {shp}")
-            if x.dtype != dt:
-                raise InvalidParameterShapeError(f"layer {li}: client {ci} dtype {x.dtype} != {dt}")
+            mixed = mixed or x.dtype != dt
         shapes.append(shp)
-        dtypes.append(dt)
+        # numpy folds rows of several dtypes too (the stream variants put their float64
+        # running model ahead of integer rows): such a layer carries its per-row dtypes
+        dtypes.append(tuple(parameters[ci][li].dtype for ci in range(n_eff)) if mixed else dt)
     return L, shapes, dtypes
 
 
@@ -855,6 +1033,9 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
     L outputs (numpy in -> numpy out, tensors in -> CUDA tensors out).  zip()
     truncation over clients/weights/scores and over layers is kept
     (fed_avg_aggregator.py:32-41); the divisor is the sum of ALL weights.
+    Clients' layers must agree in shape; where their dtypes differ (the stream
+    variants' float64 running model ahead of integer rows) the layer is folded
+    as numpy types it, row by row (fold_plan).
 
     devices: several GPUs of this process (multigpu.py): host float32 layers
     are folded one column bucket per GPU, bit-identical to one GPU.  Other
@@ -885,7 +1066,23 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
         sizes = [int(np.prod(shapes[li])) if len(shapes[li]) else 1 for li in lis]
         P = sum(sizes)
         fp32_result = result_dtype(np.dtype(np.float32), total_weights, sc) == np.float32
-        if (not on_device and P > 0 and dtypes[lis[0]] == np.float16 and f16_stream_enabled() and
+        if isinstance(dtypes[lis[0]], tuple):
+            # rows of several dtypes: one stacked matrix per run of rows of one dtype,
+            # folded term by term as numpy types them
+            rdts = dtypes[lis[0]]
+            np_dts = [np.dtype(_TORCH_TO_NP.get(d, np.void) if on_device else d) for d in rdts]
+            if any(d not in _NP_TO_TORCH for d in np_dts):
+                raise InvalidParameterShapeError(f"layer {lis[0]}: unsupported row dtypes {sorted(set(map(str, rdts)))}")
+            plan = fold_plan(np_dts, w, sc, sum(total_weights))
+            segs, i = [], 0
+            while i < n_eff:
+                j = i + 1
+                while j < n_eff and rdts[j] == rdts[i]:
+                    j += 1
+                segs.append(_stack_group(parameters[i:j], j - i, lis, sizes, P, dev, on_device))
+                i = j
+            res = _fold_general(segs, plan, w, sc, sum(total_weights))
+        elif (not on_device and P > 0 and dtypes[lis[0]] == np.float16 and f16_stream_enabled() and
                 result_dtype(np.dtype(np.float16), total_weights, sc) == np.float16):
             # host float16 rows whose result stays float16: the same pipe with
             # 2-byte rows, binary16 factors and the chunked binary16 fold

@@ -132,18 +132,25 @@ def test_half_bits_are_numpys_roundings():
 def test_mixed_weight_terms_follow_numpys_promotion():
     """Which mixes of Python-number and numpy-scalar weights the float16 fold
     types row by row, checked against the dtypes numpy itself gives."""
-    f16, f32 = np.dtype(np.float16), np.dtype(np.float32)
+    f16, f32, f64 = np.dtype(np.float16), np.dtype(np.float32), np.dtype(np.float64)
     x = np.ones(3, np.float16)
     for w in ([3, 4, np.float32(5), 6], [np.float32(3), 4], [3, np.int16(4)], [3, np.uint8(4), np.float32(2)]):
-        terms = engine._mixed_f16_terms(w, None, sum(w))
-        assert terms == [(x * k).dtype for k in w], w
-        assert (x * w[0] / sum(w)).dtype in (f16, f32) and f32 in terms and f16 in terms
-    # one dtype throughout, or anything reaching float64: the plain promoted fold is numpy's already
-    assert engine._mixed_f16_terms([np.float32(1), np.float32(2)], None, np.float32(3)) is None
-    assert engine._mixed_f16_terms([1, 2], None, 3) is None
-    assert engine._mixed_f16_terms([1, np.float16(2)], None, 3) is None
-    assert engine._mixed_f16_terms([1, np.float64(2)], None, 3) is None
-    assert engine._mixed_f16_terms([1, np.int64(2)], None, 3) is None
-    assert engine._mixed_f16_terms([1, np.float32(2)], None, np.float64(3)) is None
-    assert engine._mixed_f16_terms([1, np.float32(2)], [0.5, np.float32(0.5)], 3) is None  # numpy-scalar scores
-    assert engine._mixed_f16_terms([1, np.float32(2)], [0.5, 0.25], 3) == [f16, f32]
+        plan = engine.fold_plan(f16, w, None, sum(w))
+        assert list(plan.term) == [(x * k).dtype for k in w], w
+        assert (x * w[0] / sum(w)).dtype in (f16, f32)
+        if f32 in plan.term and f16 in plan.term:
+            assert plan.uniform is None, w
+    # one dtype throughout: a uniform fold, the rows widened once
+    assert engine.fold_plan(f16, [np.float32(1), np.float32(2)], None, np.float32(3)).uniform == f32
+    assert engine.fold_plan(f16, [1, 2], None, 3).uniform == f16
+    assert engine.fold_plan(f16, [1, np.float16(2)], None, 3).uniform == f16
+    # anything reaching float64 part-way, a strong total, numpy-scalar scores: typed term by term as well
+    assert engine.fold_plan(f16, [1, np.float64(2)], None, 3).term == (f16, f64)
+    assert engine.fold_plan(f16, [1, np.int64(2)], None, 3).term == (f16, f64)
+    assert engine.fold_plan(f16, [1, np.float32(2)], None, np.float64(3)).quot == f64
+    assert engine.fold_plan(f16, [1, np.float32(2)], [0.5, np.float32(0.5)], 3).term == (f16, f32)
+    assert engine.fold_plan(f16, [1, np.float32(2)], [0.5, np.float32(0.5)], 3).prod == (f16, f32)
+    assert engine.fold_plan(f16, [1, np.float32(2)], [0.5, 0.25], 3).term == (f16, f32)
+    for mixed in (([1, np.float64(2)], None, 3), ([1, np.float32(2)], None, np.float64(3)),
+                  ([1, np.float32(2)], [0.5, np.float32(0.5)], 3), ([1, np.float32(2)], [0.5, 0.25], 3)):
+        assert engine.fold_plan(f16, *mixed).uniform is None, mixed
