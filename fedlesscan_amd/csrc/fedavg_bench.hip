@@ -586,7 +586,7 @@ int fa_fedavg_bf16_form(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, co
     if (!aligned16(X) || (ldx % 8) || !aligned16(out_f32) || (out_bf16 && !aligned16(out_bf16)))
         return fail(FA_ERR_ARG, "the vector forms need 16-B rows");
     StreamDevice on_stream_device(stream);
-    launch_bf16_form((Bf16Form)form, (hipStream_t)stream, X, N, P, ldx, a, s, divisor, out_f32, out_bf16);
+    launch_octet_form((Bf16Form)form, Bf16Fold{a, s, divisor, out_f32, out_bf16}, (hipStream_t)stream, X, N, P, ldx);
     return check_launch("fa_fedavg_bf16_form");
 }
 int fa_num_f16_forms(void) { return kNumBf16Forms; }
@@ -601,7 +601,7 @@ int fa_fedavg_f16_form(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, con
     if (P == 0) { g_err[0] = 0; return FA_OK; }
     if (!aligned16(X) || (ldx % 8) || !aligned16(out)) return fail(FA_ERR_ARG, "the vector forms need 16-B rows");
     StreamDevice on_stream_device(stream);
-    launch_f16_form((Bf16Form)form, (hipStream_t)stream, X, N, P, ldx, a, s, half_bits_to_float(divisor), out);
+    launch_octet_form((Bf16Form)form, F16Fold{a, s, half_bits_to_float(divisor), out}, (hipStream_t)stream, X, N, P, ldx);
     return check_launch("fa_fedavg_f16_form");
 }
 int fa_num_rows16_forms(void) { return kNumRows16Forms; }
@@ -637,35 +637,24 @@ int fa_fedavg_bf16_variant(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
     if (!aligned16(X) || (ldx % 8) || !aligned16(out_f32) || (out_bf16 && !aligned16(out_bf16)))
         return bf16_auto(X, N, P, ldx, a, s, divisor, out_f32, out_bf16, stream);
     hipStream_t st = (hipStream_t)stream;
-#define FA_BF(U, C)                                                                                         \
-    {                                                                                                       \
-        const int64_t per_block = (int64_t)kBlock * (C), units = (P >> 3) + ((P & 7) ? 1 : 0);            \
-        const dim3 grid((unsigned)((units + per_block - 1) / per_block));                                   \
-        if (s)                                                                                              \
-            hipLaunchKernelGGL((k_fedavg_bf16_v8<U, C, true>), grid, dim3(kBlock), 0, st, X, N, P, ldx, a, s, \
-                               divisor, out_f32, out_bf16);                                                 \
-        else                                                                                                \
-            hipLaunchKernelGGL((k_fedavg_bf16_v8<U, C, false>), grid, dim3(kBlock), 0, st, X, N, P, ldx, a,  \
-                               s, divisor, out_f32, out_bf16);                                              \
-    }
+    const Bf16Fold f{a, s, divisor, out_f32, out_bf16};
     switch (variant) {  // must match kBf16Variants[]
-        case 1: FA_BF(8, 1); break;
-        case 2: FA_BF(8, 2); break;
-        case 3: FA_BF(2, 8); break;
-        case 4: launch_bf16_gs<8, 2>(st, 1, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case 5: launch_bf16_gs<8, 4>(st, 1, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case 6: launch_bf16_gs<8, 2>(st, -1, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case 7: launch_bf16_gs<2, 8>(st, -1, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case 8: launch_bf16_bands<2, 8>(st, 2, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case 9: launch_bf16_bands<2, 8>(st, 4, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case 10: launch_bf16_bands<8, 2>(st, 4, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case 11: launch_bf16_bands<16, 2>(st, 4, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case 12: launch_bf16_bands<8, 4>(st, 4, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case 13: launch_bf16_bands<4, 4>(st, 4, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case 14: launch_bf16_bands<8, 2>(st, 3, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        default: launch_bf16_bands<16, 1>(st, 4, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
+        case 1: launch_octet_v8<8, 1>(f, st, X, N, P, ldx); break;
+        case 2: launch_octet_v8<8, 2>(f, st, X, N, P, ldx); break;
+        case 3: launch_octet_v8<2, 8>(f, st, X, N, P, ldx); break;
+        case 4: launch_octet_gs<8, 2>(f, st, 1, X, N, P, ldx); break;
+        case 5: launch_octet_gs<8, 4>(f, st, 1, X, N, P, ldx); break;
+        case 6: launch_octet_gs<8, 2>(f, st, -1, X, N, P, ldx); break;
+        case 7: launch_octet_gs<2, 8>(f, st, -1, X, N, P, ldx); break;
+        case 8: launch_octet_bands<2, 8>(f, st, 2, X, N, P, ldx); break;
+        case 9: launch_octet_bands<2, 8>(f, st, 4, X, N, P, ldx); break;
+        case 10: launch_octet_bands<8, 2>(f, st, 4, X, N, P, ldx); break;
+        case 11: launch_octet_bands<16, 2>(f, st, 4, X, N, P, ldx); break;
+        case 12: launch_octet_bands<8, 4>(f, st, 4, X, N, P, ldx); break;
+        case 13: launch_octet_bands<4, 4>(f, st, 4, X, N, P, ldx); break;
+        case 14: launch_octet_bands<8, 2>(f, st, 3, X, N, P, ldx); break;
+        default: launch_octet_bands<16, 1>(f, st, 4, X, N, P, ldx); break;
     }
-#undef FA_BF
     return check_launch("fedavg_bf16_variant");
 }
 

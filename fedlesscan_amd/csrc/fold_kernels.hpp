@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "fedavg_hip.h"
+#include "octet_grid.hpp"  // kBlock, octet_grid
 #include "tuner.hpp"
 
 #pragma clang fp contract(off)
@@ -67,8 +68,6 @@ int check_launch(const char* what) {
     g_err[0] = 0;
     return FA_OK;
 }
-
-constexpr int kBlock = 256;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // f32x4 in the global address space: loads through pointers read from memory
@@ -1382,13 +1381,74 @@ __device__ __forceinline__ void unpack_bf16x8(u32x4 w, f32x4& even, f32x4& odd) 
 __device__ __forceinline__ void st16(void* p, u32x4 v) { __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p)); }
 
 
+// ---------------------------------------------------------------------------
+// The 16-bit octet family (bf16 and float16: 8 columns per 16-byte load).  One
+// body per arithmetic serves every caller: an octet fold and a column fold for
+// bf16 (f32 accumulators), an octet fold and a column fold for float16 (packed
+// halves, with the ACC / FIN switches of the chunked fold), and one tile
+// dispatcher.  What differs between the callers is where row i starts, which
+// is a row source: a pitched matrix or a table of row bases.  bf16_tile, the
+// stacked bf16 tile that also runs inside the one-launch step, keeps its tile
+// dispatch and its tail-column loop written out: through the shared ones the
+// compiler laid its kernels out differently, and the one-octet form measured
+// 0.8 % slower at 1024 x 67K; written out, every stacked bf16 kernel compiles
+// to the instructions it had as a separate copy.  Compared per kernel with
+// tools/kernel_isa_diff.py against the separate copies (fedavg.hip: 210 of
+// 256 kernels identical, 24 the same up to register numbers and compare
+// sense, 22 float16 / row-table kernels restructured by the compiler and
+// timed inside the copies' own spread): profiles/octet_refactor/.
+//
+// A row source views the rows as octets (T = u32x4) or as single columns
+// (T = uint16_t), already offset to the lane's first octet / its column;
+// row(i) is the lane's pointer into row i.
+template <class T>
+struct PitchedRows {  // row i of a stacked matrix: p + i * ld
+    const T* p;
+    int64_t ld;
+    __device__ __forceinline__ const T* row(int64_t i) const { return p + i * ld; }
+};
+// The bases of a row table are read as global-memory pointers: through a
+// generic pointer the row loads would be flat loads, which also count on the
+// scalar loads' counter (every wait for a factor would then wait for the rows
+// in flight).  The base itself is a wave-uniform scalar load.
+typedef __attribute__((address_space(1))) const uint16_t gu16;
+typedef __attribute__((address_space(1))) const u32x4 gu32x4;
+template <class G>
+struct TableRows {  // row i of a row table: xi[i] + o (G = gu32x4 or gu16)
+    const uint16_t* const* xi;
+    int64_t o;
+    __device__ __forceinline__ const G* row(int64_t i) const { return (const G*)xi[i] + o; }
+};
+
+// The tiling of every octet kernel: a lane owns C octets spaced B apart.  A
+// full tile folds in one call, a partial last tile octet by octet, and the
+// trailing P % 8 columns [P & ~7, P) go to the lane with o0 == P / 8.
+template <int C, int B = kBlock, class Full, class One, class Tail>
+__device__ __forceinline__ void octet_tile(int64_t bid, int64_t P, Full full, One one, Tail tail) {
+    const int64_t no = P >> 3;  // full octets
+    const int64_t o0 = bid * (B * C) + threadIdx.x;
+    if (o0 + (int64_t)(C - 1) * B < no) {
+        full(o0);
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const int64_t o = o0 + (int64_t)c * B;
+        if (o < no) one(o);
+    }
+    const int64_t tb = no / (B * C), tl = (no % (B * C)) % B;
+    if ((P & 7) && bid == tb && (int64_t)threadIdx.x == tl) tail(no * 8);
+}
+
 // One row group of U rows x C octets: loaded (ld) and folded in row order (add)
-template <int U, int C>
-__device__ __forceinline__ void octets_ld(u32x4 (&v)[U][C], const u32x4* __restrict__ p, int64_t i, int64_t ldo) {
+template <int U, int C, class Rows>
+__device__ __forceinline__ void octets_ld(u32x4 (&v)[U][C], Rows src, int64_t i) {
 #pragma unroll
-    for (int u = 0; u < U; ++u)
+    for (int u = 0; u < U; ++u) {
+        const auto* r = src.row(i + u);
 #pragma unroll
-        for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(p + (i + u) * ldo + c * kBlock);
+        for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
+    }
 }
 template <int U, int C, bool SCORED>
 __device__ __forceinline__ void octets_add(f32x4 (&ev)[C], f32x4 (&od)[C], const u32x4 (&v)[U][C],
@@ -1406,19 +1466,21 @@ __device__ __forceinline__ void octets_add(f32x4 (&ev)[C], f32x4 (&od)[C], const
     }
 }
 
-template <int U, int C, bool SCORED, int B = kBlock, int WT = 0>
-__device__ __forceinline__ void fold_octets(const u32x4* __restrict__ p, int64_t ldo, int64_t N,
-                                            const float* __restrict__ a, const float* __restrict__ s,
-                                            float divisor, float* __restrict__ out, uint16_t* __restrict__ outb,
-                                            int64_t o0) {
+// The bf16 octet fold: the lane's C octets of rows 0..N-1 of src, in row order;
+// o0 = the lane's first octet in out / outb.
+template <int U, int C, bool SCORED, int B = kBlock, int WT = 0, class Rows>
+__device__ __forceinline__ void fold_octets(Rows src, int64_t N, const float* __restrict__ a,
+                                            const float* __restrict__ s, float divisor, float* __restrict__ out,
+                                            uint16_t* __restrict__ outb, int64_t o0) {
     static_assert(B == kBlock, "octet tiles are kBlock lanes wide");
     f32x4 ev[C], od[C];
     {
+        const auto* r = src.row(0);
         const float a0 = a[0], s0 = SCORED ? s[0] : 1.0f;
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             f32x4 e, o;
-            unpack_bf16x8(__builtin_nontemporal_load(p + c * B), e, o);
+            unpack_bf16x8(__builtin_nontemporal_load(r + c * B), e, o);
             ev[c] = term4<SCORED>(e, a0, s0);
             od[c] = term4<SCORED>(o, a0, s0);
         }
@@ -1426,17 +1488,18 @@ __device__ __forceinline__ void fold_octets(const u32x4* __restrict__ p, int64_t
     int64_t i = 1;
     for (; i + U <= N; i += U) {
         u32x4 v[U][C];
-        octets_ld<U, C>(v, p, i, ldo);
+        octets_ld<U, C>(v, src, i);
         // deep unrolls: every load of the group issued before the first add
         if constexpr (U >= 16) __builtin_amdgcn_sched_barrier(0);
         octets_add<U, C, SCORED>(ev, od, v, a, s, i);
     }
     for (; i < N; ++i) {
+        const auto* r = src.row(i);
         const float ai = a[i], si = SCORED ? s[i] : 1.0f;
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             f32x4 e, o;
-            unpack_bf16x8(__builtin_nontemporal_load(p + i * ldo + c * B), e, o);
+            unpack_bf16x8(__builtin_nontemporal_load(r + c * B), e, o);
             ev[c] = add4(ev[c], term4<SCORED>(e, ai, si));
             od[c] = add4(od[c], term4<SCORED>(o, ai, si));
         }
@@ -1475,8 +1538,21 @@ __device__ __forceinline__ void fold_octets(const u32x4* __restrict__ p, int64_t
     }
 }
 
-// bf16 rows: a lane owns C octets (8 columns, one 16-byte load per row each)
-// spaced kBlock apart; the trailing P%8 columns go to the lane with o0 == P/8.
+// One bf16 column (a P % 8 tail lane, the one-column kernel): the f32 quotient
+template <bool SCORED, class Rows>
+__device__ __forceinline__ float fold_column_bf16(Rows src, int64_t N, const float* __restrict__ a,
+                                                  const float* __restrict__ s, float divisor) {
+    float acc = term1<SCORED>(bf2f(*src.row(0)), a[0], SCORED ? s[0] : 1.0f);
+    for (int64_t i = 1; i < N; ++i) acc = acc + term1<SCORED>(bf2f(*src.row(i)), a[i], SCORED ? s[i] : 1.0f);
+    return acc / divisor;
+}
+// out (fp32) and outb (RNE bf16) of one column, each optional
+__device__ __forceinline__ void st_column_bf16(float q, float* out, uint16_t* outb, int64_t col) {
+    if (out) out[col] = q;
+    if (outb) outb[col] = f2bf_rne(q);
+}
+
+// One octet tile of a stacked bf16 matrix
 template <int U, int C, bool SCORED, int B = kBlock, int WT = 0>
 __device__ __forceinline__ void bf16_tile(int64_t bid, const uint16_t* __restrict__ X, int64_t N, int64_t P,
                                           int64_t ldx, const float* __restrict__ a, const float* __restrict__ s,
@@ -1486,13 +1562,13 @@ __device__ __forceinline__ void bf16_tile(int64_t bid, const uint16_t* __restric
     const int64_t o0 = bid * (B * C) + threadIdx.x;
     const u32x4* X8 = reinterpret_cast<const u32x4*>(X);
     if (o0 + (int64_t)(C - 1) * B < no) {
-        fold_octets<U, C, SCORED, B, WT>(X8 + o0, ldo, N, a, s, divisor, out, outb, o0);
+        fold_octets<U, C, SCORED, B, WT>(PitchedRows<u32x4>{X8 + o0, ldo}, N, a, s, divisor, out, outb, o0);
         return;
     }
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         const int64_t o = o0 + (int64_t)c * B;
-        if (o < no) fold_octets<U, 1, SCORED, B, WT>(X8 + o, ldo, N, a, s, divisor, out, outb, o);
+        if (o < no) fold_octets<U, 1, SCORED, B, WT>(PitchedRows<u32x4>{X8 + o, ldo}, N, a, s, divisor, out, outb, o);
     }
     const int64_t tb = no / (B * C), tl = (no % (B * C)) % B;
     if ((P & 7) && bid == tb && (int64_t)threadIdx.x == tl) {
@@ -1528,134 +1604,45 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_bf16_gs(
 }
 
 // bf16 list-of-rows form with every row 16-B aligned (fa_fedavg_bf16_ptrs,
-// rows_aligned != 0): fold_octets with row i's base read from xi[i] (a
-// wave-uniform scalar load) instead of p + i * ldo; o = the lane's first octet.
-// Same unpack, terms, adds, divide and stores, hence the same bits as the
-// stacked fold over the same rows.  Functions of their own beside the stacked
-// ones (as fold_quads_rows): the stacked kernels keep their generated code.
-// The bases are read as global-memory pointers: through a generic pointer the
-// row loads would be flat loads, which also count on the scalar loads' counter
-// (every wait for a factor would then wait for the rows in flight).
-typedef __attribute__((address_space(1))) const uint16_t gu16;
-typedef __attribute__((address_space(1))) const u32x4 gu32x4;
-
-template <int U, int C, bool SCORED>
-__device__ __forceinline__ void fold_octets_rows(const uint16_t* const* __restrict__ xi, int64_t o, int64_t N,
-                                                 const float* __restrict__ a, const float* __restrict__ s,
-                                                 float divisor, float* __restrict__ out,
-                                                 uint16_t* __restrict__ outb) {
-    f32x4 ev[C], od[C];
-    {
-        const gu32x4* r = (const gu32x4*)xi[0] + o;
-        const float a0 = a[0], s0 = SCORED ? s[0] : 1.0f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            f32x4 e, d;
-            unpack_bf16x8(__builtin_nontemporal_load(r + c * kBlock), e, d);
-            ev[c] = term4<SCORED>(e, a0, s0);
-            od[c] = term4<SCORED>(d, a0, s0);
-        }
-    }
-    int64_t i = 1;
-    for (; i + U <= N; i += U) {
-        u32x4 v[U][C];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const gu32x4* r = (const gu32x4*)xi[i + u] + o;
-#pragma unroll
-            for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
-        }
-        // deep unrolls: every load of the group issued before the first add
-        if constexpr (U >= 16) __builtin_amdgcn_sched_barrier(0);
-        octets_add<U, C, SCORED>(ev, od, v, a, s, i);
-    }
-    for (; i < N; ++i) {
-        const gu32x4* r = (const gu32x4*)xi[i] + o;
-        const float ai = a[i], si = SCORED ? s[i] : 1.0f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            f32x4 e, d;
-            unpack_bf16x8(__builtin_nontemporal_load(r + c * kBlock), e, d);
-            ev[c] = add4(ev[c], term4<SCORED>(e, ai, si));
-            od[c] = add4(od[c], term4<SCORED>(d, ai, si));
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const f32x4 e = div4(ev[c], divisor), d = div4(od[c], divisor);
-        const int64_t oc = o + (int64_t)c * kBlock;
-        if (out) {
-            f32x4* o4 = reinterpret_cast<f32x4*>(out) + 2 * oc;
-            st16(o4, __builtin_bit_cast(u32x4, f32x4{e.x, d.x, e.y, d.y}));
-            st16(o4 + 1, __builtin_bit_cast(u32x4, f32x4{e.z, d.z, e.w, d.w}));
-        }
-        if (outb) {
-            u32x4 b;
-            b.x = (uint32_t)f2bf_rne(e.x) | ((uint32_t)f2bf_rne(d.x) << 16);
-            b.y = (uint32_t)f2bf_rne(e.y) | ((uint32_t)f2bf_rne(d.y) << 16);
-            b.z = (uint32_t)f2bf_rne(e.z) | ((uint32_t)f2bf_rne(d.z) << 16);
-            b.w = (uint32_t)f2bf_rne(e.w) | ((uint32_t)f2bf_rne(d.w) << 16);
-            st16(reinterpret_cast<u32x4*>(outb) + oc, b);
-        }
-    }
-}
-
-// grid-stride over octet tiles (the tiling of bf16_tile: C octets per lane
-// spaced kBlock apart, a partial last tile octet by octet, the trailing P % 8
-// columns on the lane bf16_tile picks)
+// rows_aligned != 0): the stacked fold's body over a row table, hence its bits
+// over the same rows.  Grid-stride over octet tiles.
 template <int U, int C, bool SCORED>
 __global__ __launch_bounds__(kBlock) void k_fedavg_bf16_rows_gs(
     const uint16_t* const* __restrict__ xi, int64_t N, int64_t P, const float* __restrict__ a,
     const float* __restrict__ s, float divisor, float* __restrict__ out, uint16_t* __restrict__ outb,
     int64_t ntiles) {
-    const int64_t no = P >> 3;  // full octets
-    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-        const int64_t o0 = bid * (kBlock * C) + threadIdx.x;
-        if (o0 + (int64_t)(C - 1) * kBlock < no) {
-            fold_octets_rows<U, C, SCORED>(xi, o0, N, a, s, divisor, out, outb);
-            continue;
-        }
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int64_t o = o0 + (int64_t)c * kBlock;
-            if (o < no) fold_octets_rows<U, 1, SCORED>(xi, o, N, a, s, divisor, out, outb);
-        }
-        const int64_t tb = no / (kBlock * C), tl = (no % (kBlock * C)) % kBlock;
-        if ((P & 7) && bid == tb && (int64_t)threadIdx.x == tl) {
-            for (int64_t col = no * 8; col < P; ++col) {
-                float acc = term1<SCORED>(bf2f(((const gu16*)xi[0])[col]), a[0], SCORED ? s[0] : 1.0f);
-                for (int64_t i = 1; i < N; ++i)
-                    acc = acc + term1<SCORED>(bf2f(((const gu16*)xi[i])[col]), a[i], SCORED ? s[i] : 1.0f);
-                acc = acc / divisor;
-                if (out) out[col] = acc;
-                if (outb) outb[col] = f2bf_rne(acc);
-            }
-        }
-    }
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        octet_tile<C>(
+            bid, P,
+            [&](int64_t o) { fold_octets<U, C, SCORED>(TableRows<gu32x4>{xi, o}, N, a, s, divisor, out, outb, o); },
+            [&](int64_t o) { fold_octets<U, 1, SCORED>(TableRows<gu32x4>{xi, o}, N, a, s, divisor, out, outb, o); },
+            [&](int64_t col) {
+                for (; col < P; ++col)
+                    st_column_bf16(fold_column_bf16<SCORED>(TableRows<gu16>{xi, col}, N, a, s, divisor), out, outb, col);
+            });
 }
 
 // bf16 list-of-rows form, rows at any 2-B offset: lane = one column, row i's
 // base a wave-uniform load from the table, 8 rows of loads ahead of the ordered
-// adds (as k_fold_f32_rows_scalar); the arithmetic of the P % 8 tail above.
+// adds (as k_fold_f32_rows_scalar); the arithmetic of fold_column_bf16.
 template <bool SCORED>
 __global__ __launch_bounds__(kBlock) void k_fedavg_bf16_rows_scalar(
     const uint16_t* const* __restrict__ xi, int64_t N, int64_t P, const float* __restrict__ a,
     const float* __restrict__ s, float divisor, float* __restrict__ out, uint16_t* __restrict__ outb) {
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= P) return;
-    float acc = term1<SCORED>(bf2f(((const gu16*)xi[0])[c]), a[0], SCORED ? s[0] : 1.0f);
+    const TableRows<gu16> src{xi, c};
+    float acc = term1<SCORED>(bf2f(*src.row(0)), a[0], SCORED ? s[0] : 1.0f);
     int64_t i = 1;
     for (; i + 8 <= N; i += 8) {
         uint16_t v[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load((const gu16*)xi[i + u] + c);
+        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load(src.row(i + u));
 #pragma unroll
         for (int u = 0; u < 8; ++u) acc = acc + term1<SCORED>(bf2f(v[u]), a[i + u], SCORED ? s[i + u] : 1.0f);
     }
-    for (; i < N; ++i) acc = acc + term1<SCORED>(bf2f(((const gu16*)xi[i])[c]), a[i], SCORED ? s[i] : 1.0f);
-    acc = acc / divisor;
-    if (out) out[c] = acc;
-    if (outb) outb[c] = f2bf_rne(acc);
+    for (; i < N; ++i) acc = acc + term1<SCORED>(bf2f(*src.row(i)), a[i], SCORED ? s[i] : 1.0f);
+    st_column_bf16(acc / divisor, out, outb, c);
 }
 
 // ---------------------------------------------------------------------------
@@ -1691,7 +1678,8 @@ __device__ __forceinline__ _Float16 factor_h(const uint16_t* __restrict__ a, int
     const uint32_t w = *(cu32*)reinterpret_cast<const uint32_t*>(__builtin_align_down(q, 4));
     return h_bits((uint16_t)(__builtin_is_aligned(q, 4) ? w : (w >> 16)));
 }
-__device__ __forceinline__ f16x8 ld_h8(const u32x4* p) { return __builtin_bit_cast(f16x8, __builtin_nontemporal_load(p)); }
+template <class Ptr>  // const u32x4* or const gu32x4*
+__device__ __forceinline__ f16x8 ld_h8(Ptr p) { return __builtin_bit_cast(f16x8, __builtin_nontemporal_load(p)); }
 
 template <bool SCORED>
 __device__ __forceinline__ f16x8 term_h8(f16x8 x, _Float16 a, _Float16 s) {
@@ -1710,31 +1698,62 @@ __device__ __forceinline__ f16x8 div_h8(f16x8 acc, float d) {
 }
 __device__ __forceinline__ _Float16 div_h1(_Float16 acc, float d) { return (_Float16)((float)acc / d); }
 
-// One column of a float16 fold (the P % 8 tail lane and the scalar kernel)
-template <bool SCORED>
-__device__ __forceinline__ uint16_t fold_column_f16(const uint16_t* __restrict__ X, int64_t N, int64_t ldx,
-                                                    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
-                                                    float divisor) {
-    _Float16 acc = term_h1<SCORED>(h_bits(X[0]), factor_h(a, 0), SCORED ? factor_h(s, 0) : (_Float16)1);
-    for (int64_t i = 1; i < N; ++i)
-        acc = acc + term_h1<SCORED>(h_bits(X[i * ldx]), factor_h(a, i), SCORED ? factor_h(s, i) : (_Float16)1);
-    return bits_h(div_h1(acc, divisor));
+// The float16 folds carry the ACC / FIN switches of the fp32 fold_quads (the
+// chunked fold, fa_fold_f16, uses them; every other caller is !ACC, FIN):
+//   ACC: the fold continues from acc_in (halves; may alias out: a lane reads
+//        its own octets before it writes them); !ACC: acc = t_0, not 0 + t_0,
+//        so a column of -0.0 stays -0.0.
+//   FIN: out = fl16(acc / divisor) (div_h8); !FIN: out = acc as halves.  Every
+//        add already rounds to binary16, so the halves carried from one chunk
+//        to the next are the accumulator itself: any cut of the rows gives the
+//        bits of one fa_fedavg_f16 over all of them.
+// The partial accumulator is stored with plain stores (the next chunk's fold
+// reads it back), the final result non-temporally.
+template <bool FIN>
+__device__ __forceinline__ void st_h8(u32x4* out, f16x8 acc, float divisor) {
+    if constexpr (FIN) st16(out, __builtin_bit_cast(u32x4, div_h8(acc, divisor)));
+    else *out = __builtin_bit_cast(u32x4, acc);
 }
 
-template <int U, int C, bool SCORED>
-__device__ __forceinline__ void fold_octets_f16(const u32x4* __restrict__ p, int64_t ldo, int64_t N,
-                                                const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
-                                                float divisor, u32x4* __restrict__ out) {
+// One float16 column (a P % 8 tail lane, the one-column kernels)
+template <bool SCORED, bool ACC, bool FIN, class Rows>
+__device__ __forceinline__ uint16_t fold_column_f16(Rows src, int64_t N, const uint16_t* __restrict__ a,
+                                                    const uint16_t* __restrict__ s, const uint16_t* acc_in,
+                                                    float divisor) {
+    _Float16 acc;
+    int64_t i = 0;
+    if constexpr (ACC) {
+        acc = h_bits(*acc_in);
+    } else {
+        acc = term_h1<SCORED>(h_bits(*src.row(0)), factor_h(a, 0), SCORED ? factor_h(s, 0) : (_Float16)1);
+        i = 1;
+    }
+    for (; i < N; ++i)
+        acc = acc + term_h1<SCORED>(h_bits(*src.row(i)), factor_h(a, i), SCORED ? factor_h(s, i) : (_Float16)1);
+    return bits_h(FIN ? div_h1(acc, divisor) : acc);
+}
+
+// The float16 octet fold: the lane's C octets of the rows of src, in row
+// order; acc_in and out point at the lane's first octet.
+template <int U, int C, bool SCORED, bool ACC, bool FIN, class Rows>
+__device__ __forceinline__ void fold_octets_f16(Rows src, int64_t N, const uint16_t* __restrict__ a,
+                                                const uint16_t* __restrict__ s, const u32x4* acc_in, float divisor,
+                                                u32x4* out) {
     f16x8 acc[C];
-    {
+    int64_t i = 0;
+    if constexpr (ACC) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = __builtin_bit_cast(f16x8, acc_in[c * kBlock]);
+    } else {
+        const auto* r = src.row(0);
         const _Float16 a0 = factor_h(a, 0), s0 = SCORED ? factor_h(s, 0) : (_Float16)1;
 #pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = term_h8<SCORED>(ld_h8(p + c * kBlock), a0, s0);
+        for (int c = 0; c < C; ++c) acc[c] = term_h8<SCORED>(ld_h8(r + c * kBlock), a0, s0);
+        i = 1;
     }
-    int64_t i = 1;
     for (; i + U <= N; i += U) {
         u32x4 v[U][C];
-        octets_ld<U, C>(v, p, i, ldo);
+        octets_ld<U, C>(v, src, i);
         // 2 rows x 8 octets (and the deep unrolls, as the bf16 fold): every
         // load of the group issued before the first add, the factors' scalar
         // loads behind them.  Left to itself the scheduler interleaved the
@@ -1751,44 +1770,46 @@ __device__ __forceinline__ void fold_octets_f16(const u32x4* __restrict__ p, int
         }
     }
     for (; i < N; ++i) {
+        const auto* r = src.row(i);
         const _Float16 ai = factor_h(a, i), si = SCORED ? factor_h(s, i) : (_Float16)1;
 #pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(ld_h8(p + i * ldo + c * kBlock), ai, si);
+        for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(ld_h8(r + c * kBlock), ai, si);
     }
 #pragma unroll
-    for (int c = 0; c < C; ++c) st16(out + c * kBlock, __builtin_bit_cast(u32x4, div_h8(acc[c], divisor)));
+    for (int c = 0; c < C; ++c) st_h8<FIN>(out + c * kBlock, acc[c], divisor);
 }
 
-// float16 rows: the tiling of bf16_tile (C octets per lane spaced kBlock apart,
-// the trailing P % 8 columns on the lane with o0 == P / 8), one float16 output.
-template <int U, int C, bool SCORED>
+// One octet tile of a stacked float16 matrix (acc_in may alias out)
+template <int U, int C, bool SCORED, bool ACC, bool FIN>
 __device__ __forceinline__ void f16_tile(int64_t bid, const uint16_t* __restrict__ X, int64_t N, int64_t P,
                                          int64_t ldx, const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
-                                         float divisor, uint16_t* __restrict__ out) {
-    const int64_t no = P >> 3;  // full octets
+                                         const uint16_t* acc_in, float divisor, uint16_t* out) {
     const int64_t ldo = ldx >> 3;
-    const int64_t o0 = bid * (kBlock * C) + threadIdx.x;
     const u32x4* X8 = reinterpret_cast<const u32x4*>(X);
+    const u32x4* A8 = reinterpret_cast<const u32x4*>(acc_in);
     u32x4* O8 = reinterpret_cast<u32x4*>(out);
-    if (o0 + (int64_t)(C - 1) * kBlock < no) {
-        fold_octets_f16<U, C, SCORED>(X8 + o0, ldo, N, a, s, divisor, O8 + o0);
-        return;
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const int64_t o = o0 + (int64_t)c * kBlock;
-        if (o < no) fold_octets_f16<U, 1, SCORED>(X8 + o, ldo, N, a, s, divisor, O8 + o);
-    }
-    const int64_t tb = no / (kBlock * C), tl = (no % (kBlock * C)) % kBlock;
-    if ((P & 7) && bid == tb && (int64_t)threadIdx.x == tl)
-        for (int64_t col = no * 8; col < P; ++col) out[col] = fold_column_f16<SCORED>(X + col, N, ldx, a, s, divisor);
+    octet_tile<C>(
+        bid, P,
+        [&](int64_t o) {
+            fold_octets_f16<U, C, SCORED, ACC, FIN>(PitchedRows<u32x4>{X8 + o, ldo}, N, a, s, ACC ? A8 + o : nullptr,
+                                                    divisor, O8 + o);
+        },
+        [&](int64_t o) {
+            fold_octets_f16<U, 1, SCORED, ACC, FIN>(PitchedRows<u32x4>{X8 + o, ldo}, N, a, s, ACC ? A8 + o : nullptr,
+                                                    divisor, O8 + o);
+        },
+        [&](int64_t col) {
+            for (; col < P; ++col)
+                out[col] = fold_column_f16<SCORED, ACC, FIN>(PitchedRows<uint16_t>{X + col, ldx}, N, a, s,
+                                                             ACC ? acc_in + col : nullptr, divisor);
+        });
 }
 
 template <int U, int C, bool SCORED>
 __global__ __launch_bounds__(kBlock) void k_fedavg_f16_v8(
     const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
     const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
-    f16_tile<U, C, SCORED>(blockIdx.x, X, N, P, ldx, a, s, divisor, out);
+    f16_tile<U, C, SCORED, false, true>(blockIdx.x, X, N, P, ldx, a, s, nullptr, divisor, out);
 }
 
 // grid-stride over octet tiles, as k_fedavg_bf16_gs
@@ -1798,7 +1819,7 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f16_gs(
     const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out,
     int64_t ntiles) {
     for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
-        f16_tile<U, C, SCORED>(bid, X, N, P, ldx, a, s, divisor, out);
+        f16_tile<U, C, SCORED, false, true>(bid, X, N, P, ldx, a, s, nullptr, divisor, out);
 }
 
 // float16, one column per lane: any alignment / pitch
@@ -1808,116 +1829,18 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f16_scalar(
     const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= P) return;
-    out[c] = fold_column_f16<SCORED>(X + c, N, ldx, a, s, divisor);
+    out[c] = fold_column_f16<SCORED, false, true>(PitchedRows<uint16_t>{X + c, ldx}, N, a, s, nullptr, divisor);
 }
 
-// ---------------------------------------------------------------------------
-// float16 chunked fold (fa_fold_f16): fold_octets_f16 / fold_column_f16 with
-// the ACC / FIN switches of the fp32 fold_quads, as functions of their own so
-// that the stacked kernels above keep their code.
-//   ACC: the fold continues from acc_in (halves; may alias out: a lane reads
-//        its own octets before it writes them); !ACC: acc = t_0, not 0 + t_0,
-//        so a column of -0.0 stays -0.0.
-//   FIN: out = fl16(acc / divisor) (div_h8); !FIN: out = acc as halves.  Every
-//        add already rounds to binary16, so the halves carried from one chunk
-//        to the next are the accumulator itself: any cut of the rows gives the
-//        bits of one fa_fedavg_f16 over all of them.
-// The same packed-half multiply and add, the factor_h factor reads and the
-// non-temporal row loads.  The partial accumulator is stored with plain stores
-// (the next chunk's fold reads it back), the final result non-temporally.
-// ---------------------------------------------------------------------------
-template <bool FIN>
-__device__ __forceinline__ void st_h8(u32x4* out, f16x8 acc, float divisor) {
-    if constexpr (FIN) st16(out, __builtin_bit_cast(u32x4, div_h8(acc, divisor)));
-    else *out = __builtin_bit_cast(u32x4, acc);
-}
-
-template <int U, int C, bool SCORED, bool ACC, bool FIN>
-__device__ __forceinline__ void fold_octets_f16_chunk(const u32x4* __restrict__ p, int64_t ldo, int64_t N,
-                                                      const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
-                                                      const u32x4* acc_in, float divisor, u32x4* out) {
-    f16x8 acc[C];
-    int64_t i = 0;
-    if constexpr (ACC) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = __builtin_bit_cast(f16x8, acc_in[c * kBlock]);
-    } else {
-        const _Float16 a0 = factor_h(a, 0), s0 = SCORED ? factor_h(s, 0) : (_Float16)1;
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = term_h8<SCORED>(ld_h8(p + c * kBlock), a0, s0);
-        i = 1;
-    }
-    for (; i + U <= N; i += U) {
-        u32x4 v[U][C];
-        octets_ld<U, C>(v, p, i, ldo);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const _Float16 ai = factor_h(a, i + u), si = SCORED ? factor_h(s, i + u) : (_Float16)1;
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(__builtin_bit_cast(f16x8, v[u][c]), ai, si);
-        }
-    }
-    for (; i < N; ++i) {
-        const _Float16 ai = factor_h(a, i), si = SCORED ? factor_h(s, i) : (_Float16)1;
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(ld_h8(p + i * ldo + c * kBlock), ai, si);
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) st_h8<FIN>(out + c * kBlock, acc[c], divisor);
-}
-
-// One column of the chunked fold (the P % 8 tail lane and the scalar kernel)
-template <bool SCORED, bool ACC, bool FIN>
-__device__ __forceinline__ uint16_t fold_column_f16_chunk(const uint16_t* __restrict__ X, int64_t N, int64_t ldx,
-                                                          const uint16_t* __restrict__ a,
-                                                          const uint16_t* __restrict__ s, const uint16_t* acc_in,
-                                                          float divisor) {
-    _Float16 acc;
-    int64_t i = 0;
-    if constexpr (ACC) {
-        acc = h_bits(*acc_in);
-    } else {
-        acc = term_h1<SCORED>(h_bits(X[0]), factor_h(a, 0), SCORED ? factor_h(s, 0) : (_Float16)1);
-        i = 1;
-    }
-    for (; i < N; ++i)
-        acc = acc + term_h1<SCORED>(h_bits(X[i * ldx]), factor_h(a, i), SCORED ? factor_h(s, i) : (_Float16)1);
-    return bits_h(FIN ? div_h1(acc, divisor) : acc);
-}
-
-// Grid-stride over octet tiles (the tiling of f16_tile: C octets per lane spaced
-// kBlock apart, a partial last tile octet by octet, the P % 8 columns on the
-// lane with o0 == P / 8), balanced passes set by the launch.
+// float16 chunked fold (fa_fold_f16): the ACC / FIN forms of the same tile,
+// grid-stride with balanced passes set by the launch.
 template <int U, int C, bool SCORED, bool ACC, bool FIN>
 __global__ __launch_bounds__(kBlock) void k_fold_f16_gs(
     const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
     const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
     const uint16_t* acc_in, float divisor, uint16_t* out, int64_t ntiles) {  // acc_in may alias out
-    const int64_t no = P >> 3;  // full octets
-    const int64_t ldo = ldx >> 3;
-    const u32x4* X8 = reinterpret_cast<const u32x4*>(X);
-    const u32x4* A8 = reinterpret_cast<const u32x4*>(acc_in);
-    u32x4* O8 = reinterpret_cast<u32x4*>(out);
-    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-        const int64_t o0 = bid * (kBlock * C) + threadIdx.x;
-        if (o0 + (int64_t)(C - 1) * kBlock < no) {
-            fold_octets_f16_chunk<U, C, SCORED, ACC, FIN>(X8 + o0, ldo, N, a, s, ACC ? A8 + o0 : nullptr, divisor,
-                                                          O8 + o0);
-            continue;
-        }
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int64_t o = o0 + (int64_t)c * kBlock;
-            if (o < no)
-                fold_octets_f16_chunk<U, 1, SCORED, ACC, FIN>(X8 + o, ldo, N, a, s, ACC ? A8 + o : nullptr, divisor,
-                                                              O8 + o);
-        }
-        const int64_t tb = no / (kBlock * C), tl = (no % (kBlock * C)) % kBlock;
-        if ((P & 7) && bid == tb && (int64_t)threadIdx.x == tl)
-            for (int64_t col = no * 8; col < P; ++col)
-                out[col] = fold_column_f16_chunk<SCORED, ACC, FIN>(X + col, N, ldx, a, s, ACC ? acc_in + col : nullptr,
-                                                                   divisor);
-    }
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        f16_tile<U, C, SCORED, ACC, FIN>(bid, X, N, P, ldx, a, s, acc_in, divisor, out);
 }
 
 // chunked fold, one column per lane: rows, accumulator or output at any 2-B
@@ -1929,92 +1852,31 @@ __global__ __launch_bounds__(kBlock) void k_fold_f16_scalar(
     const uint16_t* acc_in, float divisor, uint16_t* out) {  // acc_in may alias out
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= P) return;
-    out[c] = fold_column_f16_chunk<SCORED, ACC, FIN>(X + c, N, ldx, a, s, ACC ? acc_in + c : nullptr, divisor);
+    out[c] = fold_column_f16<SCORED, ACC, FIN>(PitchedRows<uint16_t>{X + c, ldx}, N, a, s,
+                                               ACC ? acc_in + c : nullptr, divisor);
 }
 
 // float16 list-of-rows form with every row 16-B aligned (fa_fedavg_f16_ptrs,
-// rows_aligned != 0): fold_octets_f16 with row i's base read from xi[i] (a
-// wave-uniform scalar load); the packed-half arithmetic, the float32 divisor
-// and the scheduling-barrier rule of that function, hence its bits.
-__device__ __forceinline__ f16x8 ld_h8g(const gu32x4* p) { return __builtin_bit_cast(f16x8, __builtin_nontemporal_load(p)); }
-
-template <int U, int C, bool SCORED>
-__device__ __forceinline__ void fold_octets_f16_rows(const uint16_t* const* __restrict__ xi, int64_t o, int64_t N,
-                                                     const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
-                                                     float divisor, u32x4* __restrict__ out) {
-    f16x8 acc[C];
-    {
-        const gu32x4* r = (const gu32x4*)xi[0] + o;
-        const _Float16 a0 = factor_h(a, 0), s0 = SCORED ? factor_h(s, 0) : (_Float16)1;
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = term_h8<SCORED>(ld_h8g(r + c * kBlock), a0, s0);
-    }
-    int64_t i = 1;
-    for (; i + U <= N; i += U) {
-        u32x4 v[U][C];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const gu32x4* r = (const gu32x4*)xi[i + u] + o;
-#pragma unroll
-            for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
-        }
-        // as fold_octets_f16: 2 rows x 8 octets and the deep unrolls issue every
-        // load of the group before the first add; the 8-row forms keep the
-        // compiler's schedule
-        if constexpr (U >= 16 || (U == 2 && C == 8)) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const _Float16 ai = factor_h(a, i + u), si = SCORED ? factor_h(s, i + u) : (_Float16)1;
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(__builtin_bit_cast(f16x8, v[u][c]), ai, si);
-        }
-    }
-    for (; i < N; ++i) {
-        const gu32x4* r = (const gu32x4*)xi[i] + o;
-        const _Float16 ai = factor_h(a, i), si = SCORED ? factor_h(s, i) : (_Float16)1;
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(ld_h8g(r + c * kBlock), ai, si);
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) st16(out + o + c * kBlock, __builtin_bit_cast(u32x4, div_h8(acc[c], divisor)));
-}
-
-// One column of a float16 row-table fold (the P % 8 tail lane): fold_column_f16
-// with the rows' own bases
-template <bool SCORED>
-__device__ __forceinline__ uint16_t fold_column_f16_rows(const uint16_t* const* __restrict__ xi, int64_t col,
-                                                         int64_t N, const uint16_t* __restrict__ a,
-                                                         const uint16_t* __restrict__ s, float divisor) {
-    _Float16 acc = term_h1<SCORED>(h_bits(((const gu16*)xi[0])[col]), factor_h(a, 0),
-                                   SCORED ? factor_h(s, 0) : (_Float16)1);
-    for (int64_t i = 1; i < N; ++i)
-        acc = acc + term_h1<SCORED>(h_bits(((const gu16*)xi[i])[col]), factor_h(a, i),
-                                    SCORED ? factor_h(s, i) : (_Float16)1);
-    return bits_h(div_h1(acc, divisor));
-}
-
-// grid-stride over octet tiles, the tiling of f16_tile
+// rows_aligned != 0): the stacked fold's body over a row table, hence its bits
+// over the same rows.  Grid-stride over octet tiles.
 template <int U, int C, bool SCORED>
 __global__ __launch_bounds__(kBlock) void k_fedavg_f16_rows_gs(
     const uint16_t* const* __restrict__ xi, int64_t N, int64_t P, const uint16_t* __restrict__ a,
     const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out, int64_t ntiles) {
-    const int64_t no = P >> 3;  // full octets
     u32x4* O8 = reinterpret_cast<u32x4*>(out);
-    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-        const int64_t o0 = bid * (kBlock * C) + threadIdx.x;
-        if (o0 + (int64_t)(C - 1) * kBlock < no) {
-            fold_octets_f16_rows<U, C, SCORED>(xi, o0, N, a, s, divisor, O8);
-            continue;
-        }
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int64_t o = o0 + (int64_t)c * kBlock;
-            if (o < no) fold_octets_f16_rows<U, 1, SCORED>(xi, o, N, a, s, divisor, O8);
-        }
-        const int64_t tb = no / (kBlock * C), tl = (no % (kBlock * C)) % kBlock;
-        if ((P & 7) && bid == tb && (int64_t)threadIdx.x == tl)
-            for (int64_t col = no * 8; col < P; ++col) out[col] = fold_column_f16_rows<SCORED>(xi, col, N, a, s, divisor);
-    }
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        octet_tile<C>(
+            bid, P,
+            [&](int64_t o) {
+                fold_octets_f16<U, C, SCORED, false, true>(TableRows<gu32x4>{xi, o}, N, a, s, nullptr, divisor, O8 + o);
+            },
+            [&](int64_t o) {
+                fold_octets_f16<U, 1, SCORED, false, true>(TableRows<gu32x4>{xi, o}, N, a, s, nullptr, divisor, O8 + o);
+            },
+            [&](int64_t col) {
+                for (; col < P; ++col)
+                    out[col] = fold_column_f16<SCORED, false, true>(TableRows<gu16>{xi, col}, N, a, s, nullptr, divisor);
+            });
 }
 
 // float16 list-of-rows form, rows at any 2-B offset: one column per lane, 8
@@ -2025,20 +1887,19 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f16_rows_scalar(
     const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= P) return;
-    _Float16 acc = term_h1<SCORED>(h_bits(((const gu16*)xi[0])[c]), factor_h(a, 0),
-                                   SCORED ? factor_h(s, 0) : (_Float16)1);
+    const TableRows<gu16> src{xi, c};
+    _Float16 acc = term_h1<SCORED>(h_bits(*src.row(0)), factor_h(a, 0), SCORED ? factor_h(s, 0) : (_Float16)1);
     int64_t i = 1;
     for (; i + 8 <= N; i += 8) {
         uint16_t v[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load((const gu16*)xi[i + u] + c);
+        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load(src.row(i + u));
 #pragma unroll
         for (int u = 0; u < 8; ++u)
             acc = acc + term_h1<SCORED>(h_bits(v[u]), factor_h(a, i + u), SCORED ? factor_h(s, i + u) : (_Float16)1);
     }
     for (; i < N; ++i)
-        acc = acc + term_h1<SCORED>(h_bits(((const gu16*)xi[i])[c]), factor_h(a, i),
-                                    SCORED ? factor_h(s, i) : (_Float16)1);
+        acc = acc + term_h1<SCORED>(h_bits(*src.row(i)), factor_h(a, i), SCORED ? factor_h(s, i) : (_Float16)1);
     out[c] = bits_h(div_h1(acc, divisor));
 }
 
@@ -2350,12 +2211,7 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_bf16_scalar(
     float* __restrict__ out, uint16_t* __restrict__ outb) {
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= P) return;
-    float acc = term1<SCORED>(bf2f(X[c]), a[0], SCORED ? s[0] : 1.0f);
-    for (int64_t i = 1; i < N; ++i)
-        acc = acc + term1<SCORED>(bf2f(X[i * ldx + c]), a[i], SCORED ? s[i] : 1.0f);
-    acc = acc / divisor;
-    if (out) out[c] = acc;
-    if (outb) outb[c] = f2bf_rne(acc);
+    st_column_bf16(fold_column_bf16<SCORED>(PitchedRows<uint16_t>{X + c, ldx}, N, a, s, divisor), out, outb, c);
 }
 
 // ---------------------------------------------------------------------------
@@ -2829,32 +2685,62 @@ int launch_lds_flags(hipStream_t st, bool sc, bool acc, bool fin, const float* X
     return FA_OK;
 }
 
-// bf16 grid-stride launch (per_cu < 0: balanced passes) and its column-band form
-template <int U, int C>
-void launch_bf16_gs(hipStream_t st, int per_cu, const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
-                    const float* a, const float* s, float d, float* out, uint16_t* outb) {
-    const int64_t per_block = (int64_t)kBlock * C, units = (P >> 3) + ((P & 7) ? 1 : 0);
-    const int64_t tiles = (units + per_block - 1) / per_block;
-    int64_t g = (int64_t)(per_cu > 0 ? per_cu : -per_cu) * cu_count();
-    if (g > tiles) g = tiles;
-    if (per_cu < 0) {
-        const int64_t passes = (tiles + g - 1) / g;
-        g = (tiles + passes - 1) / passes;
+// ---- launches of the stacked 16-bit octet kernels ------------------------
+// What differs between the bf16 and the float16 launch of a form: the kernels
+// and the arguments behind ldx.  at(c0) = the same fold from column c0 on.
+struct Bf16Fold {
+    const float *a, *s;
+    float d;
+    float* out;
+    uint16_t* outb;
+    Bf16Fold at(int64_t c0) const { return {a, s, d, out ? out + c0 : nullptr, outb ? outb + c0 : nullptr}; }
+    template <int U, int C, bool SC>
+    void v8(hipStream_t st, int64_t grid, const uint16_t* X, int64_t N, int64_t P, int64_t ldx) const {
+        hipLaunchKernelGGL((k_fedavg_bf16_v8<U, C, SC>), dim3((unsigned)grid), dim3(kBlock), 0, st, X, N, P, ldx, a, s,
+                           d, out, outb);
     }
-    if (s)
-        hipLaunchKernelGGL((k_fedavg_bf16_gs<U, C, true>), dim3((unsigned)g), dim3(kBlock), 0, st, X, N, P, ldx, a,
-                           s, d, out, outb, tiles);
-    else
-        hipLaunchKernelGGL((k_fedavg_bf16_gs<U, C, false>), dim3((unsigned)g), dim3(kBlock), 0, st, X, N, P, ldx,
-                           a, s, d, out, outb, tiles);
-}
+    template <int U, int C, bool SC>
+    void gs(hipStream_t st, OctetGrid g, const uint16_t* X, int64_t N, int64_t P, int64_t ldx) const {
+        hipLaunchKernelGGL((k_fedavg_bf16_gs<U, C, SC>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, X, N, P, ldx, a,
+                           s, d, out, outb, g.tiles);
+    }
+};
+struct F16Fold {
+    const uint16_t *a, *s;
+    float d;
+    uint16_t* out;
+    F16Fold at(int64_t c0) const { return {a, s, d, out + c0}; }
+    template <int U, int C, bool SC>
+    void v8(hipStream_t st, int64_t grid, const uint16_t* X, int64_t N, int64_t P, int64_t ldx) const {
+        hipLaunchKernelGGL((k_fedavg_f16_v8<U, C, SC>), dim3((unsigned)grid), dim3(kBlock), 0, st, X, N, P, ldx, a, s,
+                           d, out);
+    }
+    template <int U, int C, bool SC>
+    void gs(hipStream_t st, OctetGrid g, const uint16_t* X, int64_t N, int64_t P, int64_t ldx) const {
+        hipLaunchKernelGGL((k_fedavg_f16_gs<U, C, SC>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, X, N, P, ldx, a,
+                           s, d, out, g.tiles);
+    }
+};
 
-template <int U, int C>
-void launch_bf16_bands(hipStream_t st, int passes, const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
-                       const float* a, const float* s, float d, float* out, uint16_t* outb) {
+// one block per tile
+template <int U, int C, class Fold>
+void launch_octet_v8(const Fold& f, hipStream_t st, const uint16_t* X, int64_t N, int64_t P, int64_t ldx) {
+    const int64_t grid = octet_grid(P, C, 0, cu_count()).grid;
+    if (f.s) f.template v8<U, C, true>(st, grid, X, N, P, ldx);
+    else f.template v8<U, C, false>(st, grid, X, N, P, ldx);
+}
+// grid-stride (per_cu < 0: balanced passes) and its column-band form
+template <int U, int C, class Fold>
+void launch_octet_gs(const Fold& f, hipStream_t st, int per_cu, const uint16_t* X, int64_t N, int64_t P, int64_t ldx) {
+    const OctetGrid g = octet_grid(P, C, per_cu, cu_count());
+    if (f.s) f.template gs<U, C, true>(st, g, X, N, P, ldx);
+    else f.template gs<U, C, false>(st, g, X, N, P, ldx);
+}
+template <int U, int C, class Fold>
+void launch_octet_bands(const Fold& f, hipStream_t st, int passes, const uint16_t* X, int64_t N, int64_t P,
+                        int64_t ldx) {
     const int64_t to = (int64_t)kBlock * C;  // octets per tile
-    const int64_t units = (P >> 3) + ((P & 7) ? 1 : 0);
-    const int64_t tiles = (units + to - 1) / to;
+    const int64_t tiles = octet_grid(P, C, 0, cu_count()).tiles;
     const int64_t per_band = (int64_t)passes * cu_count();
     const int64_t nb = (tiles + per_band - 1) / per_band;
     const int64_t band_tiles = (tiles + nb - 1) / nb;
@@ -2862,44 +2748,7 @@ void launch_bf16_bands(hipStream_t st, int passes, const uint16_t* X, int64_t N,
         const int64_t c0 = b * band_tiles * to * 8;
         if (c0 >= P) break;
         const int64_t pb = (P - c0) < band_tiles * to * 8 ? (P - c0) : band_tiles * to * 8;
-        launch_bf16_gs<U, C>(st, -1, X + c0, N, pb, ldx, a, s, d, out ? out + c0 : nullptr, outb ? outb + c0 : nullptr);
-    }
-}
-
-// float16 grid-stride launch and its column-band form (as the bf16 pair above)
-template <int U, int C>
-void launch_f16_gs(hipStream_t st, int per_cu, const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
-                   const uint16_t* a, const uint16_t* s, float d, uint16_t* out) {
-    const int64_t per_block = (int64_t)kBlock * C, units = (P >> 3) + ((P & 7) ? 1 : 0);
-    const int64_t tiles = (units + per_block - 1) / per_block;
-    int64_t g = (int64_t)(per_cu > 0 ? per_cu : -per_cu) * cu_count();
-    if (g > tiles) g = tiles;
-    if (per_cu < 0) {
-        const int64_t passes = (tiles + g - 1) / g;
-        g = (tiles + passes - 1) / passes;
-    }
-    if (s)
-        hipLaunchKernelGGL((k_fedavg_f16_gs<U, C, true>), dim3((unsigned)g), dim3(kBlock), 0, st, X, N, P, ldx, a, s,
-                           d, out, tiles);
-    else
-        hipLaunchKernelGGL((k_fedavg_f16_gs<U, C, false>), dim3((unsigned)g), dim3(kBlock), 0, st, X, N, P, ldx, a,
-                           s, d, out, tiles);
-}
-
-template <int U, int C>
-void launch_f16_bands(hipStream_t st, int passes, const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
-                      const uint16_t* a, const uint16_t* s, float d, uint16_t* out) {
-    const int64_t to = (int64_t)kBlock * C;  // octets per tile
-    const int64_t units = (P >> 3) + ((P & 7) ? 1 : 0);
-    const int64_t tiles = (units + to - 1) / to;
-    const int64_t per_band = (int64_t)passes * cu_count();
-    const int64_t nb = (tiles + per_band - 1) / per_band;
-    const int64_t band_tiles = (tiles + nb - 1) / nb;
-    for (int64_t b = 0; b < nb; ++b) {
-        const int64_t c0 = b * band_tiles * to * 8;
-        if (c0 >= P) break;
-        const int64_t pb = (P - c0) < band_tiles * to * 8 ? (P - c0) : band_tiles * to * 8;
-        launch_f16_gs<U, C>(st, -1, X + c0, N, pb, ldx, a, s, d, out + c0);
+        launch_octet_gs<U, C>(f.at(c0), st, -1, X + c0, N, pb, ldx);
     }
 }
 
@@ -3603,35 +3452,23 @@ inline void bf16_candidates(int64_t N, int64_t P, int policy, std::vector<int>& 
             add(f);
 }
 
-inline void launch_bf16_form(Bf16Form f, hipStream_t st, const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
-                             const float* a, const float* s, float divisor, float* out_f32, uint16_t* out_bf16) {
-#define FA_BF(U, C)                                                                                         \
-    {                                                                                                       \
-        const int64_t per_block = (int64_t)kBlock * (C), units = (P >> 3) + ((P & 7) ? 1 : 0);            \
-        const dim3 grid((unsigned)((units + per_block - 1) / per_block));                                   \
-        if (s)                                                                                              \
-            hipLaunchKernelGGL((k_fedavg_bf16_v8<U, C, true>), grid, dim3(kBlock), 0, st, X, N, P, ldx, a, s, \
-                               divisor, out_f32, out_bf16);                                                 \
-        else                                                                                                \
-            hipLaunchKernelGGL((k_fedavg_bf16_v8<U, C, false>), grid, dim3(kBlock), 0, st, X, N, P, ldx, a,  \
-                               s, divisor, out_f32, out_bf16);                                              \
+// One form of the stacked 16-bit fold, bf16 (Bf16Fold) or float16 (F16Fold)
+template <class Fold>
+void launch_octet_form(Bf16Form form, const Fold& f, hipStream_t st, const uint16_t* X, int64_t N, int64_t P,
+                       int64_t ldx) {
+    switch (form) {
+        case Bf16Form::kV8U2C8: launch_octet_v8<2, 8>(f, st, X, N, P, ldx); break;
+        case Bf16Form::kV8U4C4: launch_octet_v8<4, 4>(f, st, X, N, P, ldx); break;
+        case Bf16Form::kV8U8C2: launch_octet_v8<8, 2>(f, st, X, N, P, ldx); break;
+        case Bf16Form::kV8U8C1: launch_octet_v8<8, 1>(f, st, X, N, P, ldx); break;
+        case Bf16Form::kBandsU8C4: launch_octet_bands<8, 4>(f, st, 4, X, N, P, ldx); break;
+        case Bf16Form::kBandsU8C2: launch_octet_bands<8, 2>(f, st, 4, X, N, P, ldx); break;
+        case Bf16Form::kBandsU2C8: launch_octet_bands<2, 8>(f, st, 2, X, N, P, ldx); break;
+        case Bf16Form::kBandsU4C4: launch_octet_bands<4, 4>(f, st, 4, X, N, P, ldx); break;
+        case Bf16Form::kBandsU16C2: launch_octet_bands<16, 2>(f, st, 4, X, N, P, ldx); break;
+        case Bf16Form::kGsBalU8C2: launch_octet_gs<8, 2>(f, st, -1, X, N, P, ldx); break;
+        case Bf16Form::kGs1U8C4: launch_octet_gs<8, 4>(f, st, 1, X, N, P, ldx); break;
     }
-    switch (f) {
-        case Bf16Form::kV8U2C8: FA_BF(2, 8); break;
-        case Bf16Form::kV8U4C4: FA_BF(4, 4); break;
-        case Bf16Form::kV8U8C2: FA_BF(8, 2); break;
-        case Bf16Form::kV8U8C1: FA_BF(8, 1); break;
-        case Bf16Form::kBandsU8C4: launch_bf16_bands<8, 4>(st, 4, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case Bf16Form::kBandsU8C2: launch_bf16_bands<8, 2>(st, 4, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case Bf16Form::kBandsU2C8: launch_bf16_bands<2, 8>(st, 2, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case Bf16Form::kBandsU4C4: launch_bf16_bands<4, 4>(st, 4, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case Bf16Form::kBandsU16C2:
-            launch_bf16_bands<16, 2>(st, 4, X, N, P, ldx, a, s, divisor, out_f32, out_bf16);
-            break;
-        case Bf16Form::kGsBalU8C2: launch_bf16_gs<8, 2>(st, -1, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-        case Bf16Form::kGs1U8C4: launch_bf16_gs<8, 4>(st, 1, X, N, P, ldx, a, s, divisor, out_f32, out_bf16); break;
-    }
-#undef FA_BF
 }
 
 // The product bf16 fold (exact upcast, fp32 fold in order, optional RNE bf16 copy).
@@ -3653,16 +3490,17 @@ inline int bf16_auto(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const
         return check_launch("k_fedavg_bf16_scalar");
     }
     const Bf16Form policy = pick_bf16(N, P);
+    const Bf16Fold f{a, s, divisor, out_f32, out_bf16};
     const size_t xbytes = ((size_t)(N - 1) * ldx + P) * 2;
     if ((out_f32 && overlaps(out_f32, (size_t)P * 4, X, xbytes)) ||
         (out_bf16 && overlaps(out_bf16, (size_t)P * 2, X, xbytes))) {
-        launch_bf16_form(policy, st, X, N, P, ldx, a, s, divisor, out_f32, out_bf16);  // in place: one launch
+        launch_octet_form(policy, f, st, X, N, P, ldx);  // in place: one launch
         return check_launch("fedavg_bf16");
     }
     g_tuner.run(kTuneBf16, N, P, ldx, s != nullptr, (int)policy, (double)N * (double)P * 2.0, st,
                 [&](std::vector<int>& c) { bf16_candidates(N, P, (int)policy, c); },
                 [&](int form) {
-                    launch_bf16_form((Bf16Form)form, st, X, N, P, ldx, a, s, divisor, out_f32, out_bf16);
+                    launch_octet_form((Bf16Form)form, f, st, X, N, P, ldx);
                     return FA_OK;
                 });
     return check_launch("fedavg_bf16");
@@ -3696,35 +3534,6 @@ inline float half_bits_to_float(uint16_t h) {
 // their own kind.
 inline Bf16Form pick_f16(int64_t N, int64_t P) { return pick_bf16(N, P); }
 
-inline void launch_f16_form(Bf16Form f, hipStream_t st, const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
-                            const uint16_t* a, const uint16_t* s, float divisor, uint16_t* out) {
-#define FA_HF(U, C)                                                                                         \
-    {                                                                                                       \
-        const int64_t per_block = (int64_t)kBlock * (C), units = (P >> 3) + ((P & 7) ? 1 : 0);            \
-        const dim3 grid((unsigned)((units + per_block - 1) / per_block));                                   \
-        if (s)                                                                                              \
-            hipLaunchKernelGGL((k_fedavg_f16_v8<U, C, true>), grid, dim3(kBlock), 0, st, X, N, P, ldx, a, s, \
-                               divisor, out);                                                               \
-        else                                                                                                \
-            hipLaunchKernelGGL((k_fedavg_f16_v8<U, C, false>), grid, dim3(kBlock), 0, st, X, N, P, ldx, a,  \
-                               s, divisor, out);                                                            \
-    }
-    switch (f) {
-        case Bf16Form::kV8U2C8: FA_HF(2, 8); break;
-        case Bf16Form::kV8U4C4: FA_HF(4, 4); break;
-        case Bf16Form::kV8U8C2: FA_HF(8, 2); break;
-        case Bf16Form::kV8U8C1: FA_HF(8, 1); break;
-        case Bf16Form::kBandsU8C4: launch_f16_bands<8, 4>(st, 4, X, N, P, ldx, a, s, divisor, out); break;
-        case Bf16Form::kBandsU8C2: launch_f16_bands<8, 2>(st, 4, X, N, P, ldx, a, s, divisor, out); break;
-        case Bf16Form::kBandsU2C8: launch_f16_bands<2, 8>(st, 2, X, N, P, ldx, a, s, divisor, out); break;
-        case Bf16Form::kBandsU4C4: launch_f16_bands<4, 4>(st, 4, X, N, P, ldx, a, s, divisor, out); break;
-        case Bf16Form::kBandsU16C2: launch_f16_bands<16, 2>(st, 4, X, N, P, ldx, a, s, divisor, out); break;
-        case Bf16Form::kGsBalU8C2: launch_f16_gs<8, 2>(st, -1, X, N, P, ldx, a, s, divisor, out); break;
-        case Bf16Form::kGs1U8C4: launch_f16_gs<8, 4>(st, 1, X, N, P, ldx, a, s, divisor, out); break;
-    }
-#undef FA_HF
-}
-
 // The product float16 fold (binary16 products, sums and quotient, in row order).
 inline int f16_auto(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
                     uint16_t divisor, uint16_t* out, void* stream) {
@@ -3742,14 +3551,15 @@ inline int f16_auto(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const 
         return check_launch("k_fedavg_f16_scalar");
     }
     const Bf16Form policy = pick_f16(N, P);
+    const F16Fold f{a, s, d, out};
     if (overlaps(out, (size_t)P * 2, X, ((size_t)(N - 1) * ldx + P) * 2)) {
-        launch_f16_form(policy, st, X, N, P, ldx, a, s, d, out);  // in place: one launch
+        launch_octet_form(policy, f, st, X, N, P, ldx);  // in place: one launch
         return check_launch("fedavg_f16");
     }
     g_tuner.run(kTuneF16, N, P, ldx, s != nullptr, (int)policy, (double)N * (double)P * 2.0, st,
                 [&](std::vector<int>& c) { bf16_candidates(N, P, (int)policy, c); },
                 [&](int form) {
-                    launch_f16_form((Bf16Form)form, st, X, N, P, ldx, a, s, d, out);
+                    launch_octet_form((Bf16Form)form, f, st, X, N, P, ldx);
                     return FA_OK;
                 });
     return check_launch("fedavg_f16");
@@ -3774,16 +3584,9 @@ void launch_fold_f16(hipStream_t st, bool vec, const uint16_t* X, int64_t N, int
                            acc_in, d, out);
         return;
     }
-    // tiles incl. the column-tail lane's; the fewest blocks (at most one per
-    // CU) that finish in the same number of passes
-    const int64_t per_block = (int64_t)kBlock * kFoldF16C, units = (P >> 3) + ((P & 7) ? 1 : 0);
-    const int64_t tiles = (units + per_block - 1) / per_block;
-    int64_t g = cu_count();
-    if (g > tiles) g = tiles;
-    const int64_t passes = (tiles + g - 1) / g;
-    g = (tiles + passes - 1) / passes;
-    hipLaunchKernelGGL((k_fold_f16_gs<kFoldF16U, kFoldF16C, SC, ACC, FIN>), dim3((unsigned)g), dim3(kBlock), 0, st,
-                       X, N, P, ldx, a, s, acc_in, d, out, tiles);
+    const OctetGrid g = octet_grid(P, kFoldF16C, -1, cu_count());  // at most one block per CU, balanced passes
+    hipLaunchKernelGGL((k_fold_f16_gs<kFoldF16U, kFoldF16C, SC, ACC, FIN>), dim3((unsigned)g.grid), dim3(kBlock), 0,
+                       st, X, N, P, ldx, a, s, acc_in, d, out, g.tiles);
 }
 
 inline int f16_fold(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
@@ -3824,7 +3627,7 @@ inline int f16_fold(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const 
 
 // ---- the 16-bit row-table folds (fa_fedavg_bf16_ptrs, fa_fedavg_f16_ptrs) ----
 // Row bases come from a device table.  Every-row-aligned tables take the octet
-// tiling, grid-stride with balanced passes (as launch_bf16_gs(-1)); anything
+// tiling, grid-stride with balanced passes (as launch_octet_gs(-1)); anything
 // else one column per lane.  The shape policy is fixed, not measured: octets
 // per lane from pick_octets, rows ahead as the stacked policy pairs them.
 enum class Rows16Form { kGsU2C8, kGsU8C4, kGsU8C2, kGsU8C1, kColumn };
@@ -3849,43 +3652,29 @@ inline Rows16Form pick_rows16(int64_t N, int64_t P) {
     }
 }
 
-// tiles of C octets per lane (the column-tail lane's tile included) and the
-// balanced grid over them: at most one block per CU, the fewest blocks that
-// finish in the same number of passes
-template <int C>
-inline void rows16_grid(int64_t P, int64_t& tiles, int64_t& g) {
-    const int64_t per_block = (int64_t)kBlock * C, units = (P >> 3) + ((P & 7) ? 1 : 0);
-    tiles = (units + per_block - 1) / per_block;
-    g = cu_count();
-    if (g > tiles) g = tiles;
-    const int64_t passes = (tiles + g - 1) / g;
-    g = (tiles + passes - 1) / passes;
-}
-
+// at most one block per CU, balanced passes
 template <int U, int C>
 void launch_bf16_rows_gs(hipStream_t st, const uint16_t* const* xi, int64_t N, int64_t P, const float* a,
                          const float* s, float d, float* out, uint16_t* outb) {
-    int64_t tiles, g;
-    rows16_grid<C>(P, tiles, g);
+    const OctetGrid g = octet_grid(P, C, -1, cu_count());
     if (s)
-        hipLaunchKernelGGL((k_fedavg_bf16_rows_gs<U, C, true>), dim3((unsigned)g), dim3(kBlock), 0, st, xi, N, P, a, s,
-                           d, out, outb, tiles);
+        hipLaunchKernelGGL((k_fedavg_bf16_rows_gs<U, C, true>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, xi, N, P,
+                           a, s, d, out, outb, g.tiles);
     else
-        hipLaunchKernelGGL((k_fedavg_bf16_rows_gs<U, C, false>), dim3((unsigned)g), dim3(kBlock), 0, st, xi, N, P, a,
-                           s, d, out, outb, tiles);
+        hipLaunchKernelGGL((k_fedavg_bf16_rows_gs<U, C, false>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, xi, N, P,
+                           a, s, d, out, outb, g.tiles);
 }
 
 template <int U, int C>
 void launch_f16_rows_gs(hipStream_t st, const uint16_t* const* xi, int64_t N, int64_t P, const uint16_t* a,
                         const uint16_t* s, float d, uint16_t* out) {
-    int64_t tiles, g;
-    rows16_grid<C>(P, tiles, g);
+    const OctetGrid g = octet_grid(P, C, -1, cu_count());
     if (s)
-        hipLaunchKernelGGL((k_fedavg_f16_rows_gs<U, C, true>), dim3((unsigned)g), dim3(kBlock), 0, st, xi, N, P, a, s,
-                           d, out, tiles);
+        hipLaunchKernelGGL((k_fedavg_f16_rows_gs<U, C, true>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, xi, N, P,
+                           a, s, d, out, g.tiles);
     else
-        hipLaunchKernelGGL((k_fedavg_f16_rows_gs<U, C, false>), dim3((unsigned)g), dim3(kBlock), 0, st, xi, N, P, a,
-                           s, d, out, tiles);
+        hipLaunchKernelGGL((k_fedavg_f16_rows_gs<U, C, false>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, xi, N, P,
+                           a, s, d, out, g.tiles);
 }
 
 // form < 0: the policy (rows_aligned picks the octet tiling or the column

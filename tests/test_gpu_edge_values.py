@@ -463,13 +463,24 @@ def test_bf16_every_row_table_form(dev, libs, N, P):
 # ---------------------------------------------------------------------------
 # the one-launch step (write-through tile stores), agent scope, one process
 # ---------------------------------------------------------------------------
+# Three rounds that each hold a full tile of a step form and a last tile with
+# exactly one octet: 8192 + 8 columns (4 octets per lane), 4096 + 8 (2 octets
+# per lane), and 8192 + 8 + 3 (the same with a 3-column tail).
+P_STEP_TILES = 8200 + 4104 + 8203
+
+
 def _round_offsets(P):
     """Three small rounds, every start a multiple of 8, the last one ragged."""
+    if P == P_STEP_TILES:
+        return [0, 8200, 8200 + 4104, P]
     q = P // 4 // 8 * 8
     return [0, q, 3 * q, P] if q else [0, P]
 
 
-@pytest.mark.parametrize("N,P", [(9, 1027), (33, 4099), (70, 4099)])
+# N = 1, 2 and 10 at P_STEP_TILES: the first row alone, no full row group, and
+# one group of the step forms' 8 rows ahead with a leftover row
+@pytest.mark.parametrize("N,P", [(9, 1027), (33, 4099), (70, 4099), (1, P_STEP_TILES), (2, P_STEP_TILES),
+                                 (10, P_STEP_TILES)])
 @pytest.mark.parametrize("bf16", [False, True])
 def test_one_launch_step_every_form(dev, libs, N, P, bf16):
     """Every step form (fa_fedavg_rounds_form) and the product's

@@ -198,6 +198,34 @@ def test_every_form_matches_numpy(dev, N):
         assert same_bits16(got, exp[scored]), ("pitch P + 8", N, scored, _describe(got, exp[scored]))
 
 
+def test_every_form_at_its_smallest_three_piece_shape(dev):
+    """Every form of fa_fedavg_f16_form at the smallest P with all three column
+    pieces of its tiling: one full tile of 256 * C octets, a last tile with
+    exactly one octet, and a 3-column tail.  N = 1 (the first row alone), 2 (no
+    full row group) and U + 2 (one group of U rows and a leftover row)."""
+    import re
+    from fedlesscan_amd import _lib
+    B = _lib.load_bench()
+    exp = {}
+    for form in range(B.fa_num_f16_forms()):
+        name = B.fa_f16_form_name(form).decode()
+        U, C = map(int, re.search(r"u(\d+)c(\d+)$", name).groups())
+        P = 256 * C * 8 + 8 + 3
+        for N in (1, 2, U + 2):
+            X = _rows(7 * N + C, N, P)
+            w, sc = _weights(N, N), _scores(N, N)
+            Xp = np.zeros((N, (P + 7) // 8 * 8), F16)
+            Xp[:, :P] = X
+            Xd = _dev_bits(Xp, dev)
+            for scored in (False, True):
+                if (N, P, scored) not in exp:
+                    exp[N, P, scored] = _oracle(X, w, sc if scored else None)
+                    _meaningful(exp[N, P, scored])
+                a, s, d = _factors(w, sc if scored else None)
+                got = _raw(dev, Xd, P, a, s, d, form)
+                assert same_bits16(got, exp[N, P, scored]), (name, N, P, scored, _describe(got, exp[N, P, scored]))
+
+
 # ---------------------------------------------------------------------------
 # 3. the column kernel: odd pitch, X off 16-B alignment, out off 16-B alignment
 # ---------------------------------------------------------------------------

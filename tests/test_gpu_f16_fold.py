@@ -23,8 +23,9 @@ SENTINEL = 0x5A5A  # an element the kernel never writes keeps this pattern
 # the policy folds 2 octets per lane (256 lanes): a full tile is 4096 columns;
 # 4899 = one full tile, a partial tile of 100 octets, a 3-column tail
 P_TILES = 2 * 256 * 8 + 100 * 8 + 3
-PS = [1, 7, 8, 9, 2048, 2059, P_TILES]
-NS = [1, 2, 9, 33]
+# 4107 = one full tile, a last tile with exactly one octet, a 3-column tail
+PS = [1, 7, 8, 9, 2048, 2059, 2 * 256 * 8 + 8 + 3, P_TILES]
+NS = [1, 2, 6, 9, 33]  # 6: the first row, one group of the 4 rows ahead, a leftover row
 
 
 @pytest.fixture(scope="module")

@@ -531,6 +531,38 @@ def test_bf16_variants_bit_identical(dev, lib):
         assert np.array_equal(ob.cpu().numpy().view(np.uint16), expb), v
 
 
+def test_bf16_forms_at_their_smallest_three_piece_shape(dev, lib):
+    """Every form of fa_fedavg_bf16_form at the smallest P with all three column
+    pieces of its tiling: one full tile of 256 * C octets, a last tile with
+    exactly one octet, and a 3-column tail.  N = 1 (the first row alone), 2 (no
+    full row group) and U + 2 (one group of U rows and a leftover row)."""
+    import re
+    B = lib.load_bench()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    for form in range(B.fa_num_bf16_forms()):
+        name = B.fa_bf16_form_name(form).decode()
+        U, C = map(int, re.search(r"u(\d+)c(\d+)$", name).groups())
+        P = 256 * C * 8 + 8 + 3
+        ldx = P + 5  # rows of whole octets
+        for N in (1, 2, U + 2):
+            Xb = np.zeros((N, ldx), np.uint16)
+            Xb[:, :P] = synth.clients_bf16(80 + N + C, N, 0, P)
+            w = synth.cardinalities(80 + N, N)
+            sc = np.array([(r + 1) / 11 for r in synth.round_ids(80, N, 10, 2)], np.float32)
+            Xd = torch.from_numpy(Xb.view(np.int16)).to(dev)
+            a = torch.tensor(w, dtype=torch.float32, device=dev)
+            for s in (None, sc):
+                exp, expb = OL.fedavg_bf16(np.ascontiguousarray(Xb[:, :P]), np.array(w, np.float32),
+                                           np.float32(sum(w)), s=s)
+                sd = None if s is None else torch.from_numpy(s).to(dev)
+                o = _sentinel(P, dev)
+                ob = torch.full((P,), -1, dtype=torch.int16, device=dev)
+                _bcheck(B.fa_fedavg_bf16_form(Xd.data_ptr(), N, P, ldx, a.data_ptr(), None if sd is None else sd.data_ptr(),
+                                               float(np.float32(sum(w))), o.data_ptr(), ob.data_ptr(), st, form), name)
+                assert _bits_equal(o.cpu().numpy(), exp), (name, N, s is not None)
+                assert np.array_equal(ob.cpu().numpy().view(np.uint16), expb), (name, N, s is not None)
+
+
 def test_f64_and_int_paths(dev):
     from fedlesscan_amd import engine
     X = np.stack([p[0] for p in G.parameters("f64_n40")])

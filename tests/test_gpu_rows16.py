@@ -26,7 +26,9 @@ torch = pytest.importorskip("torch")
 F16 = np.float16
 SENT16, SENT32 = 0x5A5A, 0x5A5A5A5A  # an element no kernel writes keeps this pattern
 PAD = 8  # sentinel elements behind every output
-NS = [1, 2, 9, 17, 18, 33]  # one row; no full group; group + remainder for 2, 8 and 16 rows ahead; the first row apart
+# one row; no full group; group + remainder for 2, 8 and 16 rows ahead; the first row apart;
+# 4 and 10: the first row, exactly one group of 2 / 8 rows ahead, one leftover row
+NS = [1, 2, 4, 9, 10, 17, 18, 33]
 
 
 @pytest.fixture(scope="module")
@@ -216,7 +218,8 @@ def _forms():
 
 
 def _edge_sizes(T):
-    return [1, 7, 8, 9, T - 1, T, T + 13]
+    # T + 11: a full tile, a last tile with exactly one octet, a 3-column tail
+    return [1, 7, 8, 9, T - 1, T, T + 11, T + 13]
 
 
 # ---------------------------------------------------------------------------
@@ -226,7 +229,7 @@ def _edge_sizes(T):
 @pytest.mark.parametrize("kind", ["bf16", "f16"])
 def test_every_form_at_its_tile_edges(dev, kind, N):
     """Each (rows ahead, octets per lane) form and the column form through the
-    bench-library entry, at P = 1, 7, 8, 9, T - 1, T, T + 13 for the form's
+    bench-library entry, at P = 1, 7, 8, 9, T - 1, T, T + 11, T + 13 for the form's
     tile of T columns, FedAvg and scored; bf16 with out_f32 only, out_bf16 only
     and both.  The policy (-1) runs the same sizes with the rows promised
     aligned and not.  The rows are uploaded once at the largest P; a smaller P

@@ -1,7 +1,8 @@
 """Host-only stress programs of the native pieces, built here with g++ against
 simulated HIP runtimes (no GPU): the tuner's state machine (tools/tuner_stress.cpp,
-fedlesscan_amd/csrc/tuner.hpp) and the native ingest pipe
-(tools/ingest_pipe_stress.cpp, csrc/ingest_pipe.cpp).  The sanitizer builds
+fedlesscan_amd/csrc/tuner.hpp), the native ingest pipe
+(tools/ingest_pipe_stress.cpp, csrc/ingest_pipe.cpp) and the octet kernels'
+launch grid (tools/octet_grid_check.cpp, csrc/octet_grid.hpp).  The sanitizer builds
 are tools/tuner_stress.sh and tools/ingest_pipe_stress.sh."""
 import os
 import shutil
@@ -28,6 +29,11 @@ def test_tuner_state_machine(tmp_path):
     out = _build_and_run(tmp_path, "tuner_stress", ["tools/tuner_stress.cpp"],
                          ["tools/tunersim", "fedlesscan_amd/csrc"])
     assert "tuner_stress: ok" in out
+
+
+def test_octet_grid_equals_the_arithmetic_it_replaced(tmp_path):
+    out = _build_and_run(tmp_path, "octet_grid_check", ["tools/octet_grid_check.cpp"], ["fedlesscan_amd/csrc"])
+    assert "octet_grid_check: ok" in out
 
 
 def test_ingest_pipe_host_stress(tmp_path):
