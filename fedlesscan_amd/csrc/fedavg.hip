@@ -315,6 +315,17 @@ int fa_fedavg_f32_rounds(fa_rounds* r, const float* X, int64_t N, int64_t ldx, c
 
 const char* fa_rounds_form(int bf16) { return step_form_name(pick_step(bf16 != 0)); }
 
+int fa_fedavg_f16_rounds(fa_rounds* r, const uint16_t* X, int64_t N, int64_t ldx, const uint16_t* a,
+                         const uint16_t* s, uint16_t divisor, uint16_t* out, int rounds, const int64_t* offsets,
+                         const int64_t* out_offsets, void* stream) {
+    if (!r) return fail(FA_ERR_ARG, "null fa_rounds");
+    StreamDevice on_stream_device(stream);
+    return launch_step_f16(*r, pick_step_f16(), (hipStream_t)stream, X, N, ldx, a, s, divisor, out, rounds, offsets,
+                           out_offsets);
+}
+
+const char* fa_rounds_form_f16(void) { return step_form_name_f16(pick_step_f16()); }
+
 int fa_rounds_wait(fa_rounds* r, int round, void* stream) {
     if (!r) return fail(FA_ERR_ARG, "null fa_rounds");
     StreamDevice on_stream_device(stream);

@@ -558,6 +558,17 @@ int fa_fedavg_rounds_form(void* r, int form, const void* X, int64_t N, int64_t l
                        kStepSpecs[form].bf16 ? out_bf16 : nullptr, rounds, offsets);
 }
 
+int fa_num_step_forms_f16(void) { return kNumStepFormsF16; }
+const char* fa_step_form_name_f16(int form) { return step_form_name_f16(form); }
+int fa_fedavg_f16_rounds_form(void* r, int form, const uint16_t* X, int64_t N, int64_t ldx, const uint16_t* a,
+                              const uint16_t* s, uint16_t divisor, uint16_t* out, int rounds, const int64_t* offsets,
+                              const int64_t* out_offsets, void* stream) {
+    if (!r) return fail(FA_ERR_ARG, "null rounds state");
+    StreamDevice on_stream_device(stream);
+    return launch_step_f16(*static_cast<RoundsState*>(r), form, (hipStream_t)stream, X, N, ldx, a, s, divisor, out,
+                           rounds, offsets, out_offsets);
+}
+
 int fa_bench_rounds_wait(void* r, int round, void* stream) {
     RoundsState* o = static_cast<RoundsState*>(r);
     if (!o) return fail(FA_ERR_ARG, "null rounds state");

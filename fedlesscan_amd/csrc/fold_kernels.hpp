@@ -1734,11 +1734,15 @@ __device__ __forceinline__ uint16_t fold_column_f16(Rows src, int64_t N, const u
 }
 
 // The float16 octet fold: the lane's C octets of the rows of src, in row
-// order; acc_in and out point at the lane's first octet.
-template <int U, int C, bool SCORED, bool ACC, bool FIN, class Rows>
+// order; acc_in and out point at the lane's first octet.  WT (the one-launch
+// step, final results only): the quotient octets stored write-through over
+// the tile's wave-uniform base, as fold_octets stores outb -- no non-temporal
+// store there (no valid producer form for a round another stream reads).
+template <int U, int C, bool SCORED, bool ACC, bool FIN, int WT = 0, class Rows>
 __device__ __forceinline__ void fold_octets_f16(Rows src, int64_t N, const uint16_t* __restrict__ a,
                                                 const uint16_t* __restrict__ s, const u32x4* acc_in, float divisor,
                                                 u32x4* out) {
+    static_assert(!WT || (!ACC && FIN), "write-through stores are for final results");
     f16x8 acc[C];
     int64_t i = 0;
     if constexpr (ACC) {
@@ -1775,12 +1779,21 @@ __device__ __forceinline__ void fold_octets_f16(Rows src, int64_t N, const uint1
 #pragma unroll
         for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(ld_h8(r + c * kBlock), ai, si);
     }
+    if constexpr (WT) {  // the base: the tile's first octet (out - threadIdx.x, shared by every lane)
+        const __amdgpu_buffer_rsrc_t rs = wt_rsrc(reinterpret_cast<const void*>(
+            (uintptr_t)uniform64((int64_t)(uintptr_t)(out - threadIdx.x))));
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            st16_wt<WT>(rs, (int)(16 * ((int)threadIdx.x + c * kBlock)),
+                        __builtin_bit_cast(u32x4, div_h8(acc[c], divisor)));
+        return;
+    }
 #pragma unroll
     for (int c = 0; c < C; ++c) st_h8<FIN>(out + c * kBlock, acc[c], divisor);
 }
 
 // One octet tile of a stacked float16 matrix (acc_in may alias out)
-template <int U, int C, bool SCORED, bool ACC, bool FIN>
+template <int U, int C, bool SCORED, bool ACC, bool FIN, int WT = 0>
 __device__ __forceinline__ void f16_tile(int64_t bid, const uint16_t* __restrict__ X, int64_t N, int64_t P,
                                          int64_t ldx, const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
                                          const uint16_t* acc_in, float divisor, uint16_t* out) {
@@ -1791,17 +1804,19 @@ __device__ __forceinline__ void f16_tile(int64_t bid, const uint16_t* __restrict
     octet_tile<C>(
         bid, P,
         [&](int64_t o) {
-            fold_octets_f16<U, C, SCORED, ACC, FIN>(PitchedRows<u32x4>{X8 + o, ldo}, N, a, s, ACC ? A8 + o : nullptr,
-                                                    divisor, O8 + o);
+            fold_octets_f16<U, C, SCORED, ACC, FIN, WT>(PitchedRows<u32x4>{X8 + o, ldo}, N, a, s,
+                                                        ACC ? A8 + o : nullptr, divisor, O8 + o);
         },
         [&](int64_t o) {
-            fold_octets_f16<U, 1, SCORED, ACC, FIN>(PitchedRows<u32x4>{X8 + o, ldo}, N, a, s, ACC ? A8 + o : nullptr,
-                                                    divisor, O8 + o);
+            fold_octets_f16<U, 1, SCORED, ACC, FIN, WT>(PitchedRows<u32x4>{X8 + o, ldo}, N, a, s,
+                                                        ACC ? A8 + o : nullptr, divisor, O8 + o);
         },
         [&](int64_t col) {
             for (; col < P; ++col)
                 out[col] = fold_column_f16<SCORED, ACC, FIN>(PitchedRows<uint16_t>{X + col, ldx}, N, a, s,
                                                              ACC ? acc_in + col : nullptr, divisor);
+            // WT: these few plain stores are written back before the block publishes
+            wt_tail_release<WT>();
         });
 }
 
@@ -2169,6 +2184,33 @@ __global__ __launch_bounds__(B) void k_fold_f32_step(
         const int64_t c0 = T.col0[g];
         fold_tile<US, CS, true, SCORED, false, true, true, B, WTM>(bid, X + c0, N, T.width[g], ldx, a, s, nullptr,
                                                                    divisor, out + T.ocol0[g]);
+    };
+    if constexpr (BAL) {
+        step_tiles_bal(T, sig, epoch, wide, narrow);
+    } else {
+        step_tiles(T, sig, epoch, [&](int g, int64_t bid) {
+            if (T.small[g]) narrow(g, bid);
+            else wide(g, bid);
+        });
+    }
+}
+
+// The float16 step: the schedules of k_fedavg_bf16_step over the float16 tile
+// (binary16 products, sums and quotient: the bits of fa_fedavg_f16 on each
+// round's columns), every quotient octet stored write-through.
+template <int UB, int CB, int US, int CS, bool SCORED, int B, bool BAL = false, int WTM = kWtAgent>
+__global__ __launch_bounds__(B) void k_fedavg_f16_step(
+    const uint16_t* __restrict__ X, int64_t N, int64_t ldx, const uint16_t* __restrict__ a,
+    const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out, StepTable T, unsigned int* sig,
+    unsigned int epoch) {
+    static_assert(B == kBlock, "octet tiles are kBlock lanes wide");
+    auto wide = [&](int g, int64_t bid) {
+        f16_tile<UB, CB, SCORED, false, true, WTM>(bid, X + T.col0[g], N, T.width[g], ldx, a, s, nullptr, divisor,
+                                                   out + T.ocol0[g]);
+    };
+    auto narrow = [&](int g, int64_t bid) {
+        f16_tile<US, CS, SCORED, false, true, WTM>(bid, X + T.col0[g], N, T.width[g], ldx, a, s, nullptr, divisor,
+                                                   out + T.ocol0[g]);
     };
     if constexpr (BAL) {
         step_tiles_bal(T, sig, epoch, wide, narrow);
@@ -2764,6 +2806,8 @@ struct StepSpec {
     bool last_only = false;   // the pool never reaches past the last round's columns
     bool round_tail = false;  // each round but the last: whole passes of wide tiles, the rest in narrow static tiles
     bool bal = false;         // balanced rounds: each round's wide tiles over its own balanced block count
+    bool f16 = false;         // float16 rows, factors and result (kStepSpecsF16); bf16 is false there
+    constexpr bool octets() const { return bf16 || f16; }  // 8 columns per 16-byte unit (fp32: 4)
 };
 // The policy's two forms and one comparison form per dtype beside the round-4
 // bf16 policy (the bench library and the GPU tests run every one).  Round 4
@@ -2811,6 +2855,23 @@ inline int pick_step(bool bf16) {
     static_assert(kBf16 >= 0 && kF32 >= 0, "policy step forms");
     return bf16 ? kBf16 : kF32;
 }
+// The float16 step's forms, in a table of their own (fa_num_step_forms and its
+// names stay the bf16 / fp32 ones).  A float16 row has a bf16 row's bytes, so
+// the policy takes the bf16 policy's geometry; agent scope only (no peer
+// exchange for float16):
+//   f16_step_bal_u8c4     the policy: each round's 8 x 4-octet tiles over its
+//     own balanced block count, no dynamic pool
+//   f16_step_static_u8c4  comparison: every tile static
+constexpr StepSpec kStepSpecsF16[] = {
+    {"f16_step_bal_u8c4", false, 8, 4, 8, 2, 0, true, false, true, true},
+    {"f16_step_static_u8c4", false, 8, 4, 8, 4, 0, false, false, false, true},
+};
+constexpr int kNumStepFormsF16 = (int)(sizeof(kStepSpecsF16) / sizeof(kStepSpecsF16[0]));
+inline const char* step_form_name_f16(int f) { return (f >= 0 && f < kNumStepFormsF16) ? kStepSpecsF16[f].name : ""; }
+inline int pick_step_f16() {
+    static_assert(name_eq(kStepSpecsF16[0].name, "f16_step_bal_u8c4"), "policy step form");
+    return 0;
+}
 
 // The per-launch state of fa_fedavg_*_rounds: the signal words in device
 // memory, the waiters' timeout record in mapped host memory and the host
@@ -2846,7 +2907,7 @@ struct RoundsState {
 // from the last round) in narrow tiles.  FA status.
 inline int build_step_table(const StepSpec& sp, int rounds, const int64_t* offsets, const int64_t* out_offsets,
                             int64_t ldx, int64_t grid, StepTable& T) {
-    const int64_t ucols = sp.bf16 ? 8 : 4;  // columns per octet / quad
+    const int64_t ucols = sp.octets() ? 8 : 4;  // columns per octet / quad
     const int64_t wide_cols = (int64_t)kBlock * sp.cb * ucols;
     T = StepTable{};
     T.rounds = rounds;
@@ -2866,7 +2927,7 @@ inline int build_step_table(const StepSpec& sp, int rounds, const int64_t* offse
         split[k] = ((w - pool) / wide_cols) * wide_cols;  // the static part ends on a wide-tile boundary
         pool = 0;
     }
-    auto units = [&](int64_t w) { return sp.bf16 ? (w >> 3) + ((w & 7) ? 1 : 0) : (w >> 2) + ((w & 3) ? 1 : 0); };
+    auto units = [&](int64_t w) { return sp.octets() ? (w >> 3) + ((w & 7) ? 1 : 0) : (w >> 2) + ((w & 3) ? 1 : 0); };
     int64_t total = 0;
     // static segments first (all of them precede every dynamic one in column
     // order: only a suffix of the step is dynamic), then the dynamic ones
@@ -2993,17 +3054,19 @@ inline int rounds_check(RoundsState& o) {
     return n;
 }
 
-// Enqueue one step launch of form f over `rounds` slots at local columns
-// [offsets[k], offsets[k+1]).
-inline int launch_step(RoundsState& R, int f, hipStream_t st, const void* X, int64_t N, int64_t ldx,
-                       const float* a, const float* s, float divisor, float* out, uint16_t* outb, int rounds,
-                       const int64_t* offsets, const int64_t* out_offsets = nullptr) {
+// Enqueue one step launch of form sp over `rounds` slots at local columns
+// [offsets[k], offsets[k+1]): the protocol every dtype shares (the epoch, the
+// start / done events, the gate wait, the capture refusal, the argument
+// checks).  fp32 and bf16 forms take float32 factors and write out (float32)
+// and / or outb; float16 forms (sp.f16) take binary16 factors and write out as
+// halves, the divisor the half's exact float32 value.
+inline int launch_step_spec(RoundsState& R, const StepSpec& sp, hipStream_t st, const void* X, int64_t N,
+                            int64_t ldx, const void* a, const void* s, float divisor, void* out, uint16_t* outb,
+                            int rounds, const int64_t* offsets, const int64_t* out_offsets) {
     R.launched = false;
-    if (f < 0 || f >= kNumStepForms) return fail(FA_ERR_ARG, "unknown step form %d", f);
     if (rounds < 1 || rounds > kMaxRounds || !offsets) return fail(FA_ERR_ARG, "rounds must be 1..%d", kMaxRounds);
-    const StepSpec& sp = kStepSpecs[f];
-    const int64_t col_align = sp.bf16 ? 8 : 4;
-    // fp32 rows write out; bf16 rows out and/or outb (ABI 5: out may be null)
+    const int64_t col_align = sp.octets() ? 8 : 4;
+    // fp32 and float16 rows write out; bf16 rows out and/or outb (ABI 5: out may be null)
     if (!X || !a || N < 1 || (sp.bf16 ? (!out && !outb) : !out))
         return fail(FA_ERR_ARG, sp.bf16 ? "null X/a, no output (out_f32 and out_bf16 both null) or N < 1"
                                         : "null X/a/out or N < 1");
@@ -3035,31 +3098,46 @@ inline int launch_step(RoundsState& R, int f, hipStream_t st, const void* X, int
     if (R.start && hipEventRecord(R.start, st) != hipSuccess) return check_launch("rounds fold: start event");
     const uint16_t* Xb = static_cast<const uint16_t*>(X);
     const float* Xf = static_cast<const float*>(X);
+    const float *af = static_cast<const float*>(a), *sf = static_cast<const float*>(s);
+    const uint16_t *ah = static_cast<const uint16_t*>(a), *sh = static_cast<const uint16_t*>(s);
+    float* outf = static_cast<float*>(out);
+    uint16_t* outh = static_cast<uint16_t*>(out);
     // the kernel instantiation is found from the form's tile shapes (never by
     // its index): a form whose shapes no instantiation below has is refused
     bool launched = false;
 #define FA_STB(UB, CB, US, CS, BAL, WTM)                                                                         \
-    if (!launched && sp.bf16 && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS && sp.bal == BAL &&     \
-        wtm == WTM) {                                                                                            \
+    if (!launched && sp.bf16 && !sp.f16 && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS &&           \
+        sp.bal == BAL && wtm == WTM) {                                                                           \
         launched = true;                                                                                         \
         if (s)                                                                                                   \
             hipLaunchKernelGGL((k_fedavg_bf16_step<UB, CB, US, CS, true, kBlock, BAL, WTM>), dim3((unsigned)grid), \
-                               dim3(kBlock), 0, st, Xb, N, ldx, a, s, divisor, out, outb, T, R.sig, epoch);     \
+                               dim3(kBlock), 0, st, Xb, N, ldx, af, sf, divisor, outf, outb, T, R.sig, epoch);   \
         else                                                                                                     \
             hipLaunchKernelGGL((k_fedavg_bf16_step<UB, CB, US, CS, false, kBlock, BAL, WTM>),                    \
-                               dim3((unsigned)grid), dim3(kBlock), 0, st, Xb, N, ldx, a, s, divisor, out, outb, T, \
+                               dim3((unsigned)grid), dim3(kBlock), 0, st, Xb, N, ldx, af, sf, divisor, outf, outb, T, \
                                R.sig, epoch);                                                                    \
     }
 #define FA_STF(UB, CB, US, CS, BAL, WTM)                                                                         \
-    if (!launched && !sp.bf16 && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS && sp.bal == BAL &&    \
+    if (!launched && !sp.octets() && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS && sp.bal == BAL && \
         wtm == WTM) {                                                                                            \
         launched = true;                                                                                         \
         if (s)                                                                                                   \
             hipLaunchKernelGGL((k_fold_f32_step<UB, CB, US, CS, true, kBlock, BAL, WTM>), dim3((unsigned)grid),  \
-                               dim3(kBlock), 0, st, Xf, N, ldx, a, s, divisor, out, T, R.sig, epoch);           \
+                               dim3(kBlock), 0, st, Xf, N, ldx, af, sf, divisor, outf, T, R.sig, epoch);         \
         else                                                                                                     \
             hipLaunchKernelGGL((k_fold_f32_step<UB, CB, US, CS, false, kBlock, BAL, WTM>), dim3((unsigned)grid), \
-                               dim3(kBlock), 0, st, Xf, N, ldx, a, s, divisor, out, T, R.sig, epoch);           \
+                               dim3(kBlock), 0, st, Xf, N, ldx, af, sf, divisor, outf, T, R.sig, epoch);         \
+    }
+#define FA_STH(UB, CB, US, CS, BAL, WTM)                                                                         \
+    if (!launched && sp.f16 && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS && sp.bal == BAL &&      \
+        wtm == WTM) {                                                                                            \
+        launched = true;                                                                                         \
+        if (s)                                                                                                   \
+            hipLaunchKernelGGL((k_fedavg_f16_step<UB, CB, US, CS, true, kBlock, BAL, WTM>), dim3((unsigned)grid), \
+                               dim3(kBlock), 0, st, Xb, N, ldx, ah, sh, divisor, outh, T, R.sig, epoch);         \
+        else                                                                                                     \
+            hipLaunchKernelGGL((k_fedavg_f16_step<UB, CB, US, CS, false, kBlock, BAL, WTM>), dim3((unsigned)grid), \
+                               dim3(kBlock), 0, st, Xb, N, ldx, ah, sh, divisor, outh, T, R.sig, epoch);         \
     }
     FA_STB(8, 4, 8, 2, false, kWtAgent)
     FA_STB(8, 4, 8, 4, false, kWtAgent)
@@ -3069,8 +3147,12 @@ inline int launch_step(RoundsState& R, int f, hipStream_t st, const void* X, int
     // system-coherent stores: the two policy forms only (a peer exchange's launches)
     FA_STB(8, 4, 8, 2, true, kWtSystem)
     FA_STF(8, 4, 16, 1, false, kWtSystem)
+    // float16: agent scope only
+    FA_STH(8, 4, 8, 2, true, kWtAgent)
+    FA_STH(8, 4, 8, 4, false, kWtAgent)
 #undef FA_STB
 #undef FA_STF
+#undef FA_STH
     if (!launched)
         return fail(FA_ERR_ARG, "step form %s: no kernel for its tile shapes%s", sp.name,
                     wtm == kWtSystem ? " with system-coherent stores (the policy forms only)" : "");
@@ -3083,6 +3165,14 @@ inline int launch_step(RoundsState& R, int f, hipStream_t st, const void* X, int
     R.rounds = rounds;
     R.launched = true;
     return FA_OK;
+}
+// Form f of kStepSpecs (fp32 and bf16 rows)
+inline int launch_step(RoundsState& R, int f, hipStream_t st, const void* X, int64_t N, int64_t ldx,
+                       const float* a, const float* s, float divisor, float* out, uint16_t* outb, int rounds,
+                       const int64_t* offsets, const int64_t* out_offsets = nullptr) {
+    R.launched = false;
+    if (f < 0 || f >= kNumStepForms) return fail(FA_ERR_ARG, "unknown step form %d", f);
+    return launch_step_spec(R, kStepSpecs[f], st, X, N, ldx, a, s, divisor, out, outb, rounds, offsets, out_offsets);
 }
 
 // ---- the pointer-table fold's forms (fa_fedavg_f32_ptrs_aligned) ----------
@@ -3623,6 +3713,17 @@ inline int f16_fold(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const 
     }
 #undef FA_FH
     return check_launch("fa_fold_f16");
+}
+
+// Form f of kStepSpecsF16 (fa_fedavg_f16_rounds): binary16 factors and divisor
+// as bit patterns, the rest as launch_step.
+inline int launch_step_f16(RoundsState& R, int f, hipStream_t st, const uint16_t* X, int64_t N, int64_t ldx,
+                           const uint16_t* a, const uint16_t* s, uint16_t divisor, uint16_t* out, int rounds,
+                           const int64_t* offsets, const int64_t* out_offsets) {
+    R.launched = false;
+    if (f < 0 || f >= kNumStepFormsF16) return fail(FA_ERR_ARG, "unknown float16 step form %d", f);
+    return launch_step_spec(R, kStepSpecsF16[f], st, X, N, ldx, a, s, half_bits_to_float(divisor), out, nullptr,
+                            rounds, offsets, out_offsets);
 }
 
 // ---- the 16-bit row-table folds (fa_fedavg_bf16_ptrs, fa_fedavg_f16_ptrs) ----

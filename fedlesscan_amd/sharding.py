@@ -71,14 +71,15 @@ def tail_shares(rounds: int, tail: float, steps: int = 1) -> List[float]:
 # gather still hides behind round 4's fold at rho 0.14; the steeper 1, 1,
 # 0.35, 0.125 measured 0.11 ms more fold per C3 rank step on one GPU);
 # bf16: a gentle geometric tail, 1, 0.7, 0.49, 0.34, so that every round
-# still covers the previous round's gather.
-DEFAULT_TAIL = {"f32": (0.125, 1), "bf16": (0.343, 3)}
+# still covers the previous round's gather; float16 moves bf16's
+# bytes in and out, so it takes bf16's layout.
+DEFAULT_TAIL = {"f32": (0.125, 1), "bf16": (0.343, 3), "f16": (0.343, 3)}
 
 
 def overlap_layout(P: int, world: int, dtype: str = "f32", rounds: int = 4, align: int = ALIGN,
                    quantum: int = 0) -> "SlotLayout":
     """The SlotLayout ShardedAggregator.aggregate_slots should get for a
-    `dtype` ("f32" / "bf16") model of P params over `world` ranks (quantum:
+    `dtype` ("f32" / "bf16" / "f16") model of P params over `world` ranks (quantum:
     see SlotLayout, e.g. pass_quantum())."""
     tail, steps = DEFAULT_TAIL[dtype]
     return SlotLayout(P, world, rounds, align=align, shares=tail_shares(rounds, tail, steps) if rounds > 1 else None,
@@ -89,7 +90,7 @@ def pass_quantum(cus: int, dtype: str = "f32") -> int:
     """Columns one pass of the one-launch step's wide tiles covers (a block per
     CU, 256 lanes x 4 quads / octets): a round that is a whole number of
     passes completes with its last pass instead of a tile-time after it."""
-    return cus * 256 * 4 * (8 if dtype == "bf16" else 4)
+    return cus * 256 * 4 * (8 if dtype in ("bf16", "f16") else 4)
 
 
 class SlotLayout:
@@ -232,13 +233,23 @@ def device_ident(device) -> str:
     return f"{arch}:{p.multi_processor_count}".replace(" ", "_")
 
 
-def step_key(ident: str, bf16: bool, n_clients: int, layout: "SlotLayout", exchange: str = "rccl") -> str:
+def step_key(ident: str, bf16, n_clients: int, layout: "SlotLayout", exchange: str = "rccl", *,
+             dtype: Optional[str] = None) -> str:
     """The key of a step-form decision (fa_step_lookup / fa_step_record):
     device identity, dtype (".peer" appended for the peer-copy exchange),
     world size, client-count bucket (the count moves from round to round with
-    stragglers; a form's advantage does not), P and the layout's slot widths."""
+    stragglers; a form's advantage does not), P and the layout's slot widths.
+    The dtype: `bf16` as a bool (True bf16, False fp32) or as the name "f32" /
+    "bf16" / "f16", or the keyword `dtype`, which wins; each dtype's decisions
+    have keys of their own (the key spells float16 out: the cache file's
+    step lines take "f32", "bf16" and "float16")."""
     bucket = 1 << max(0, int(n_clients) - 1).bit_length()
-    dt = ("bf16" if bf16 else "f32") + (".peer" if exchange == "peer_copy" else "")
+    name = dtype if dtype is not None else (bf16 if isinstance(bf16, str) else ("bf16" if bf16 else "f32"))
+    if name not in DEFAULT_TAIL:
+        raise ValueError(f"step_key: dtype {name!r} is not one of {sorted(DEFAULT_TAIL)}")
+    if name == "f16" and exchange == "peer_copy":
+        raise ValueError("step_key: float16 steps take the RCCL exchange only")
+    dt = ("float16" if name == "f16" else name) + (".peer" if exchange == "peer_copy" else "")
     return f"{ident} {dt} {layout.world} {bucket} {layout.P} {','.join(str(w) for w in layout.widths)}"
 
 
@@ -443,7 +454,8 @@ class ShardedAggregator:
             if not X_local.is_cuda:
                 return None
             ident = self.ident = device_ident(X_local.device)
-        return step_key(ident, X_local.dtype == torch.bfloat16, int(X_local.shape[0]), layout, self.exchange)
+        dt = "f16" if X_local.dtype == torch.float16 else X_local.dtype == torch.bfloat16
+        return step_key(ident, dt, int(X_local.shape[0]), layout, self.exchange)
 
     def step_form(self, X_local: torch.Tensor, layout: "SlotLayout") -> Optional[str]:
         """The recorded step form for this shape ("one launch" / "per round"),
@@ -546,7 +558,12 @@ class ShardedAggregator:
 
     def aggregate(self, X_local: torch.Tensor, weights: Sequence, scores: Optional[Sequence] = None,
                   P: Optional[int] = None, total=None) -> torch.Tensor:
-        """X_local = this rank's columns [start, end) of the stacked updates, all N clients."""
+        """X_local = this rank's columns [start, end) of the stacked updates, all N clients.
+        float16 rows under factors that keep them float16 give a float16 model."""
+        f16 = X_local.dtype == torch.float16
+        if f16 and self.default_fold:
+            # factors that promote the rows: refused on every rank, before any collective
+            self._f16_factors(weights, scores, total)
         if P is None:
             t = torch.tensor([X_local.shape[1]], dtype=torch.int64, device=X_local.device)
             if self.world > 1:
@@ -558,8 +575,19 @@ class ShardedAggregator:
         if hi > lo:
             local = self.fold(X_local, weights, scores, total=total)
         else:
-            local = torch.empty(0, dtype=torch.float32, device=X_local.device)
+            local = torch.empty(0, dtype=torch.float16 if f16 else torch.float32, device=X_local.device)
         return self.gather(local, P)
+
+    @staticmethod
+    def _f16_factors(weights, scores, total):
+        """The binary16 factors of a float16 step (engine.f16_factors);
+        factors that promote the rows are refused: the slots are float16."""
+        from .aggregator.exceptions import InvalidParameterShapeError
+        from .engine import f16_factors
+        f = f16_factors(weights, scores, total)
+        if f is None:
+            raise InvalidParameterShapeError("weights/scores promote the float16 fold (numpy scalar types)")
+        return f
 
     def aggregate_slots(self, X_local: torch.Tensor, weights: Sequence, scores: Optional[Sequence],
                         layout: "SlotLayout", out: Optional[torch.Tensor] = None, total=None) -> torch.Tensor:
@@ -568,29 +596,39 @@ class ShardedAggregator:
 
         X_local: [N, layout.local_width], this rank's slots side by side (columns
         past P may hold anything; their outputs are trimmed).  Returns [P]:
-        float32 for fp32 updates; for bf16 updates the RNE bf16 model (the fold
-        still accumulates in fp32), so the exchange moves 2 bytes per parameter,
+        float32 for fp32 updates; float16 for float16 updates (binary16
+        arithmetic throughout, as numpy's; RCCL exchange only); for bf16
+        updates the RNE bf16 model (the fold still accumulates in fp32), so the exchange moves 2 bytes per parameter,
         half the xGMI bytes of the fp32 result.  `fold` must accept out= (and
         out_bf16= for bf16 input), as engine.fold_stacked does.  Raises
         AggregationError (every rank) when a one-launch step's round wait timed
         out (check="sync"; "deferred": at check_timeouts())."""
         if X_local.shape[1] != layout.local_width:
             raise ValueError(f"X_local has {X_local.shape[1]} columns, layout needs {layout.local_width}")
+        if X_local.dtype == torch.float16 and self.exchange == "peer_copy":
+            from .aggregator.exceptions import InvalidParameterShapeError
+            raise InvalidParameterShapeError('float16 slots take the RCCL exchange (exchange="rccl"): the peer-copy '
+                                             "exchange moves float32 and bfloat16 slots only")
         if not X_local.is_cuda or torch.cuda.is_current_stream_capturing():
             # CPU ranks, or a HIP graph capture (the one launch refuses
             # capture: its epochs would replay): per-round launches, nothing
             # timed or checked
             return self._aggregate_slots(X_local, weights, scores, layout, out, total)
         # the factors, rounded once for the whole step (numpy's weak-scalar
-        # rule, engine.f32_factors): the default fold's slots are float32 /
-        # bf16 buffers, so promoted factors (numpy-scalar weights) are refused
+        # rule, engine.f32_factors / f16_factors): the default fold's slots are
+        # float32 / bf16 / float16 buffers, so promoted factors (numpy-scalar
+        # weights) are refused
         f = None
         if self.default_fold:
             from .aggregator.exceptions import InvalidParameterShapeError
             from .engine import f32_factors
-            if X_local.dtype not in (torch.float32, torch.bfloat16):
-                raise InvalidParameterShapeError(f"sharded slots take float32 or bfloat16 rows, not {X_local.dtype}")
-            f = f32_factors(weights, scores, total)
+            if X_local.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+                raise InvalidParameterShapeError(
+                    f"sharded slots take float32, bfloat16 or float16 rows, not {X_local.dtype}")
+            if X_local.dtype == torch.float16:
+                f = self._f16_factors(weights, scores, total)
+            else:
+                f = f32_factors(weights, scores, total)
             if f is None:
                 raise InvalidParameterShapeError("weights/scores promote the float32 fold (numpy scalar types)")
         one, probing = self._form(X_local, layout)
@@ -734,20 +772,20 @@ class ShardedAggregator:
         ranks never split on it."""
         if not (self.default_fold and X_local.is_cuda) or not 1 < layout.rounds <= 8:
             return False
-        if X_local.dtype not in (torch.float32, torch.bfloat16):
+        if X_local.dtype not in (torch.float32, torch.bfloat16, torch.float16):
             return False
         if X_local.shape[0] < 1 or min(layout.widths) < 1:
             return False
-        align = 8 if X_local.dtype == torch.bfloat16 else 4
+        align = 8 if X_local.dtype in (torch.bfloat16, torch.float16) else 4
         return not any(layout.offset(k) % align for k in range(layout.rounds))
 
     @staticmethod
     def _aligned(X_local: torch.Tensor) -> torch.Tensor:
         """X_local, or an aligned copy of it when its rows are not 16-B aligned
-        or its pitch is off the octet (bf16) / quad (fp32) grid: the one
+        or its pitch is off the octet (bf16, float16) / quad (fp32) grid: the one
         launch's 16-byte loads need both.  The copy runs on the current stream
         (the fold stream), in order before the fold that reads it."""
-        align = 8 if X_local.dtype == torch.bfloat16 else 4
+        align = 8 if X_local.dtype in (torch.bfloat16, torch.float16) else 4
         if (X_local.data_ptr() % 16 == 0 and X_local.stride(1) == 1
                 and (X_local.shape[0] == 1 or X_local.stride(0) % align == 0)):
             return X_local
@@ -779,7 +817,7 @@ class ShardedAggregator:
         from . import engine
         dev = X_local.device
         bf16 = X_local.dtype == torch.bfloat16
-        odt = torch.bfloat16 if bf16 else torch.float32
+        odt = X_local.dtype if X_local.dtype in (torch.bfloat16, torch.float16) else torch.float32
         full = out if out is not None else torch.empty(layout.padded_total, dtype=odt, device=dev)
         if full.dtype != odt or full.numel() < layout.padded_total or not full.is_contiguous():
             raise ValueError(f"out needs {layout.padded_total} contiguous {odt} elements")
@@ -788,7 +826,8 @@ class ShardedAggregator:
         fs = torch.cuda.current_stream(dev)
         e = _timing_pair(fs, folds)
         # all the fold stores: the fp32 result, or for bf16 rows only its
-        # RNE-bf16 copy (no fp32 result, ABI 5) -- the form the exchange moves
+        # RNE-bf16 copy (no fp32 result, ABI 5) -- the form the exchange moves;
+        # float16 rows their float16 result
         kw = {"out_bf16": full} if bf16 else {"out": full}
         r = engine.fold_rounds(X_local, weights, scores, offs, total=total, factors=factors,
                                out_offsets=[lo for lo, _ in own], **kw)
@@ -832,12 +871,13 @@ class ShardedAggregator:
 
     def _aggregate_slots(self, X_local, weights, scores, layout, out, total, folds=None, factors=None):
         bf16 = X_local.dtype == torch.bfloat16
-        odt = torch.bfloat16 if bf16 else torch.float32
+        odt = X_local.dtype if X_local.dtype in (torch.bfloat16, torch.float16) else torch.float32
         full = out if out is not None else torch.empty(layout.padded_total, dtype=odt, device=X_local.device)
         if full.dtype != odt or full.numel() < layout.padded_total or not full.is_contiguous():
             raise ValueError(f"out needs {layout.padded_total} contiguous {odt} elements")
         # each round's fold writes straight into this rank's chunk of the model
-        # (fp32 rows the fp32 result, bf16 rows only its RNE-bf16 copy), and the
+        # (fp32 rows the fp32 result, float16 rows the float16 one, bf16 rows
+        # only its RNE-bf16 copy), and the
         # round's all-gather runs in place: at world 1 nothing is copied
         cur = torch.cuda.current_stream(X_local.device) if X_local.is_cuda else None
         staged = None
@@ -875,6 +915,8 @@ class ShardedAggregator:
                          scores: Optional[Sequence] = None, device=None) -> List:
         """Reference-shaped entry (fed_avg_aggregator.py:24-42 over per-client
         layer lists): every rank sees the same per-client float32 numpy layers
+        (or float16 ones throughout, under factors that keep them float16: the
+        layers come back float16, folded in binary16 as numpy folds them)
         and copies only the pieces of each layer that fall in its own bucket
         (no full-row concatenation).  zip() truncation is kept: rows beyond the
         shorter of parameters / weights / scores are not folded, but the divisor
@@ -889,23 +931,27 @@ class ShardedAggregator:
             return []
         L = min(len(p) for p in parameters[:n])
         shapes = [np.asarray(parameters[0][li]).shape for li in range(L)]
+        # one dtype for every layer of every client: float32, or float16
+        dt0 = getattr(parameters[0][0], "dtype", None) if L else None
+        ldt = np.dtype(np.float16) if dt0 == np.float16 else np.dtype(np.float32)
         for i in range(n):
             for li in range(L):
                 x = parameters[i][li]
-                if not isinstance(x, np.ndarray) or x.dtype != np.float32 or x.shape != shapes[li]:
+                if not isinstance(x, np.ndarray) or x.dtype != ldt or x.shape != shapes[li]:
                     raise InvalidParameterShapeError(
-                        f"sharded aggregation takes float32 numpy layers shaped like client 0's; client {i} "
+                        f"sharded aggregation takes {ldt} numpy layers shaped like client 0's; client {i} "
                         f"layer {li} is {getattr(x, 'dtype', type(x))} {getattr(x, 'shape', None)}")
         sc = None if scores is None else list(scores[:n])
         total = sum(weights)
-        if result_dtype(np.dtype(np.float32), list(weights), sc, total) != np.float32:
-            raise InvalidParameterShapeError("weights/scores promote the float32 layers (numpy scalar types)")
+        if result_dtype(ldt, list(weights), sc, total) != ldt:
+            raise InvalidParameterShapeError(f"weights/scores promote the {ldt} layers (numpy scalar types)")
         sizes = [int(np.prod(s)) if len(s) else 1 for s in shapes]
         offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         P = int(offs[-1])
         lo, hi = self.bounds(P)
         dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        host = torch.empty((n, hi - lo), dtype=torch.float32, pin_memory=dev.type == "cuda")
+        host = torch.empty((n, hi - lo), dtype=torch.float16 if ldt == np.float16 else torch.float32,
+                           pin_memory=dev.type == "cuda")
         hv = host.numpy()
         for li in range(L):  # layers overlapping [lo, hi) only
             a, b = max(lo, int(offs[li])), min(hi, int(offs[li + 1]))

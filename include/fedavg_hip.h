@@ -237,6 +237,27 @@ int fa_rounds_timeouts(fa_rounds* r);
 /* [host] the kernel form fa_fedavg_bf16_rounds (bf16 != 0) / _f32_rounds runs */
 const char* fa_rounds_form(int bf16);
 
+/* The one launch per exchange step for float16 rows (new symbols, ABI still
+ * 7): `_aggregate` of both strategies (fed_avg_aggregator.py:31-41,
+ * stall_aware_aggregation.py:52-66) on a rank's slots of float16 layers, which
+ * numpy folds in binary16 under Python-number weights -- the arithmetic of
+ * fa_fedavg_f16, every round of a step in one launch as fa_fedavg_bf16_rounds.
+ * Bit for bit fa_fedavg_f16 on each round's columns.  a, s [device, N halves]
+ * and divisor are binary16 bit patterns as for fa_fedavg_f16 (s == NULL for
+ * FedAvg); the kernels read the aligned 4-byte word that holds each factor, so
+ * a and s must each end on a 4-byte boundary inside their allocation, as for
+ * fa_fold_f16.  out [halves] receives round k at columns [offsets[k],
+ * offsets[k+1]) or, with out_offsets, [out_offsets[k], ...).  offsets and
+ * out_offsets % 8 == 0, 1 <= rounds <= 8, X and out 16-B aligned, ldx % 8 == 0;
+ * a capturing stream -> FA_ERR_ARG.  The rounds are published at agent scope
+ * (a state of fa_peers_rounds, whose rounds other GPUs read, -> FA_ERR_ARG).
+ * fa_rounds_wait / _check / _timeouts serve it as they do the other two. */
+int fa_fedavg_f16_rounds(fa_rounds* r, const uint16_t* X, int64_t N, int64_t ldx,
+                         const uint16_t* a, const uint16_t* s, uint16_t divisor, uint16_t* out,
+                         int rounds, const int64_t* offsets, const int64_t* out_offsets, void* stream);
+/* [host] the kernel form fa_fedavg_f16_rounds runs */
+const char* fa_rounds_form_f16(void);
+
 /* ---- kernel-free peer exchange of a step (ABI 4; ABI 5: no fence) ----------
  * The reference saves ONE global model per round (aggregation.py:125-138 ->
  * ParameterDao.save, client_daos.py:351-378); at N > 1 every rank folds its

@@ -113,6 +113,14 @@ int fa_fedavg_rounds_form(void* r, int form, const void* X, int64_t N, int64_t l
                           float divisor, float* out, uint16_t* out_bf16, int rounds, const int64_t* offsets,
                           void* stream);
 int fa_bench_rounds_wait(void* r, int round, void* stream);
+/* The float16 step's forms (a table of their own: fa_num_step_forms and its
+ * names stay the bf16 / fp32 ones) and fa_fedavg_f16_rounds with a chosen one,
+ * over a fa_bench_rounds_create state (agent scope). */
+int fa_num_step_forms_f16(void);
+const char* fa_step_form_name_f16(int form);
+int fa_fedavg_f16_rounds_form(void* r, int form, const uint16_t* X, int64_t N, int64_t ldx, const uint16_t* a,
+                              const uint16_t* s, uint16_t divisor, uint16_t* out, int rounds, const int64_t* offsets,
+                              const int64_t* out_offsets, void* stream);
 /* How the state's launches publish their rounds: 0 agent scope (the default,
  * sc1 tile stores); 1 system scope as a peer exchange's state (fa_peers_rounds:
  * sc0 sc1 tile stores, the policy forms only); 2 system scope as round 5 did
