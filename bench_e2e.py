@@ -28,9 +28,12 @@ interleaved in one process: the streamed route (the native pipe with 2-byte
 rows and the chunked binary16 fold) and FEDAVG_F16_STREAM=0 (every row stacked
 into one pinned matrix, one H2D, one fold).  It reports each route's median and
 min-max, the pinned H2D rate of the same run, whether the two routes agree bit
-for bit, and a column sample against numpy's own float16 fold.
+for bit, and a column sample against numpy's own float16 fold.  --dtype float64
+does the same on float64 NPZ blobs: the float64 pipe (8-byte rows, the chunked
+float64 fold) against FEDAVG_F64_STREAM=0, with the sample against numpy's
+float64 fold.
 
-Rates are input bytes (N * P * 4, or * 2 for float16) per second.  Results are
+Rates are input bytes (N * P * 4, * 2 for float16, * 8 for float64) per second.  Results are
 compared bit for bit.
 Writes one JSON line (rank 0, one GPU).  Not the headline metric: DESIGN.md.
 """
@@ -108,31 +111,53 @@ def make_blobs_f16(N, P, seed):
     return blobs
 
 
-def same_bits16(a, b) -> bool:
-    """Equal NaN positions, equal bit patterns elsewhere (the float16 fold's contract)."""
+def make_blobs_f64(N, P, seed):
+    """float64 NPZ blobs: the synthetic rows widened and scaled by 1 + 1/3, which fills
+    the low mantissa bits; split into layers as make_blobs does."""
+    from oracle import oracle_lib as OL
+    from fedlesscan_amd.common.serialization import NpzWeightsSerializer
+    ser, blobs = NpzWeightsSerializer(), []
+    cuts = [0, P // 64, P // 8, P // 2, P]
+    for i in range(N):
+        row = OL.synth_f32(seed, 1, P, row0=i)[0].astype(np.float64) * (1.0 + 1.0 / 3.0)
+        blobs.append(ser.serialize([row[cuts[k]:cuts[k + 1]].reshape(-1, 1) if k % 2 else row[cuts[k]:cuts[k + 1]]
+                                    for k in range(4)]))
+    return blobs
+
+
+def same_bits(a, b, bits=np.uint16) -> bool:
+    """Equal NaN positions, equal bit patterns elsewhere (the float16 / float64 folds' contract)."""
     na, nb = np.isnan(a), np.isnan(b)
     return bool(a.shape == b.shape and np.array_equal(na, nb) and
-                np.array_equal(a.view(np.uint16)[~na], b.view(np.uint16)[~na]))
+                np.array_equal(a.view(bits)[~na], b.view(bits)[~na]))
 
 
-def main_f16(a):
-    """The float16 comparison: streamed route against FEDAVG_F16_STREAM=0, interleaved."""
+def main_streamed_vs_materialised(a):
+    """The float16 / float64 comparison: streamed route against FEDAVG_F16_STREAM=0 /
+    FEDAVG_F64_STREAM=0, interleaved."""
     from fedlesscan_amd import engine
     from fedlesscan_amd.ingest import NativeStreamingFold
     from fedlesscan_amd.npz import read_layers
     from oracle import fedavg_oracle as O  # checker only
     N, P = a.clients, a.params
+    f64 = a.dtype == "float64"
+    np_dt, tdt, esz = (np.float64, torch.float64, 8) if f64 else (np.float16, torch.float16, 2)
+    ubits = np.uint64 if f64 else np.uint16
+    switch = "FEDAVG_F64_STREAM" if f64 else "FEDAVG_F16_STREAM"
     t0 = time.time()
-    blobs = make_blobs_f16(N, P, a.seed)
-    cards = [int(v) for v in np.random.default_rng(a.seed + 1000).integers(1, 41, N)]  # total < 65504: finite
+    if f64:
+        blobs, cards = make_blobs_f64(N, P, a.seed), synth.cardinalities(a.seed, N)
+    else:
+        blobs = make_blobs_f16(N, P, a.seed)
+        cards = [int(v) for v in np.random.default_rng(a.seed + 1000).integers(1, 41, N)]  # total < 65504: finite
     gen_s = time.time() - t0
-    in_bytes = N * P * 2
+    in_bytes = N * P * esz
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     routes = {"streamed": "1", "materialised": "0"}
 
     def one_round(flag):
-        os.environ["FEDAVG_F16_STREAM"] = flag
+        os.environ[switch] = flag
         crs = results(blobs, cards)
         t0 = time.perf_counter()
         out, _ = FedAvgAggregator().aggregate(crs, None)
@@ -151,13 +176,13 @@ def main_f16(a):
             counted[k] = {"pipe_rows": NativeStreamingFold.stats["rows"] - r0,
                           "stacked_groups": engine.stats["stacked_groups"] - g0}
             ts[k].append(dt)
-    os.environ.pop("FEDAVG_F16_STREAM", None)
+    os.environ.pop(switch, None)
     flat = {k: np.concatenate([np.asarray(x).reshape(-1) for x in v]) for k, v in outs.items()}
     t0 = time.perf_counter()
     for b in blobs:
         read_layers(b)
     t_decode = time.perf_counter() - t0
-    host = torch.empty(min(in_bytes // 2, 1 << 29), dtype=torch.float16, pin_memory=True)
+    host = torch.empty(min(in_bytes // esz, (1 << 30) // esz), dtype=tdt, pin_memory=True)
     dbuf = torch.empty_like(host, device=dev)
     dbuf.copy_(host, non_blocking=True)
     torch.cuda.synchronize()
@@ -165,12 +190,12 @@ def main_f16(a):
     for _ in range(3):
         dbuf.copy_(host, non_blocking=True)
     torch.cuda.synchronize()
-    h2d_gbs = 3 * host.numel() * 2 / (time.perf_counter() - t0) / 1e9
+    h2d_gbs = 3 * host.numel() * esz / (time.perf_counter() - t0) / 1e9
     med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
     spread = max(ts["materialised"]) - min(ts["materialised"])
     res = {
-        "metric": "end-to-end aggregation of float16 NPZ blobs, streamed route vs FEDAVG_F16_STREAM=0",
-        "dtype": "float16", "clients": N, "params": P, "input_bytes": in_bytes, "reps": a.reps,
+        "metric": f"end-to-end aggregation of {a.dtype} NPZ blobs, streamed route vs {switch}=0",
+        "dtype": a.dtype, "clients": N, "params": P, "input_bytes": in_bytes, "reps": a.reps,
         "gen_s": round(gen_s, 1),
     }
     for k in routes:
@@ -183,24 +208,25 @@ def main_f16(a):
     res["streamed_fraction_of_h2d"] = round(in_bytes / med["streamed"] / 1e9 / h2d_gbs, 3)
     res["decode_views_s"] = round(t_decode, 4)
     res["stream_chunk_mb"] = int(os.environ.get("FEDAVG_STREAM_CHUNK_MB", "32"))
-    res["routes_bit_equal"] = same_bits16(flat["streamed"], flat["materialised"])
-    # numpy's own float16 fold on the first and the last K columns
+    res["routes_bit_equal"] = same_bits(flat["streamed"], flat["materialised"], ubits)
+    # numpy's own fold in the rows' dtype on the first and the last K columns
     K = min(a.check_cols or 4096, P)
     ok = True
     for c0 in sorted({0, P - K}):
         X = np.stack([np.concatenate([np.asarray(x).reshape(-1) for x in read_layers(b)])[c0:c0 + K] for b in blobs])
         with np.errstate(all="ignore"):
             exp = O.fedavg_stacked(X, cards)
-        ok &= exp.dtype == np.float16 and same_bits16(flat["streamed"][c0:c0 + K], exp)
+        ok &= exp.dtype == np_dt and same_bits(flat["streamed"][c0:c0 + K], exp, ubits)
     res["bit_exact_column_sample"] = bool(ok)
-    res["column_sample"] = f"first and last {K} columns vs numpy's float16 fold"
+    res["column_sample"] = f"first and last {K} columns vs numpy's {a.dtype} fold"
     print(json.dumps(res), flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--dtype", choices=["float32", "float16"], default="float32",
-                    help="float16: the streamed route against FEDAVG_F16_STREAM=0, interleaved (NPZ blobs, one GPU)")
+    ap.add_argument("--dtype", choices=["float32", "float16", "float64"], default="float32",
+                    help="float16 / float64: the streamed route against FEDAVG_F16_STREAM=0 / FEDAVG_F64_STREAM=0, "
+                         "interleaved (NPZ blobs, one GPU)")
     ap.add_argument("--clients", type=int, default=100)
     ap.add_argument("--params", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=7)
@@ -214,10 +240,10 @@ def main():
                     help="comma-separated GPU ordinals for the multi-GPU drop-in (FedAvgAggregator(devices=...)); "
                          "'all' = every visible GPU; a GPU may repeat (buckets sharing one GPU)")
     a = ap.parse_args()
-    if a.dtype == "float16":
+    if a.dtype in ("float16", "float64"):
         if a.bson or a.pinned_store or a.devices:
-            ap.error("--dtype float16 measures NPZ blobs on one GPU")
-        return main_f16(a)
+            ap.error(f"--dtype {a.dtype} measures NPZ blobs on one GPU")
+        return main_streamed_vs_materialised(a)
     from oracle import fedavg_oracle as O  # checker + CPU reference timing only
     N, P = a.clients, a.params
     t0 = time.time()

@@ -79,6 +79,8 @@ _PROTOS = {
     "fa_peers_rounds": (_vp, [_vp]),
     "fa_peers_exchange": (_int, [_vp, _int, _vp, _vp, _vp, _vp]),
     "fa_fedavg_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f64, _vp, _vp]),
+    "fa_fold_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _f64, _int, _vp, _vp]),
+    "fa_fedavg_f64_ptrs": (_int, [_vp, _i64, _i64, _vp, _vp, _f64, _int, _vp, _vp]),
     "fa_fedavg_i32": (_int, [_vp, _i64, _i64, _i64, _vp, _f64, _vp, _vp]),
     "fa_fedavg_i64": (_int, [_vp, _i64, _i64, _i64, _vp, _f64, _vp, _vp]),
     "fa_npz_index": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _int]),
@@ -109,6 +111,10 @@ _PROTOS = {
     "fa_ingest_begin_f16": (_int, [_vp, _vp, _vp, _i64]),
     "fa_ingest_add_f16": (_int, [_vp, _vp, _vp, _i64, ctypes.c_uint16, ctypes.c_uint16, _int]),
     "fa_ingest_finish_f16": (_int, [_vp, ctypes.c_uint16]),
+    "fa_ingest_create_f64": (_int, [_vp, _i64, _i64, _int, _int]),
+    "fa_ingest_begin_f64": (_int, [_vp, _vp, _vp, _i64]),
+    "fa_ingest_add_f64": (_int, [_vp, _vp, _vp, _i64, _f64, _f64, _int]),
+    "fa_ingest_finish_f64": (_int, [_vp, _f64]),
 }
 
 # libfedavg_hip_bench.so (include/fedavg_hip_bench.h)

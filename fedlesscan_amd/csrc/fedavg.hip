@@ -487,6 +487,16 @@ int fa_fedavg_f64(const double* X, int64_t N, int64_t P, int64_t ldx, const doub
     return check_launch("k_fedavg_f64");
 }
 
+int fa_fold_f64(const double* X, int64_t N, int64_t P, int64_t ldx, const double* a, const double* s,
+                const double* acc_in, double divisor, int finalize, double* out, void* stream) {
+    return f64_fold(X, N, P, ldx, a, s, acc_in, divisor, finalize, out, stream);
+}
+
+int fa_fedavg_f64_ptrs(const double* const* xi, int64_t N, int64_t P, const double* a, const double* s,
+                       double divisor, int rows_aligned, double* out, void* stream) {
+    return f64_rows_fold(xi, N, P, a, s, divisor, rows_aligned, out, stream);
+}
+
 int fa_fedavg_i32(const int32_t* X, int64_t N, int64_t P, int64_t ldx, const int64_t* a, double divisor,
                   double* out, void* stream) {
     int rc = check_common(N, P, ldx, X, a, out);

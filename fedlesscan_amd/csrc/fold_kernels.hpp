@@ -1413,19 +1413,21 @@ struct PitchedRows {  // row i of a stacked matrix: p + i * ld
 // in flight).  The base itself is a wave-uniform scalar load.
 typedef __attribute__((address_space(1))) const uint16_t gu16;
 typedef __attribute__((address_space(1))) const u32x4 gu32x4;
-template <class G>
-struct TableRows {  // row i of a row table: xi[i] + o (G = gu32x4 or gu16)
-    const uint16_t* const* xi;
+template <class G, class E = uint16_t>
+struct TableRows {  // row i of a row table: xi[i] + o (G = gu32x4 or gu16; float64: gf64x2 or gf64, E = double)
+    const E* const* xi;
     int64_t o;
     __device__ __forceinline__ const G* row(int64_t i) const { return (const G*)xi[i] + o; }
 };
 
 // The tiling of every octet kernel: a lane owns C octets spaced B apart.  A
 // full tile folds in one call, a partial last tile octet by octet, and the
-// trailing P % 8 columns [P & ~7, P) go to the lane with o0 == P / 8.
-template <int C, int B = kBlock, class Full, class One, class Tail>
+// trailing P % 8 columns [P & ~7, P) go to the lane with o0 == P / 8.  LG: the
+// columns of a 16-byte unit as a power of two (3: an octet of 16-bit elements;
+// 1: a pair of float64).
+template <int C, int B = kBlock, int LG = 3, class Full, class One, class Tail>
 __device__ __forceinline__ void octet_tile(int64_t bid, int64_t P, Full full, One one, Tail tail) {
-    const int64_t no = P >> 3;  // full octets
+    const int64_t no = P >> LG;  // full units
     const int64_t o0 = bid * (B * C) + threadIdx.x;
     if (o0 + (int64_t)(C - 1) * B < no) {
         full(o0);
@@ -1437,7 +1439,7 @@ __device__ __forceinline__ void octet_tile(int64_t bid, int64_t P, Full full, On
         if (o < no) one(o);
     }
     const int64_t tb = no / (B * C), tl = (no % (B * C)) % B;
-    if ((P & 7) && bid == tb && (int64_t)threadIdx.x == tl) tail(no * 8);
+    if ((P & ((1 << LG) - 1)) && bid == tb && (int64_t)threadIdx.x == tl) tail(no << LG);
 }
 
 // One row group of U rows x C octets: loaded (ld) and folded in row order (add)
@@ -2322,6 +2324,202 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f64(
         acc = acc + t;
     }
     out[c] = acc / divisor;
+}
+
+// ---------------------------------------------------------------------------
+// The float64 pair family (fa_fold_f64, fa_fedavg_f64_ptrs): the arithmetic of
+// k_fedavg_f64_v2 -- double multiply, double add, the IEEE double divide, no
+// FMA -- over a row source, written the way fold_octets_f16 is.  A 16-byte
+// load holds a pair of columns; a lane owns C pairs spaced kBlock lanes apart
+// and issues U rows x C pairs of non-temporal loads ahead of the ordered adds.
+// The ACC / FIN switches are those of the float16 folds:
+//   ACC: the fold continues from acc_in (may alias out: a lane reads its own
+//        pairs before it writes them); !ACC: acc = t_0, not 0 + t_0, so a
+//        column of -0.0 stays -0.0.
+//   FIN: out = fl64(acc / divisor); !FIN: out = acc.  Every add rounds to
+//        binary64, so the doubles carried from one chunk to the next are the
+//        accumulator itself: any cut of the rows gives the bits of one
+//        fa_fedavg_f64 over all of them.
+// The partial accumulator is stored with plain stores (the next chunk's fold
+// reads it back), the final result non-temporally.  Row-table bases are read
+// as global-memory pointers (TableRows, for the reason written above it); the
+// factors are inputs no launch writes and are read as constant memory, so
+// they are scalar loads wherever they stand.
+// ---------------------------------------------------------------------------
+typedef __attribute__((address_space(1))) const f64x2 gf64x2;
+typedef __attribute__((address_space(1))) const double gf64;
+typedef __attribute__((address_space(4))) const double cf64;
+__device__ __forceinline__ double factor_d(const double* __restrict__ a, int64_t i) { return *(cf64*)(a + i); }
+
+template <bool SCORED>
+__device__ __forceinline__ f64x2 term_d2(f64x2 x, double a, double s) {
+    f64x2 t = x * a;
+    if constexpr (SCORED) t = t * s;
+    return t;
+}
+template <bool SCORED>
+__device__ __forceinline__ double term_d1(double x, double a, double s) {
+    double t = x * a;
+    if constexpr (SCORED) t = t * s;
+    return t;
+}
+template <bool FIN>
+__device__ __forceinline__ void st_d2(f64x2* out, f64x2 acc, double divisor) {
+    if constexpr (FIN) __builtin_nontemporal_store(acc / divisor, out);
+    else *out = acc;
+}
+
+// One float64 column (the P % 2 tail lane, the one-column kernels): 8 rows of
+// loads ahead of the ordered adds
+template <bool SCORED, bool ACC, bool FIN, class Rows>
+__device__ __forceinline__ double fold_column_f64(Rows src, int64_t N, const double* __restrict__ a,
+                                                  const double* __restrict__ s, const double* acc_in,
+                                                  double divisor) {
+    double acc;
+    int64_t i = 0;
+    if constexpr (ACC) {
+        acc = *acc_in;
+    } else {
+        acc = term_d1<SCORED>(*src.row(0), factor_d(a, 0), SCORED ? factor_d(s, 0) : 1.0);
+        i = 1;
+    }
+    for (; i + 8 <= N; i += 8) {
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load(src.row(i + u));
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            acc = acc + term_d1<SCORED>(v[u], factor_d(a, i + u), SCORED ? factor_d(s, i + u) : 1.0);
+    }
+    for (; i < N; ++i) acc = acc + term_d1<SCORED>(*src.row(i), factor_d(a, i), SCORED ? factor_d(s, i) : 1.0);
+    return FIN ? acc / divisor : acc;
+}
+
+// The float64 pair fold: the lane's C pairs of the rows of src, in row order;
+// acc_in and out point at the lane's first pair.
+template <int U, int C, bool SCORED, bool ACC, bool FIN, class Rows>
+__device__ __forceinline__ void fold_pairs_f64(Rows src, int64_t N, const double* __restrict__ a,
+                                               const double* __restrict__ s, const f64x2* acc_in, double divisor,
+                                               f64x2* out) {
+    f64x2 acc[C];
+    int64_t i = 0;
+    if constexpr (ACC) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = acc_in[c * kBlock];
+    } else {
+        const auto* r = src.row(0);
+        const double a0 = factor_d(a, 0), s0 = SCORED ? factor_d(s, 0) : 1.0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = term_d2<SCORED>(__builtin_nontemporal_load(r + c * kBlock), a0, s0);
+        i = 1;
+    }
+    for (; i + U <= N; i += U) {
+        f64x2 v[U][C];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const auto* r = src.row(i + u);
+#pragma unroll
+            for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const double ai = factor_d(a, i + u), si = SCORED ? factor_d(s, i + u) : 1.0;
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_d2<SCORED>(v[u][c], ai, si);
+        }
+    }
+    for (; i < N; ++i) {
+        const auto* r = src.row(i);
+        const double ai = factor_d(a, i), si = SCORED ? factor_d(s, i) : 1.0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_d2<SCORED>(__builtin_nontemporal_load(r + c * kBlock), ai, si);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) st_d2<FIN>(out + c * kBlock, acc[c], divisor);
+}
+
+// One pair tile of a stacked float64 matrix (acc_in may alias out): the tiling
+// of octet_tile with pairs in place of octets
+template <int U, int C, bool SCORED, bool ACC, bool FIN>
+__device__ __forceinline__ void f64_tile(int64_t bid, const double* __restrict__ X, int64_t N, int64_t P,
+                                         int64_t ldx, const double* __restrict__ a, const double* __restrict__ s,
+                                         const double* acc_in, double divisor, double* out) {
+    const int64_t ldp = ldx >> 1;
+    const f64x2* X2 = reinterpret_cast<const f64x2*>(X);
+    const f64x2* A2 = reinterpret_cast<const f64x2*>(acc_in);
+    f64x2* O2 = reinterpret_cast<f64x2*>(out);
+    octet_tile<C, kBlock, 1>(
+        bid, P,
+        [&](int64_t o) {
+            fold_pairs_f64<U, C, SCORED, ACC, FIN>(PitchedRows<f64x2>{X2 + o, ldp}, N, a, s, ACC ? A2 + o : nullptr,
+                                                   divisor, O2 + o);
+        },
+        [&](int64_t o) {
+            fold_pairs_f64<U, 1, SCORED, ACC, FIN>(PitchedRows<f64x2>{X2 + o, ldp}, N, a, s, ACC ? A2 + o : nullptr,
+                                                   divisor, O2 + o);
+        },
+        [&](int64_t col) {  // the P % 2 column
+            out[col] = fold_column_f64<SCORED, ACC, FIN>(PitchedRows<double>{X + col, ldx}, N, a, s,
+                                                         ACC ? acc_in + col : nullptr, divisor);
+        });
+}
+
+// float64 chunked fold (fa_fold_f64): grid-stride over pair tiles with
+// balanced passes set by the launch
+template <int U, int C, bool SCORED, bool ACC, bool FIN>
+__global__ __launch_bounds__(kBlock) void k_fold_f64_gs(
+    const double* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
+    const double* __restrict__ a, const double* __restrict__ s,
+    const double* acc_in, double divisor, double* out, int64_t ntiles) {  // acc_in may alias out
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        f64_tile<U, C, SCORED, ACC, FIN>(bid, X, N, P, ldx, a, s, acc_in, divisor, out);
+}
+
+// chunked fold, one column per lane: rows, accumulator or output at any 8-B
+// offset, any pitch
+template <bool SCORED, bool ACC, bool FIN>
+__global__ __launch_bounds__(kBlock) void k_fold_f64_scalar(
+    const double* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
+    const double* __restrict__ a, const double* __restrict__ s,
+    const double* acc_in, double divisor, double* out) {  // acc_in may alias out
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P) return;
+    out[c] = fold_column_f64<SCORED, ACC, FIN>(PitchedRows<double>{X + c, ldx}, N, a, s,
+                                               ACC ? acc_in + c : nullptr, divisor);
+}
+
+// float64 list-of-rows form with every row 16-B aligned (fa_fedavg_f64_ptrs,
+// rows_aligned != 0): the pair fold over a row table, grid-stride over pair tiles
+template <int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f64_rows_gs(
+    const double* const* __restrict__ xi, int64_t N, int64_t P, const double* __restrict__ a,
+    const double* __restrict__ s, double divisor, double* __restrict__ out, int64_t ntiles) {
+    f64x2* O2 = reinterpret_cast<f64x2*>(out);
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        octet_tile<C, kBlock, 1>(
+            bid, P,
+            [&](int64_t o) {
+                fold_pairs_f64<U, C, SCORED, false, true>(TableRows<gf64x2, double>{xi, o}, N, a, s, nullptr, divisor,
+                                                          O2 + o);
+            },
+            [&](int64_t o) {
+                fold_pairs_f64<U, 1, SCORED, false, true>(TableRows<gf64x2, double>{xi, o}, N, a, s, nullptr, divisor,
+                                                          O2 + o);
+            },
+            [&](int64_t col) {
+                out[col] = fold_column_f64<SCORED, false, true>(TableRows<gf64, double>{xi, col}, N, a, s, nullptr,
+                                                                divisor);
+            });
+}
+
+// float64 list-of-rows form, rows at any 8-B offset: one column per lane
+template <bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f64_rows_scalar(
+    const double* const* __restrict__ xi, int64_t N, int64_t P, const double* __restrict__ a,
+    const double* __restrict__ s, double divisor, double* __restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P) return;
+    out[c] = fold_column_f64<SCORED, false, true>(TableRows<gf64, double>{xi, c}, N, a, s, nullptr, divisor);
 }
 
 // numpy integer semantics: product and fold in the input dtype with
@@ -3837,6 +4035,110 @@ inline int f16_rows_fold(const uint16_t* const* xi, int64_t N, int64_t P, const 
             break;
     }
     return check_launch("fa_fedavg_f16_ptrs");
+}
+
+// ---- the float64 pair folds (fa_fold_f64, fa_fedavg_f64_ptrs) -----------------
+// One form per shape, fixed on the host, no tuner kind.  Pairs per lane: the
+// most of 4, 2, 1 whose balanced grid (at most one block per CU) still covers
+// 7/8 of the CUs, else 1 -- the bytes in flight come from the width first.
+// Rows ahead: 4 for the chunked fold (the ingest pipe's chunks have 1 to a few
+// dozen rows, and its first chunks ramp 1, 2, 4), 8 for the row table (hundreds
+// of rows: the fp32 large-model geometry, 8 rows x 4 x 16 B, where the width
+// allows 4 pairs).  DESIGN.md 5 float64.
+constexpr int kFoldF64U = 4, kRowsF64U = 8;
+
+inline int pick_pairs(int64_t P, int64_t cus) {
+    for (int c = 4; c > 1; c >>= 1)
+        if (octet_grid(P, c, -1, cus, 1).grid * 8 >= cus * 7) return c;
+    return 1;
+}
+
+template <int C, bool SC, bool ACC, bool FIN>
+void launch_fold_f64_gs(hipStream_t st, const double* X, int64_t N, int64_t P, int64_t ldx, const double* a,
+                        const double* s, const double* acc_in, double d, double* out) {
+    const OctetGrid g = octet_grid(P, C, -1, cu_count(), 1);
+    hipLaunchKernelGGL((k_fold_f64_gs<kFoldF64U, C, SC, ACC, FIN>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, X, N,
+                       P, ldx, a, s, acc_in, d, out, g.tiles);
+}
+
+template <bool SC, bool ACC, bool FIN>
+void launch_fold_f64(hipStream_t st, bool vec, const double* X, int64_t N, int64_t P, int64_t ldx, const double* a,
+                     const double* s, const double* acc_in, double d, double* out) {
+    if (!vec) {
+        hipLaunchKernelGGL((k_fold_f64_scalar<SC, ACC, FIN>), grid_for(P), dim3(kBlock), 0, st, X, N, P, ldx, a, s,
+                           acc_in, d, out);
+        return;
+    }
+    switch (pick_pairs(P, cu_count())) {
+        case 4: launch_fold_f64_gs<4, SC, ACC, FIN>(st, X, N, P, ldx, a, s, acc_in, d, out); break;
+        case 2: launch_fold_f64_gs<2, SC, ACC, FIN>(st, X, N, P, ldx, a, s, acc_in, d, out); break;
+        default: launch_fold_f64_gs<1, SC, ACC, FIN>(st, X, N, P, ldx, a, s, acc_in, d, out); break;
+    }
+}
+
+inline int f64_fold(const double* X, int64_t N, int64_t P, int64_t ldx, const double* a, const double* s,
+                    const double* acc_in, double divisor, int finalize, double* out, void* stream) {
+    if (!(acc_in && N == 0)) {
+        int rc = check_common(N, P, ldx, X, a, out);
+        if (rc) return rc;
+    } else if (P < 0) {
+        return fail(FA_ERR_ARG, "negative size (N=0, P=%lld)", (long long)P);
+    } else if (P > 0 && !out) {
+        return fail(FA_ERR_ARG, "null out pointer");
+    }
+    if (P == 0) { g_err[0] = 0; return FA_OK; }
+    hipStream_t st = (hipStream_t)stream;
+    StreamDevice on_stream_device(stream);
+    const bool sc = s != nullptr, acc = acc_in != nullptr, fin = finalize != 0;
+    const bool vec = (N == 0 || aligned16(X)) && (ldx % 2 == 0) && aligned16(out) && (!acc || aligned16(acc_in));
+#define FA_FD(SC, ACC, FIN) launch_fold_f64<SC, ACC, FIN>(st, vec, X, N, P, ldx, a, s, acc_in, divisor, out)
+    if (sc) {
+        if (acc) { if (fin) FA_FD(true, true, true); else FA_FD(true, true, false); }
+        else     { if (fin) FA_FD(true, false, true); else FA_FD(true, false, false); }
+    } else {
+        if (acc) { if (fin) FA_FD(false, true, true); else FA_FD(false, true, false); }
+        else     { if (fin) FA_FD(false, false, true); else FA_FD(false, false, false); }
+    }
+#undef FA_FD
+    return check_launch("fa_fold_f64");
+}
+
+template <int C>
+void launch_f64_rows_gs(hipStream_t st, const double* const* xi, int64_t N, int64_t P, const double* a,
+                        const double* s, double d, double* out) {
+    const OctetGrid g = octet_grid(P, C, -1, cu_count(), 1);
+    if (s)
+        hipLaunchKernelGGL((k_fedavg_f64_rows_gs<kRowsF64U, C, true>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, xi,
+                           N, P, a, s, d, out, g.tiles);
+    else
+        hipLaunchKernelGGL((k_fedavg_f64_rows_gs<kRowsF64U, C, false>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, xi,
+                           N, P, a, s, d, out, g.tiles);
+}
+
+inline int f64_rows_fold(const double* const* xi, int64_t N, int64_t P, const double* a, const double* s,
+                         double divisor, int rows_aligned, double* out, void* stream) {
+    int rc = check_common(N, P, P, xi, a, out);
+    if (rc) return rc;
+    if (P == 0) { g_err[0] = 0; return FA_OK; }
+    if (rows_aligned && !aligned16(out))
+        return fail(FA_ERR_ARG, "the pair form of the float64 row-table fold needs 16-B aligned rows and out");
+    hipStream_t st = (hipStream_t)stream;
+    StreamDevice on_stream_device(stream);
+    if (!rows_aligned) {
+        if (s)
+            hipLaunchKernelGGL(k_fedavg_f64_rows_scalar<true>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a, s, divisor,
+                               out);
+        else
+            hipLaunchKernelGGL(k_fedavg_f64_rows_scalar<false>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a, s,
+                               divisor, out);
+        return check_launch("fa_fedavg_f64_ptrs");
+    }
+    switch (pick_pairs(P, cu_count())) {
+        case 4: launch_f64_rows_gs<4>(st, xi, N, P, a, s, divisor, out); break;
+        case 2: launch_f64_rows_gs<2>(st, xi, N, P, a, s, divisor, out); break;
+        default: launch_f64_rows_gs<1>(st, xi, N, P, a, s, divisor, out); break;
+    }
+    return check_launch("fa_fedavg_f64_ptrs");
 }
 
 }  // namespace

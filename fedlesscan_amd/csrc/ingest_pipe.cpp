@@ -1,8 +1,8 @@
 // ingest_pipe.cpp — native streaming ingest for libfedavg_hip.so:
 // client rows in host memory -> packed into page-locked slots by a persistent
 // worker pool -> one DMA per slot on a copy stream -> the in-order chunked fold
-// (fa_fold_f32, or fa_fold_f16 for a float16 pipe) on the caller's compute
-// stream.
+// (fa_fold_f32, or fa_fold_f16 / fa_fold_f64 for a float16 / float64 pipe) on
+// the caller's compute stream.
 //
 // Reference path replaced: the strategies' aggregate() materialises every
 // decoded client (fed_avg_aggregator.py:64-92, stall_aware_aggregation.py:
@@ -14,7 +14,8 @@
 // order with the accumulator carried across them, so the result is
 // bit-identical to one fa_fedavg_f32 over all rows (the property fa_fold_f32
 // documents).  A pipe has an element kind: float32 rows with float factors and
-// a float accumulator, or binary16 rows (the *_f16 entries) with binary16
+// a float accumulator, binary16 rows (the *_f16 entries) with binary16
+// factors and accumulator, or float64 rows (the *_f64 entries) with double
 // factors and accumulator; everything else -- slots, ramps, packing, the
 // issuer, abandon and reuse -- is shared and counts in bytes.
 //
@@ -120,7 +121,7 @@ constexpr int64_t kTaskBytes = 1 << 20;  // one copy task: >= 1 MiB keeps the po
 
 enum class SlotState { kFree, kFilling, kQueued, kIssued };
 
-enum Kind { kF32 = 0, kF16 = 1 };
+enum Kind { kF32 = 0, kF16 = 1, kF64 = 2 };
 
 struct Slot {
     uint8_t* host = nullptr;      // [R][ldx] elements, page-locked
@@ -152,7 +153,7 @@ struct fa_ingest {
     hipStream_t copy[2] = {nullptr, nullptr};  // chunks alternate between two copy streams
     int64_t issued = 0;                         // chunks issued (issuer thread)
     // per round
-    void* acc = nullptr;  // float* or, for a float16 pipe, uint16_t*
+    void* acc = nullptr;  // float*, or uint16_t* (a float16 pipe), or double* (a float64 pipe)
     hipStream_t compute = nullptr;
     int cur = 0;
     int64_t rows = 0;
@@ -162,6 +163,7 @@ struct fa_ingest {
     int scored = -1;       // -1 unknown, 0 FedAvg, 1 stall-aware
     float divisor = 0.f;
     uint16_t divisor_h = 0;  // a float16 pipe's divisor (binary16 bits)
+    double divisor_d = 0.0;  // a float64 pipe's divisor
     // issuer
     std::thread issuer;
     std::mutex mu;
@@ -196,6 +198,9 @@ int issue(fa_ingest* p, const QueueItem& it) {
         if (p->kind == kF16)
             return fa_fold_f16(nullptr, 0, p->P, p->ldx, nullptr, nullptr, (const uint16_t*)p->acc, p->divisor_h, 1,
                                (uint16_t*)p->acc, p->compute);
+        if (p->kind == kF64)
+            return fa_fold_f64(nullptr, 0, p->P, p->ldx, nullptr, nullptr, (const double*)p->acc, p->divisor_d, 1,
+                               (double*)p->acc, p->compute);
         return fa_fold_f32(nullptr, 0, p->P, p->ldx, nullptr, nullptr, (const float*)p->acc, p->divisor, 1,
                            (float*)p->acc, p->compute);
     }
@@ -224,6 +229,10 @@ int issue(fa_ingest* p, const QueueItem& it) {
                          (const uint16_t*)sdev, p->started ? (const uint16_t*)p->acc : nullptr,
                          it.final_chunk ? p->divisor_h : (uint16_t)0, it.final_chunk ? 1 : 0, (uint16_t*)p->acc,
                          p->compute);
+    else if (p->kind == kF64)
+        rc = fa_fold_f64((const double*)S.dev, S.rows, p->P, p->ldx, (const double*)S.fac_dev, (const double*)sdev,
+                         p->started ? (const double*)p->acc : nullptr, it.final_chunk ? p->divisor_d : 0.0,
+                         it.final_chunk ? 1 : 0, (double*)p->acc, p->compute);
     else
         rc = fa_fold_f32((const float*)S.dev, S.rows, p->P, p->ldx, (const float*)S.fac_dev, (const float*)sdev,
                          p->started ? (const float*)p->acc : nullptr, it.final_chunk ? p->divisor : 0.f,
@@ -323,8 +332,8 @@ int create_pipe(fa_ingest** out, int64_t P, int64_t chunk_bytes, int slots, int 
     fa_ingest* p = new fa_ingest();
     p->P = P;
     p->kind = kind;
-    p->elem = kind == kF16 ? 2 : 4;
-    p->ldx = (P + 63) / 64 * 64;  // a row pitch of 64 elements (256 / 128 B): the vector folds
+    p->elem = kind == kF16 ? 2 : (kind == kF64 ? 8 : 4);
+    p->ldx = (P + 63) / 64 * 64;  // a row pitch of 64 elements (128 / 256 / 512 B): the vector folds
     p->R = std::max<int64_t>(1, chunk_bytes / (p->ldx * p->elem));
     p->K = slots;
     p->fac_bytes = (2 * p->R * p->elem + 255) / 256 * 256;
@@ -359,8 +368,8 @@ int create_pipe(fa_ingest** out, int64_t P, int64_t chunk_bytes, int slots, int 
 }
 
 int wrong_kind(const char* entry) {
-    return fa_internal_fail(FA_ERR_ARG, (std::string(entry) + ": the pipe was created for the other element kind "
-                                                              "(float32 / float16 entries do not mix)").c_str());
+    return fa_internal_fail(FA_ERR_ARG, (std::string(entry) + ": the pipe was created for another element kind "
+                                                              "(float32 / float16 / float64 entries do not mix)").c_str());
 }
 
 int begin_round(fa_ingest* p, void* acc, void* stream, int64_t expected_rows, int kind) {
@@ -410,8 +419,9 @@ int add_row(fa_ingest* p, const void* const* srcs, const int64_t* sizes, int64_t
         total += sizes[i];
     }
     if (total != p->P * p->elem)
-        return fa_internal_fail(FA_ERR_SHAPE, kind == kF16 ? "fa_ingest_add: row bytes != P * 2"
-                                                           : "fa_ingest_add: row bytes != P * 4");
+        return fa_internal_fail(FA_ERR_SHAPE, kind == kF16   ? "fa_ingest_add: row bytes != P * 2"
+                                              : kind == kF64 ? "fa_ingest_add: row bytes != P * 8"
+                                                             : "fa_ingest_add: row bytes != P * 4");
     if (int rc = report(p)) return rc;
     p->scored = has_s ? 1 : 0;
     Slot& S = p->slots[p->cur];
@@ -431,9 +441,10 @@ int add_row(fa_ingest* p, const void* const* srcs, const int64_t* sizes, int64_t
     S.has_s = has_s != 0;
     const float one_f = 1.0f;
     const uint16_t one_h = 0x3C00u;  // binary16 1.0
+    const double one_d = 1.0;
+    const void* one = kind == kF16 ? (const void*)&one_h : (kind == kF64 ? (const void*)&one_d : (const void*)&one_f);
     memcpy(S.fac_host + r * p->elem, a, (size_t)p->elem);
-    memcpy(S.fac_host + (p->R + r) * p->elem,
-           has_s ? s : (kind == kF16 ? (const void*)&one_h : (const void*)&one_f), (size_t)p->elem);
+    memcpy(S.fac_host + (p->R + r) * p->elem, has_s ? s : one, (size_t)p->elem);
     // copy tasks of 1 MiB, split across pieces and inside large pieces; 256 KiB
     // while the round's first chunks ramp up (the first DMA waits for them)
     const int64_t task_bytes = p->chunks <= 2 ? kTaskBytes / 4 : kTaskBytes;
@@ -474,12 +485,13 @@ int add_row(fa_ingest* p, const void* const* srcs, const int64_t* sizes, int64_t
     return FA_OK;
 }
 
-int finish_round(fa_ingest* p, float divisor, uint16_t divisor_h, int kind) {
+int finish_round(fa_ingest* p, float divisor, uint16_t divisor_h, double divisor_d, int kind) {
     if (!p) return fa_internal_fail(FA_ERR_ARG, "fa_ingest_finish: bad arguments");
     if (p->kind != kind) return wrong_kind("fa_ingest_finish");
     if (p->rows == 0) return fa_internal_fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
     p->divisor = divisor;  // read by the issuer for the final item, which is queued below
     p->divisor_h = divisor_h;
+    p->divisor_d = divisor_d;
     Slot& S = p->slots[p->cur];
     if (S.state == SlotState::kFilling && S.rows > 0) {
         enqueue(p, p->cur, true);
@@ -507,6 +519,9 @@ int fa_ingest_create(fa_ingest** out, int64_t P, int64_t chunk_bytes, int slots,
 int fa_ingest_create_f16(fa_ingest** out, int64_t P, int64_t chunk_bytes, int slots, int device) {
     return create_pipe(out, P, chunk_bytes, slots, device, kF16);
 }
+int fa_ingest_create_f64(fa_ingest** out, int64_t P, int64_t chunk_bytes, int slots, int device) {
+    return create_pipe(out, P, chunk_bytes, slots, device, kF64);
+}
 
 int fa_ingest_rows_per_chunk(const fa_ingest* p) { return p ? (int)p->R : 0; }
 
@@ -515,6 +530,9 @@ int fa_ingest_begin(fa_ingest* p, float* acc, void* stream, int64_t expected_row
 }
 int fa_ingest_begin_f16(fa_ingest* p, uint16_t* acc, void* stream, int64_t expected_rows) {
     return begin_round(p, acc, stream, expected_rows, kF16);
+}
+int fa_ingest_begin_f64(fa_ingest* p, double* acc, void* stream, int64_t expected_rows) {
+    return begin_round(p, acc, stream, expected_rows, kF64);
 }
 
 int fa_ingest_add(fa_ingest* p, const void* const* srcs, const int64_t* sizes, int64_t n, float a, float s,
@@ -525,9 +543,14 @@ int fa_ingest_add_f16(fa_ingest* p, const void* const* srcs, const int64_t* size
                       int has_s) {
     return add_row(p, srcs, sizes, n, &a, &s, has_s, kF16);
 }
+int fa_ingest_add_f64(fa_ingest* p, const void* const* srcs, const int64_t* sizes, int64_t n, double a, double s,
+                      int has_s) {
+    return add_row(p, srcs, sizes, n, &a, &s, has_s, kF64);
+}
 
-int fa_ingest_finish(fa_ingest* p, float divisor) { return finish_round(p, divisor, 0, kF32); }
-int fa_ingest_finish_f16(fa_ingest* p, uint16_t divisor) { return finish_round(p, 0.f, divisor, kF16); }
+int fa_ingest_finish(fa_ingest* p, float divisor) { return finish_round(p, divisor, 0, 0.0, kF32); }
+int fa_ingest_finish_f16(fa_ingest* p, uint16_t divisor) { return finish_round(p, 0.f, divisor, 0.0, kF16); }
+int fa_ingest_finish_f64(fa_ingest* p, double divisor) { return finish_round(p, 0.f, 0, divisor, kF64); }
 
 int fa_ingest_destroy(fa_ingest* p) {
     if (!p) return FA_OK;

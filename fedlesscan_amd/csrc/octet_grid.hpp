@@ -13,11 +13,13 @@ constexpr int kBlock = 256;  // lanes per block of every fold kernel
 //   per_cu > 0   per_cu blocks per CU, at most one per tile
 //   per_cu < 0   -per_cu blocks per CU, then the fewest blocks that finish in
 //                the same number of passes (balanced passes)
+// lg: the columns of a 16-byte unit as a power of two (3: an octet; 1: a pair
+// of float64, the float64 pair kernels).
 struct OctetGrid {
     int64_t tiles, grid;
 };
-inline OctetGrid octet_grid(int64_t P, int C, int per_cu, int64_t cus) {
-    const int64_t per_block = (int64_t)kBlock * C, units = (P >> 3) + ((P & 7) ? 1 : 0);
+inline OctetGrid octet_grid(int64_t P, int C, int per_cu, int64_t cus, int lg = 3) {
+    const int64_t per_block = (int64_t)kBlock * C, units = (P >> lg) + ((P & (((int64_t)1 << lg) - 1)) ? 1 : 0);
     const int64_t tiles = (units + per_block - 1) / per_block;
     if (per_cu == 0) return {tiles, tiles};
     int64_t g = (int64_t)(per_cu > 0 ? per_cu : -per_cu) * cus;

@@ -3,7 +3,7 @@
 Layering
   engine.fold_stacked(X, weights, scores)   X: CUDA tensor [N, P] (row pitch = X.stride(0))
   engine.fold_rows(rows, weights, scores)   N separately allocated CUDA rows (pointer list: fp32,
-                                            bf16, float16; engine.RowSet prepares a reusable row set)
+                                            bf16, float16, float64; engine.RowSet prepares a reusable row set)
   engine.aggregate_layers(params, weights)  host or device per-client layer lists -> per-layer outputs
 
 The scalar factors are formed on the host exactly as numpy forms them in the
@@ -485,8 +485,9 @@ def _fold_general(segs: List[torch.Tensor], plan: FoldPlan, weights: Sequence, s
                 (widened exactly where the dtype grows) over the run, with the
                 factors that are still to be applied, or factor 1 over finished
                 terms (x * 1 is exact).  An integer sum wraps, so its order is
-                free: a torch integer sum.  float64 has no accumulate entry but
-                nothing is wider: from the first float64 sum on, the widened
+                free: a torch integer sum.  float64 needs no accumulate step here
+                (fa_fold_f64 serves the ingest pipe): nothing is wider, so
+                from the first float64 sum on, the widened
                 accumulator and every later term are rows of one matrix that
                 fa_fedavg_f64 folds once, in order, with the true divisor
       quotient  in plan.quot, by the total rounded to it.
@@ -831,10 +832,11 @@ def _equal_stride_view(rows, host_ptrs: np.ndarray, P: int) -> Optional[torch.Te
 
 _dtype_of = operator.attrgetter("dtype")
 # dtypes the library folds through a device table of row pointers
-_ROW_TABLE_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
-# process-wide route counters (diagnostics, as StreamingFold.stats): 16-bit folds
-# that ran through a row table, layer groups copied into a stacked matrix
-stats = {"rows16_folds": 0, "stacked_groups": 0}
+_ROW_TABLE_DTYPES = (torch.float32, torch.bfloat16, torch.float16, torch.float64)
+# process-wide route counters (diagnostics, as StreamingFold.stats): 16-bit and
+# float64 folds that ran through a row table, layer groups copied into a
+# stacked matrix
+stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0}
 
 
 class RowSet:
@@ -848,8 +850,9 @@ class RowSet:
       - other fp32 rows get a device table of row pointers for
         fa_fedavg_f32_ptrs_aligned (every row 16-B aligned) or
         fa_fedavg_f32_ptrs (any alignment);
-      - other bfloat16 / float16 rows get the same table for
-        fa_fedavg_bf16_ptrs / fa_fedavg_f16_ptrs (`aligned` picks the kernels).
+      - other bfloat16 / float16 / float64 rows get the same table for
+        fa_fedavg_bf16_ptrs / fa_fedavg_f16_ptrs / fa_fedavg_f64_ptrs
+        (`aligned` picks the kernels).
     fold_rows(rowset, weights) then costs the factor upload and the kernel.
     The RowSet keeps the tensors alive; their CONTENTS may change between
     folds, their storage may not (re-create the RowSet after reallocating)."""
@@ -875,7 +878,8 @@ class RowSet:
         self.ptrs = None
         self.host_ptrs = None
         self.aligned = False
-        if dt in _ROW_TABLE_DTYPES and P > 0:
+        # (float64 rows met under a stream capture keep the stacked copy they had before the row table)
+        if dt in _ROW_TABLE_DTYPES and P > 0 and not (dt == torch.float64 and torch.cuda.is_current_stream_capturing()):
             host_ptrs = self.host_ptrs = np.fromiter(map(torch.Tensor.data_ptr, rows), dtype=np.int64, count=N)
             self.view = _equal_stride_view(rows, host_ptrs, P)
             if self.view is None:
@@ -966,11 +970,33 @@ def _fold_rows_f16(rs: "RowSet", weights, scores, out, total):
     return out
 
 
+def _fold_rows_f64(rs: "RowSet", weights, scores, out, total):
+    """float64 rows whose result stays float64 through the row table
+    (fa_fedavg_f64_ptrs): the factors of fold_stacked's float64 branch."""
+    dev, P = rs.device, rs.P
+    _check_out("out", out, torch.float64, P)
+    dst = out
+    if out is not None and rs.overlaps(out):
+        out = None
+    if out is None:
+        out = torch.empty(P, dtype=torch.float64, device=dev)
+    f = Factors(weights, scores, _F64, total=total)
+    a, s = f.to(dev)
+    aligned = rs.aligned and out.data_ptr() % 16 == 0
+    _lib.call("fa_fedavg_f64_ptrs", rs.ptrs.data_ptr(), rs.N, P, a.data_ptr(), _ptr(s), float(f.div), int(aligned),
+              out.data_ptr(), stream_ptr(dev))
+    stats["rows64_folds"] += 1
+    if dst is not None and dst is not out:
+        dst.reshape(-1)[:P].copy_(out)
+        return dst
+    return out
+
+
 def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
               out: Optional[torch.Tensor] = None, total=None, want_bf16: bool = False,
               out_bf16: Optional[torch.Tensor] = None):
     """The fold over separately allocated 1-D CUDA rows (no stacking copy for
-    fp32, bfloat16 and float16 rows whose result stays float16).  `rows` is a
+    fp32, bfloat16 and float16 / float64 rows whose result stays in their dtype).  `rows` is a
     RowSet (prepared once, reusable) or a sequence of tensors (a RowSet is
     built for this call).  want_bf16 / out_bf16: as fold_stacked (bf16 rows)."""
     rs = rows if isinstance(rows, RowSet) else RowSet(rows)
@@ -988,6 +1014,10 @@ def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
     if (rs.dtype == torch.float16 and rs.view is None and rs.P > 0
             and result_dtype(np.dtype(np.float16), weights, scores, total) == np.float16):
         return _fold_rows_f16(rs, weights, scores, out, total)
+    if (rs.dtype == torch.float64 and rs.view is None and rs.P > 0
+            and not torch.cuda.is_current_stream_capturing()  # captured float64 rows keep the stacked route
+            and result_dtype(_F64, weights, scores, total) == _F64):
+        return _fold_rows_f64(rs, weights, scores, out, total)
     fw = Factors.weak_f32(weights, scores, total) if rs.dtype == torch.float32 else None
     if fw is None and (rs.dtype != torch.float32
                        or result_dtype(np.dtype(np.float32), weights, scores, total) != np.float32):
@@ -1051,14 +1081,18 @@ def _rows_route(dt, fp32_result: bool, w, sc, total, where: torch.device, dev) -
     """Does a group of device layers of dtype dt fold per layer through
     fold_rows' row tables (no stacked copy)?  fp32 layers whose result stays
     fp32; bf16 layers (always float32 factors); float16 layers whose result
-    stays float16.  The 16-bit groups only where the layers already lie on the
-    device the fold was asked for (the stacked copy is what moves them)."""
+    stays float16; float64 layers whose result stays float64.  The 16-bit and
+    float64 groups only where the layers already lie on the device the fold
+    was asked for (the stacked copy is what moves them)."""
     if dt == torch.float32:
         return fp32_result
     d = torch.device(dev)
     here = where.type == d.type and where.index == (d.index if d.index is not None else torch.cuda.current_device())
     if dt == torch.bfloat16:
         return here
+    if dt == torch.float64:
+        return (here and not torch.cuda.is_current_stream_capturing()
+                and result_dtype(_F64, w, sc, total) == _F64)
     return dt == torch.float16 and here and result_dtype(np.dtype(np.float16), w, sc, total) == np.float16
 
 
@@ -1134,6 +1168,12 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
             # 2-byte rows, binary16 factors and the chunked binary16 fold
             # (fa_fold_f16), on one GPU
             res = _stream_group(parameters, n_eff, lis, P, w, sc, sum(total_weights), dev, np.float16)
+        elif (not on_device and P > 0 and dtypes[lis[0]] == np.float64 and f64_stream_enabled() and
+                result_dtype(_F64, total_weights, sc) == _F64):
+            # host float64 rows whose result stays float64: the same pipe with
+            # 8-byte rows, double factors and the chunked float64 fold
+            # (fa_fold_f64), on one GPU
+            res = _stream_group(parameters, n_eff, lis, P, w, sc, sum(total_weights), dev, np.float64)
         elif (not on_device and P > 0 and dtypes[lis[0]] == np.float32 and fp32_result):
             # host fp32 rows: pipelined pinned-chunk H2D + in-order chunked fold (bit-identical)
             if multi is not None:  # one column bucket per GPU, result assembled in pinned host memory
@@ -1147,8 +1187,8 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
         elif on_device and _rows_route(dtypes[lis[0]], fp32_result, w, sc, sum(total_weights),
                                        parameters[0][lis[0]].device, dev) and all(
                 parameters[i][li].is_contiguous() for i in range(n_eff) for li in lis):
-            # device fp32 / bf16 layers, and float16 layers whose result stays
-            # float16: fold each layer straight from the clients' own tensors
+            # device fp32 / bf16 layers, and float16 / float64 layers whose result
+            # stays in their dtype: fold each layer straight from the clients' own tensors
             # through a row-pointer list -- no stacking copy
             for li in lis:
                 rows = [parameters[i][li].reshape(-1) for i in range(n_eff)]
@@ -1187,19 +1227,28 @@ def f16_stream_enabled() -> bool:
     return os.environ.get("FEDAVG_F16_STREAM", "1") != "0"
 
 
-def _stream_dtype(layers) -> Optional[np.dtype]:
-    """The dtype a row streams in: float32 or float16 when every layer is a
-    numpy array of that one dtype; None otherwise (mixed or other dtypes)."""
+def f64_stream_enabled() -> bool:
+    """Host float64 rows stream through the ingest pipe unless
+    FEDAVG_F64_STREAM=0 (read per call), which keeps the materialised route:
+    every row stacked into one pinned matrix, one H2D, one fa_fedavg_f64."""
+    return os.environ.get("FEDAVG_F64_STREAM", "1") != "0"
+
+
+def _stream_dtype(layers, f64: bool = False) -> Optional[np.dtype]:
+    """The dtype a row streams in: float32 or float16 -- and, where the caller
+    has a float64 pipe to offer (f64: one GPU, FEDAVG_F64_STREAM not 0),
+    float64 -- when every layer is a numpy array of that one dtype; None
+    otherwise (mixed or other dtypes)."""
     dts = {x.dtype for x in layers if isinstance(x, np.ndarray)}
     if len(dts) != 1 or not all(isinstance(x, np.ndarray) for x in layers):
         return None
     dt = dts.pop()
-    return dt if dt in (np.float32, np.float16) else None
+    return dt if dt in (np.float32, np.float16) or (f64 and dt == np.float64) else None
 
 
 def _fast_row(layers, shapes, dtype=np.float32) -> bool:
     """A row the streaming path can take: numpy layers of `dtype` (row 0's:
-    float32 or float16) shaped like row 0."""
+    float32, float16 or float64) shaped like row 0."""
     return (len(layers) == len(shapes) and
             all(isinstance(x, np.ndarray) and x.dtype == dtype and x.shape == shp
                 for x, shp in zip(layers, shapes)))
@@ -1215,7 +1264,9 @@ def aggregate_decoded(items, scores: Optional[Sequence] = None, device: Optional
     pipelined StreamingFold as soon as it is decoded, so decoding row i+1
     overlaps the DMA of row i.  Same rows, same order, same factors: the result
     is bit-identical.  Rows whose layers are all float16 stream the same way
-    through a float16 pipe (one GPU; FEDAVG_F16_STREAM=0 turns that off).
+    through a float16 pipe (one GPU; FEDAVG_F16_STREAM=0 turns that off), and
+    rows whose layers are all float64 through a float64 pipe (one GPU;
+    FEDAVG_F64_STREAM=0 turns that off).
     Anything else (other or mixed dtypes, a row shaped or typed unlike row 0,
     weights that are not Python scalars, device tensors, nothing to fold)
     drains the iterator and runs aggregate_layers over every row, which is
@@ -1238,7 +1289,8 @@ def aggregate_decoded(items, scores: Optional[Sequence] = None, device: Optional
     rows, weights = [first[0]], [first[1]]
     shapes = [getattr(x, "shape", None) for x in first[0]]
     n_fold = len(scores) if scores is not None else None
-    dt = _stream_dtype(first[0]) if len(shapes) > 0 else None
+    # float64 rows stream on one GPU only, like float16 ones
+    dt = _stream_dtype(first[0], f64=multi is None and f64_stream_enabled()) if len(shapes) > 0 else None
     if dt == np.float16 and (multi is not None or not f16_stream_enabled()):
         dt = None  # float16 rows stream on one GPU only
     fast = (dt is not None and _fast_row(first[0], shapes, dt) and _py_scalar(first[1]) and

@@ -21,7 +21,10 @@ bandwidth, not PCIe, is the limit.
 float16 rows take the native pipe only (NativeStreamingFold(dtype=float16):
 2-byte rows, binary16 factors, a float16 accumulator, fa_fold_f16), bit-identical
 to one fa_fedavg_f16 over all rows (tests/test_gpu_f16_ingest.py); the
-Python-driven StreamingFold stays float32-only.
+Python-driven StreamingFold stays float32-only.  float64 rows take the native
+pipe the same way (NativeStreamingFold(dtype=float64): 8-byte rows, double
+factors, a float64 accumulator, fa_fold_f64), bit-identical to one
+fa_fedavg_f64 over all rows (tests/test_gpu_f64_ingest.py).
 
 Memory: `slots` pinned + `slots` device chunks of chunk_rows x P floats (2 by
 default; FEDAVG_STREAM_SLOTS overrides) and one [P] accumulator, independent of
@@ -246,8 +249,7 @@ class _PipeCache:
                 return p
         dev, P, chunk_bytes, slots, dtype = key
         h = ctypes.c_void_p()
-        _lib.call("fa_ingest_create_f16" if dtype == "float16" else "fa_ingest_create", ctypes.byref(h), P,
-                  chunk_bytes, slots, dev)
+        _lib.call("fa_ingest_create" + _KIND_SUFFIX[dtype], ctypes.byref(h), P, chunk_bytes, slots, dev)
         return h
 
     def put(self, key, pipe):
@@ -268,12 +270,22 @@ class _PipeCache:
 
 
 _pipes = _PipeCache()
+# the fa_ingest_* entries of a pipe's element kind, by dtype name
+_KIND_SUFFIX = {"float32": "", "float16": "_f16", "float64": "_f64"}
+_TORCH_DTYPE = {"float32": torch.float32, "float16": torch.float16, "float64": torch.float64}
 
 
 def _half_bits(v) -> int:
     """The binary16 bit pattern numpy rounds the scalar v to (round_scalars, as
     engine.Factors forms a float16 fold's factors and divisor; overflow gives inf)."""
     return int(round_scalars([v], np.float16).view(np.uint16)[0])
+
+
+def _double(v) -> float:
+    """The binary64 value numpy rounds the scalar v to (round_scalars, as
+    engine.Factors forms a float64 fold's factors: a Python int above 2**53
+    rounds to nearest even, one beyond the range raises OverflowError)."""
+    return float(round_scalars([v], np.float64)[0])
 
 
 class NativeStreamingFold:
@@ -284,11 +296,14 @@ class NativeStreamingFold:
     are queued and decoding the next row overlaps everything else.  The rows'
     arrays are kept alive until finish() (the workers read them).
 
-    dtype: float32 (default) or float16.  A float16 fold takes float16 rows,
+    dtype: float32 (default), float16 or float64.  A float16 fold takes float16 rows,
     keeps a float16 accumulator and rounds every factor and the divisor to
     binary16 with round_scalars, as engine.fold_stacked forms them for
     fa_fedavg_f16 (a factor that overflows stays inf), so the result is the
-    reference's own binary16 fold, bit for bit (fa_fold_f16)."""
+    reference's own binary16 fold, bit for bit (fa_fold_f16).  A float64 fold
+    takes float64 rows, keeps a float64 accumulator and forms every factor and
+    the divisor as engine.Factors(..., np.float64, total=...) does for
+    fa_fedavg_f64 (fold_stacked's float64 branch), folded by fa_fold_f64."""
 
     stats = {"rows": 0}
 
@@ -297,19 +312,23 @@ class NativeStreamingFold:
         if P <= 0:
             raise InvalidParameterShapeError("StreamingFold needs P > 0")
         self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.float32, np.float16):
-            raise InvalidParameterShapeError(f"StreamingFold takes float32 or float16 rows, not {self.dtype}")
+        if self.dtype not in (np.float32, np.float16, np.float64):
+            raise InvalidParameterShapeError(f"StreamingFold takes float32, float16 or float64 rows, not {self.dtype}")
         self.f16 = self.dtype == np.float16
+        self.f64 = self.dtype == np.float64
+        sfx = _KIND_SUFFIX[self.dtype.name]
         self.P = P
         self.dev = device or torch.device("cuda", torch.cuda.current_device())
         if self.dev.index is None:
             self.dev = torch.device("cuda", torch.cuda.current_device())
         self.key = (self.dev.index, P, int(chunk_bytes), int(slots), self.dtype.name)
         self.pipe = _pipes.get(self.key)
-        self.acc = torch.empty(P, dtype=torch.float16 if self.f16 else torch.float32, device=self.dev)
+        self.acc = torch.empty(P, dtype=_TORCH_DTYPE[self.dtype.name], device=self.dev)
         self.L = _lib.load()
+        self._add = getattr(self.L, "fa_ingest_add" + sfx)
+        self._finish = getattr(self.L, "fa_ingest_finish" + sfx)
         try:
-            begin = self.L.fa_ingest_begin_f16 if self.f16 else self.L.fa_ingest_begin
+            begin = getattr(self.L, "fa_ingest_begin" + sfx)
             _lib.check(begin(self.pipe, self.acc.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream,
                              max(0, int(expected_rows))), "fa_ingest_begin")
         except BaseException:
@@ -347,7 +366,15 @@ class NativeStreamingFold:
             except BaseException:
                 self._fail()
                 raise
-            rc = self.L.fa_ingest_add_f16(self.pipe, ptrs, sizes, n, a, s, 0 if score is None else 1)
+            rc = self._add(self.pipe, ptrs, sizes, n, a, s, 0 if score is None else 1)
+        elif self.f64:
+            try:  # fl64(n_i), fl64(score): the values Factors hands fa_fedavg_f64
+                a = _double(weight)
+                s = 1.0 if score is None else _double(score)
+            except BaseException:
+                self._fail()
+                raise
+            rc = self._add(self.pipe, ptrs, sizes, n, a, s, 0 if score is None else 1)
         else:
             a = float(np.float32(weight))  # fl32(n_i): numpy's rounding of the Python scalar
             s = 1.0 if score is None else float(np.float32(score))
@@ -376,7 +403,14 @@ class NativeStreamingFold:
             except BaseException:
                 self._fail()
                 raise
-            rc = self.L.fa_ingest_finish_f16(self.pipe, div)
+            rc = self._finish(self.pipe, div)
+        elif self.f64:
+            try:
+                div = float(np.float64(total))  # Factors.div of a float64 fold
+            except BaseException:
+                self._fail()
+                raise
+            rc = self._finish(self.pipe, div)
         else:
             rc = self.L.fa_ingest_finish(self.pipe, float(np.float32(total)))
         if rc:
@@ -429,10 +463,10 @@ def make_streaming_fold(P: int, device, chunk_bytes: int, direct: bool = False, 
     Python-driven StreamingFold for the direct-DMA route (page-locked
     documents) or when FEDAVG_NATIVE_INGEST=0.  expected_rows: the round's row
     count when the caller knows it (the native pipe then shrinks its last
-    chunks).  dtype float16 always takes the native pipe: the Python-driven
-    StreamingFold is float32-only."""
-    if np.dtype(dtype) == np.float16:
-        return NativeStreamingFold(P, device, chunk_bytes, STREAM_SLOTS or 3, expected_rows, dtype=np.float16)
+    chunks).  dtype float16 or float64 always takes the native pipe: the
+    Python-driven StreamingFold is float32-only."""
+    if np.dtype(dtype) in (np.float16, np.float64):
+        return NativeStreamingFold(P, device, chunk_bytes, STREAM_SLOTS or 3, expected_rows, dtype=np.dtype(dtype))
     if NATIVE_INGEST and not direct:
         return NativeStreamingFold(P, device, chunk_bytes, STREAM_SLOTS or 3, expected_rows)
     return StreamingFold(P, chunk_rows=max(1, chunk_bytes // (4 * P)), device=device, direct=direct,

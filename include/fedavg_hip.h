@@ -418,6 +418,44 @@ int fa_fedavg_f64(const double* X, int64_t N, int64_t P, int64_t ldx,
                   const double* a, const double* s, double divisor,
                   double* out, void* stream);
 
+/* Chunked binary64 fold (new symbol, ABI still 7): fa_fold_f32's contract in
+ * the arithmetic of fa_fedavg_f64, the building block of streaming ingest for
+ * float64 models (numpy's default dtype; the reference's aggregate() on
+ * float64 results, fed_avg_aggregator.py:57-92,
+ * stall_aware_aggregation.py:82-117, and its own unit-test fixture,
+ * test/test_aggregation.py:23-38):
+ *   t_i = fl64(fl64(x_i * a_i) * s_i)       (s == NULL: t_i = fl64(x_i * a_i)); no FMA
+ *   acc_in == NULL : acc = t_0 (not 0 + t_0: a column of -0.0 stays -0.0)
+ *   acc_in != NULL : acc = fl64(acc_in[p] + t_0), then t_1, ... in row order
+ *   finalize != 0  : out = fl64(acc / divisor), the IEEE divide, no reciprocal;
+ *                    else out = acc
+ *   N == 0 with acc_in: only the divide (or, without finalize, a copy)
+ * acc_in may alias out.  Subnormals are kept, NaN by position.  Every add
+ * rounds to binary64 already, so folding the rows in any cuts is bit-identical
+ * to one fa_fedavg_f64 over all of them.  Argument checks and status codes as
+ * fa_fedavg_f64 (N == 0 without acc_in -> FA_ERR_NO_CLIENTS).  One form fixed
+ * by shape (4, 2 or 1 pairs of columns per lane by width, 4 rows ahead,
+ * balanced grid-stride passes over at most one block per CU); X, acc_in or out
+ * off 16-B alignment or an odd ldx: one column per lane. */
+int fa_fold_f64(const double* X, int64_t N, int64_t P, int64_t ldx,
+                const double* a, const double* s, const double* acc_in,
+                double divisor, int finalize, double* out, void* stream);
+
+/* The float64 fold over N separately allocated client rows (new symbol, ABI
+ * still 7): xi is a [device] array of N [device] pointers, each to P doubles --
+ * the list-of-arrays form the reference passes (fed_avg_aggregator.py:32-35),
+ * folded where the rows lie, with no stacking copy.  rows_aligned != 0 is the
+ * caller's promise that every row and out are 16-B aligned and takes the pair
+ * kernel (a fixed form per shape, 8 rows ahead); with 0 rows and out may sit
+ * at any 8-B offset and one lane folds a column.  Bit for bit the result of
+ * fa_fedavg_f64 over the same rows stacked, with either kernel.  Argument
+ * checks and status codes as fa_fedavg_f16_ptrs (rows_aligned != 0 with out
+ * off 16-B alignment -> FA_ERR_ARG).  The table lives in device memory, so
+ * the library cannot see an alias: out may not overlap a row. */
+int fa_fedavg_f64_ptrs(const double* const* xi, int64_t N, int64_t P,
+                       const double* a, const double* s, double divisor, int rows_aligned,
+                       double* out, void* stream);
+
 /* Integer updates: numpy keeps `layer * n` and the np.add fold in the integer
  * dtype (wrapping) and true-divides into float64 (fed_avg_aggregator.py:33,39).
  * a = integer cardinalities [device, int64]; out float64. */
@@ -509,6 +547,25 @@ int fa_ingest_begin_f16(fa_ingest* pipe, uint16_t* acc, void* stream, int64_t ex
 int fa_ingest_add_f16(fa_ingest* pipe, const void* const* srcs, const int64_t* sizes, int64_t n, uint16_t a,
                       uint16_t s, int has_s);
 int fa_ingest_finish_f16(fa_ingest* pipe, uint16_t divisor);
+/* The same pipe for float64 models (new symbols, ABI still 7): numpy's default
+ * dtype, the reference's own aggregation fixture (test/test_aggregation.py:
+ * 23-38) and what its aggregate() folds float64 results in
+ * (fed_avg_aggregator.py:57-92, stall_aware_aggregation.py:82-117).  A pipe
+ * created with fa_ingest_create_f64 takes rows of P doubles (pitch P rounded
+ * up to 64 doubles, chunk_bytes / (pitch * 8) rows per chunk), the factors
+ * a = fl64(n_i), s = fl64(score) and the divisor as doubles, keeps its factor
+ * block in doubles ahead of the rows in the chunk's one DMA (padded to 256 B)
+ * and folds into acc [device, P doubles] with fa_fold_f64: bit-identical to
+ * fa_fedavg_f64 over all rows.  Pieces of a row are copied bytewise and may
+ * start at any byte offset (views into NPZ blobs).  Ramps, the halving tail,
+ * abandon and reuse, and the error paths are those of the float32 pipe; an
+ * entry of one kind on a pipe of another returns FA_ERR_ARG and leaves the
+ * pipe as it was. */
+int fa_ingest_create_f64(fa_ingest** pipe, int64_t P, int64_t chunk_bytes, int slots, int device);
+int fa_ingest_begin_f64(fa_ingest* pipe, double* acc, void* stream, int64_t expected_rows);
+int fa_ingest_add_f64(fa_ingest* pipe, const void* const* srcs, const int64_t* sizes, int64_t n, double a,
+                      double s, int has_s);
+int fa_ingest_finish_f64(fa_ingest* pipe, double divisor);
 
 /* ---- host-side ingest (no GPU): NPZ wire format -> pinned staging ----------
  * Client blobs are uncompressed NPZ archives (NpzWeightsSerializer,

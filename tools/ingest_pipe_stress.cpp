@@ -9,7 +9,9 @@
 // destroy with copies possibly in flight, and finish with no rows.
 // float16 pipes (the *_f16 entries) run the same way against a CPU restatement
 // of fa_fold_f16: plain and scored rounds, an abandoned round then a reused
-// pipe, and calls of the wrong element kind.
+// pipe, and calls of the wrong element kind.  float64 pipes (the *_f64
+// entries) likewise against a CPU restatement of fa_fold_f64, with rows handed
+// over as pieces at odd byte offsets (the pack is bytewise).
 //   tools/ingest_pipe_stress.sh   (builds with -fsanitize=thread, then address,undefined)
 #include <stdint.h>
 #include <stdio.h>
@@ -122,6 +124,30 @@ extern "C" int fa_fold_f16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
             acc = hadd(acc, t);
         }
         out[p] = finalize ? hdiv(acc, divisor) : acc;
+    }
+    return FA_OK;
+}
+
+// CPU restatement of fa_fold_f64 (fedavg_hip.h): binary64 products, sums and quotient in row order
+extern "C" int fa_fold_f64(const double* X, int64_t N, int64_t P, int64_t ldx, const double* a, const double* s,
+                           const double* acc_in, double divisor, int finalize, double* out, void*) {
+    if (N == 0 && !acc_in) return fa_internal_fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
+    for (int64_t p = 0; p < P; ++p) {
+        double acc;
+        int64_t i = 0;
+        if (acc_in) {
+            acc = acc_in[p];
+        } else {
+            acc = X[p] * a[0];
+            if (s) acc = acc * s[0];
+            i = 1;
+        }
+        for (; i < N; ++i) {
+            double t = X[i * ldx + p] * a[i];
+            if (s) t = t * s[i];
+            acc = acc + t;
+        }
+        out[p] = finalize ? acc / divisor : acc;
     }
     return FA_OK;
 }
@@ -297,6 +323,98 @@ static void worker_f16(int tid, int rounds) {
     }
 }
 
+// float64 rounds: plain and scored (pipe reused), an abandoned round then a
+// clean one, wrong-kind calls on every pair of kinds.  The rows live in a byte
+// buffer at an odd offset, as views into an NPZ blob do.
+static void worker_f64(int tid, int rounds) {
+    std::mt19937_64 rng(8642 + tid);
+    for (int r = 0; r < rounds; ++r) {
+        const int64_t P = 1 + rng() % 40000;
+        const int64_t N = 1 + rng() % 33;
+        const int slots = 2 + rng() % 5;
+        const int64_t ldx = (P + 63) / 64 * 64;
+        const int64_t chunk = ldx * 8 * (1 + rng() % 6);
+        std::vector<double> X(N * P), a(N), s(N);
+        for (auto& v : X) v = (double)((int64_t)(rng() % 2000001) - 1000000) / 3.0;  // low mantissa bits filled
+        double total = 0.0;
+        for (int64_t i = 0; i < N; ++i) {
+            a[i] = (double)(1 + rng() % 600);
+            total += a[i];
+            s[i] = (double)(1 + rng() % 11) / 11.0;
+        }
+        const int64_t shift = 1 + rng() % 7;  // the rows' byte offset inside the blob: never 8-B aligned
+        std::vector<uint8_t> blob((size_t)(N * P * 8 + 8));
+        memcpy(blob.data() + shift, X.data(), (size_t)(N * P * 8));
+        fa_ingest* pipe = nullptr;
+        check(fa_ingest_create_f64(&pipe, P, chunk, slots, tid % 2) == FA_OK, "create f64");
+        check(fa_ingest_rows_per_chunk(pipe) == (int)(chunk / (ldx * 8)), "rows per chunk f64");
+        std::vector<double> acc(P, -1.0), exp(P);
+        for (int rep = 0; rep < 2; ++rep) {  // plain, then scored, on the same pipe
+            const bool scored = rep == 1;
+            const int64_t guess[4] = {0, N, N + 3, N > 2 ? N - 2 : 1};
+            check(fa_ingest_begin_f64(pipe, acc.data(), nullptr, guess[rng() % 4]) == FA_OK, "begin f64");
+            for (int64_t i = 0; i < N; ++i) {
+                // the row in 1-4 pieces of any number of bytes (a double may straddle two pieces)
+                std::vector<const void*> src;
+                std::vector<int64_t> sz;
+                int64_t off = 0;
+                const int parts = 1 + rng() % 4;
+                for (int k = 0; k < parts; ++k) {
+                    const int64_t len = k == parts - 1 ? P * 8 - off : (P * 8 - off) * (int64_t)(rng() % 100) / 100;
+                    src.push_back(blob.data() + shift + i * P * 8 + off);
+                    sz.push_back(len);
+                    off += len;
+                }
+                check(fa_ingest_add_f64(pipe, src.data(), sz.data(), (int64_t)src.size(), a[i], s[i], scored) == FA_OK,
+                      "add f64");
+            }
+            check(fa_ingest_finish_f64(pipe, total) == FA_OK, "finish f64");
+            fa_fold_f64(X.data(), N, P, P, a.data(), scored ? s.data() : nullptr, nullptr, total, 1, exp.data(),
+                        nullptr);
+            check(memcmp(exp.data(), acc.data(), P * 8) == 0, "bit-exact f64");
+        }
+        // wrong-kind calls: refused, and the pipe is left as it was
+        const void* src0 = blob.data() + shift;
+        int64_t full = P * 8, shortb = (P - 1) * 8;
+        std::vector<float> acc32(P);
+        std::vector<uint16_t> acc16(P);
+        check(fa_ingest_begin(pipe, acc32.data(), nullptr, 0) == FA_ERR_ARG, "f32 begin on an f64 pipe");
+        check(fa_ingest_begin_f16(pipe, acc16.data(), nullptr, 0) == FA_ERR_ARG, "f16 begin on an f64 pipe");
+        check(fa_ingest_begin_f64(pipe, acc.data(), nullptr, 0) == FA_OK, "begin f64 2");
+        check(fa_ingest_add(pipe, &src0, &full, 1, 1.f, 1.f, 0) == FA_ERR_ARG, "f32 add on an f64 pipe");
+        check(fa_ingest_add_f16(pipe, &src0, &full, 1, 0x3C00, 0x3C00, 0) == FA_ERR_ARG, "f16 add on an f64 pipe");
+        check(fa_ingest_finish(pipe, 1.f) == FA_ERR_ARG, "f32 finish on an f64 pipe");
+        check(fa_ingest_finish_f16(pipe, 0x3C00) == FA_ERR_ARG, "f16 finish on an f64 pipe");
+        // errors mid-round, a chunk half filled, then the pipe reused: the abandoned rows do not join
+        check(fa_ingest_add_f64(pipe, &src0, &full, 1, 1.0, 1.0, 0) == FA_OK, "add f64 ok");
+        check(fa_ingest_add_f64(pipe, &src0, &shortb, 1, 1.0, 1.0, 0) == FA_ERR_SHAPE, "short f64 row rejected");
+        check(fa_ingest_add_f64(pipe, &src0, &full, 1, 1.0, 0.5, 1) == FA_ERR_SHAPE, "mixed scores rejected f64");
+        check(fa_ingest_add_f64(pipe, &src0, &full, 1, 7.0, 1.0, 0) == FA_OK, "add f64 ok 2");
+        check(fa_ingest_begin_f64(pipe, acc.data(), nullptr, 0) == FA_OK, "begin f64 after an abandoned round");
+        for (int64_t i = 0; i < N; ++i) {
+            const void* src = blob.data() + shift + i * P * 8;
+            check(fa_ingest_add_f64(pipe, &src, &full, 1, a[i], s[i], 0) == FA_OK, "add f64 after abandon");
+        }
+        check(fa_ingest_finish_f64(pipe, total) == FA_OK, "finish f64 after abandon");
+        fa_fold_f64(X.data(), N, P, P, a.data(), nullptr, nullptr, total, 1, exp.data(), nullptr);
+        check(memcmp(exp.data(), acc.data(), P * 8) == 0, "bit-exact f64 after an abandoned round");
+        fa_ingest_destroy(pipe);
+        // the reverse: f64 entries on a float32 and on a float16 pipe
+        fa_ingest* other[2] = {nullptr, nullptr};
+        check(fa_ingest_create(&other[0], P, chunk, slots, 0) == FA_OK, "create f32");
+        check(fa_ingest_create_f16(&other[1], P, chunk, slots, 0) == FA_OK, "create f16");
+        for (fa_ingest* q : other) {
+            check(fa_ingest_begin_f64(q, acc.data(), nullptr, 0) == FA_ERR_ARG, "f64 begin on another pipe");
+            check(fa_ingest_add_f64(q, &src0, &full, 1, 1.0, 1.0, 0) == FA_ERR_ARG, "f64 add on another pipe");
+            check(fa_ingest_finish_f64(q, 1.0) == FA_ERR_ARG, "f64 finish on another pipe");
+        }
+        check(fa_ingest_begin(other[0], acc32.data(), nullptr, 0) == FA_OK, "begin f32 after refused calls");
+        check(fa_ingest_finish(other[0], 1.f) == FA_ERR_NO_CLIENTS, "empty f32 round after refused calls");
+        fa_ingest_destroy(other[0]);
+        fa_ingest_destroy(other[1]);
+    }
+}
+
 // f2h / h2f against a few known patterns (the restated fold rests on them)
 static void check_half() {
     check(f2h(1.0f) == 0x3C00 && f2h(-2.0f) == 0xC000 && f2h(65504.f) == 0x7BFF, "f2h normals");
@@ -317,6 +435,7 @@ int main() {
     std::vector<std::thread> ts;
     for (int t = 0; t < 3; ++t) ts.emplace_back(worker, t, 12);
     for (int t = 0; t < 2; ++t) ts.emplace_back(worker_f16, t, 8);
+    for (int t = 0; t < 2; ++t) ts.emplace_back(worker_f64, t, 8);
     for (auto& t : ts) t.join();
     if (g_fail.load()) {
         fprintf(stderr, "%d failures\n", g_fail.load());
