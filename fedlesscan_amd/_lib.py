@@ -70,6 +70,8 @@ _PROTOS = {
     "fa_rounds_form": (ctypes.c_char_p, [_int]),
     "fa_fedavg_f16_rounds": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, ctypes.c_uint16, _vp, _int, _vp, _vp, _vp]),
     "fa_rounds_form_f16": (ctypes.c_char_p, []),
+    "fa_fedavg_f64_rounds": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _f64, _vp, _int, _vp, _vp, _vp]),
+    "fa_rounds_form_f64": (ctypes.c_char_p, []),
     "fa_peers_create": (_int, [_vp, _int, _int, _int, _i64]),
     "fa_peers_destroy": (_int, [_vp]),
     "fa_peers_handle_bytes": (_int, []),
@@ -160,6 +162,9 @@ _BENCH_PROTOS = {
     "fa_step_form_name_f16": (ctypes.c_char_p, [_int]),
     "fa_fedavg_f16_rounds_form": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, ctypes.c_uint16, _vp, _int, _vp, _vp,
                                          _vp]),
+    "fa_num_step_forms_f64": (_int, []),
+    "fa_step_form_name_f64": (ctypes.c_char_p, [_int]),
+    "fa_fedavg_f64_rounds_form": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _f64, _vp, _int, _vp, _vp, _vp]),
     "fa_bench_rounds_set_sys": (_int, [_vp, _int]),
     "fa_num_ptrs_variants": (_int, []),
     "fa_ptrs_variant_name": (ctypes.c_char_p, [_int]),

@@ -326,6 +326,17 @@ int fa_fedavg_f16_rounds(fa_rounds* r, const uint16_t* X, int64_t N, int64_t ldx
 
 const char* fa_rounds_form_f16(void) { return step_form_name_f16(pick_step_f16()); }
 
+int fa_fedavg_f64_rounds(fa_rounds* r, const double* X, int64_t N, int64_t ldx, const double* a, const double* s,
+                         double divisor, double* out, int rounds, const int64_t* offsets,
+                         const int64_t* out_offsets, void* stream) {
+    if (!r) return fail(FA_ERR_ARG, "null fa_rounds");
+    StreamDevice on_stream_device(stream);
+    return launch_step_f64(*r, pick_step_f64(), (hipStream_t)stream, X, N, ldx, a, s, divisor, out, rounds, offsets,
+                           out_offsets);
+}
+
+const char* fa_rounds_form_f64(void) { return step_form_name_f64(pick_step_f64()); }
+
 int fa_rounds_wait(fa_rounds* r, int round, void* stream) {
     if (!r) return fail(FA_ERR_ARG, "null fa_rounds");
     StreamDevice on_stream_device(stream);

@@ -569,6 +569,17 @@ int fa_fedavg_f16_rounds_form(void* r, int form, const uint16_t* X, int64_t N, i
                            rounds, offsets, out_offsets);
 }
 
+int fa_num_step_forms_f64(void) { return kNumStepFormsF64; }
+const char* fa_step_form_name_f64(int form) { return step_form_name_f64(form); }
+int fa_fedavg_f64_rounds_form(void* r, int form, const double* X, int64_t N, int64_t ldx, const double* a,
+                              const double* s, double divisor, double* out, int rounds, const int64_t* offsets,
+                              const int64_t* out_offsets, void* stream) {
+    if (!r) return fail(FA_ERR_ARG, "null rounds state");
+    StreamDevice on_stream_device(stream);
+    return launch_step_f64(*static_cast<RoundsState*>(r), form, (hipStream_t)stream, X, N, ldx, a, s, divisor, out,
+                           rounds, offsets, out_offsets);
+}
+
 int fa_bench_rounds_wait(void* r, int round, void* stream) {
     RoundsState* o = static_cast<RoundsState*>(r);
     if (!o) return fail(FA_ERR_ARG, "null rounds state");

@@ -2396,11 +2396,16 @@ __device__ __forceinline__ double fold_column_f64(Rows src, int64_t N, const dou
 }
 
 // The float64 pair fold: the lane's C pairs of the rows of src, in row order;
-// acc_in and out point at the lane's first pair.
-template <int U, int C, bool SCORED, bool ACC, bool FIN, class Rows>
+// acc_in and out point at the lane's first pair.  WT (the one-launch step,
+// final results only): the quotient pairs stored write-through over the
+// tile's wave-uniform base, as fold_octets_f16 stores its octets -- no
+// non-temporal store there (no valid producer form for a round another stream
+// reads).
+template <int U, int C, bool SCORED, bool ACC, bool FIN, int WT = 0, class Rows>
 __device__ __forceinline__ void fold_pairs_f64(Rows src, int64_t N, const double* __restrict__ a,
                                                const double* __restrict__ s, const f64x2* acc_in, double divisor,
                                                f64x2* out) {
+    static_assert(!WT || (!ACC && FIN), "write-through stores are for final results");
     f64x2 acc[C];
     int64_t i = 0;
     if constexpr (ACC) {
@@ -2434,13 +2439,22 @@ __device__ __forceinline__ void fold_pairs_f64(Rows src, int64_t N, const double
 #pragma unroll
         for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_d2<SCORED>(__builtin_nontemporal_load(r + c * kBlock), ai, si);
     }
+    if constexpr (WT) {  // the base: the tile's first pair (out - threadIdx.x, shared by every lane)
+        const __amdgpu_buffer_rsrc_t rs = wt_rsrc(reinterpret_cast<const void*>(
+            (uintptr_t)uniform64((int64_t)(uintptr_t)(out - threadIdx.x))));
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            st16_wt<WT>(rs, (int)(16 * ((int)threadIdx.x + c * kBlock)),
+                        __builtin_bit_cast(u32x4, f64x2(acc[c] / divisor)));
+        return;
+    }
 #pragma unroll
     for (int c = 0; c < C; ++c) st_d2<FIN>(out + c * kBlock, acc[c], divisor);
 }
 
 // One pair tile of a stacked float64 matrix (acc_in may alias out): the tiling
 // of octet_tile with pairs in place of octets
-template <int U, int C, bool SCORED, bool ACC, bool FIN>
+template <int U, int C, bool SCORED, bool ACC, bool FIN, int WT = 0>
 __device__ __forceinline__ void f64_tile(int64_t bid, const double* __restrict__ X, int64_t N, int64_t P,
                                          int64_t ldx, const double* __restrict__ a, const double* __restrict__ s,
                                          const double* acc_in, double divisor, double* out) {
@@ -2451,16 +2465,18 @@ __device__ __forceinline__ void f64_tile(int64_t bid, const double* __restrict__
     octet_tile<C, kBlock, 1>(
         bid, P,
         [&](int64_t o) {
-            fold_pairs_f64<U, C, SCORED, ACC, FIN>(PitchedRows<f64x2>{X2 + o, ldp}, N, a, s, ACC ? A2 + o : nullptr,
-                                                   divisor, O2 + o);
+            fold_pairs_f64<U, C, SCORED, ACC, FIN, WT>(PitchedRows<f64x2>{X2 + o, ldp}, N, a, s,
+                                                       ACC ? A2 + o : nullptr, divisor, O2 + o);
         },
         [&](int64_t o) {
-            fold_pairs_f64<U, 1, SCORED, ACC, FIN>(PitchedRows<f64x2>{X2 + o, ldp}, N, a, s, ACC ? A2 + o : nullptr,
-                                                   divisor, O2 + o);
+            fold_pairs_f64<U, 1, SCORED, ACC, FIN, WT>(PitchedRows<f64x2>{X2 + o, ldp}, N, a, s,
+                                                       ACC ? A2 + o : nullptr, divisor, O2 + o);
         },
         [&](int64_t col) {  // the P % 2 column
             out[col] = fold_column_f64<SCORED, ACC, FIN>(PitchedRows<double>{X + col, ldx}, N, a, s,
                                                          ACC ? acc_in + col : nullptr, divisor);
+            // WT: this one plain store is written back before the block publishes
+            wt_tail_release<WT>();
         });
 }
 
@@ -2473,6 +2489,34 @@ __global__ __launch_bounds__(kBlock) void k_fold_f64_gs(
     const double* acc_in, double divisor, double* out, int64_t ntiles) {  // acc_in may alias out
     for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
         f64_tile<U, C, SCORED, ACC, FIN>(bid, X, N, P, ldx, a, s, acc_in, divisor, out);
+}
+
+// The float64 step: the schedules of k_fedavg_f16_step over the float64 pair
+// tile (double products, ordered double sums, the IEEE double divide: the bits
+// of fa_fedavg_f64 on each round's columns), every quotient pair stored
+// write-through; agent scope only.
+template <int UB, int CB, int US, int CS, bool SCORED, int B, bool BAL = false, int WTM = kWtAgent>
+__global__ __launch_bounds__(B) void k_fedavg_f64_step(
+    const double* __restrict__ X, int64_t N, int64_t ldx, const double* __restrict__ a,
+    const double* __restrict__ s, double divisor, double* __restrict__ out, StepTable T, unsigned int* sig,
+    unsigned int epoch) {
+    static_assert(B == kBlock, "pair tiles are kBlock lanes wide");
+    auto wide = [&](int g, int64_t bid) {
+        f64_tile<UB, CB, SCORED, false, true, WTM>(bid, X + T.col0[g], N, T.width[g], ldx, a, s, nullptr, divisor,
+                                                   out + T.ocol0[g]);
+    };
+    auto narrow = [&](int g, int64_t bid) {
+        f64_tile<US, CS, SCORED, false, true, WTM>(bid, X + T.col0[g], N, T.width[g], ldx, a, s, nullptr, divisor,
+                                                   out + T.ocol0[g]);
+    };
+    if constexpr (BAL) {
+        step_tiles_bal(T, sig, epoch, wide, narrow);
+    } else {
+        step_tiles(T, sig, epoch, [&](int g, int64_t bid) {
+            if (T.small[g]) narrow(g, bid);
+            else wide(g, bid);
+        });
+    }
 }
 
 // chunked fold, one column per lane: rows, accumulator or output at any 8-B
@@ -3005,7 +3049,10 @@ struct StepSpec {
     bool round_tail = false;  // each round but the last: whole passes of wide tiles, the rest in narrow static tiles
     bool bal = false;         // balanced rounds: each round's wide tiles over its own balanced block count
     bool f16 = false;         // float16 rows, factors and result (kStepSpecsF16); bf16 is false there
-    constexpr bool octets() const { return bf16 || f16; }  // 8 columns per 16-byte unit (fp32: 4)
+    bool f64 = false;         // float64 rows, factors and result (kStepSpecsF64); bf16 and f16 are false there
+    constexpr bool octets() const { return bf16 || f16; }  // 16-bit elements
+    // columns per 16-byte unit: an octet of 16-bit elements, a quad of fp32, a pair of float64
+    constexpr int ucols() const { return octets() ? 8 : f64 ? 2 : 4; }
 };
 // The policy's two forms and one comparison form per dtype beside the round-4
 // bf16 policy (the bench library and the GPU tests run every one).  Round 4
@@ -3070,6 +3117,28 @@ inline int pick_step_f16() {
     static_assert(name_eq(kStepSpecsF16[0].name, "f16_step_bal_u8c4"), "policy step form");
     return 0;
 }
+// The float64 step's forms, in a table of their own.  A float64 column has
+// twice an fp32 column's bytes in and out at the same client count, so the
+// forms are the fp32 step's geometries over pairs; agent scope only (no peer
+// exchange for float64):
+//   f64_step_bal_u8c4      each round's 8 x 4-pair tiles over its own balanced
+//     block count, no dynamic pool
+//   f64_step_sd_u8c4_p75   the fp32 policy's geometry: 8 x 4-pair static tiles
+//     and a 0.75-pass pool of 16 x 1-pair tiles
+//   f64_step_static_u8c4   comparison: every tile static
+// The policy (pick_step_f64): whichever of the first two measured faster by
+// more than the other's spread, else the balanced form.
+constexpr StepSpec kStepSpecsF64[] = {
+    {"f64_step_bal_u8c4", false, 8, 4, 8, 2, 0, true, false, true, false, true},
+    {"f64_step_sd_u8c4_p75", false, 8, 4, 16, 1, 75, false, false, false, false, true},
+    {"f64_step_static_u8c4", false, 8, 4, 8, 4, 0, false, false, false, false, true},
+};
+constexpr int kNumStepFormsF64 = (int)(sizeof(kStepSpecsF64) / sizeof(kStepSpecsF64[0]));
+inline const char* step_form_name_f64(int f) { return (f >= 0 && f < kNumStepFormsF64) ? kStepSpecsF64[f].name : ""; }
+inline int pick_step_f64() {
+    static_assert(name_eq(kStepSpecsF64[0].name, "f64_step_bal_u8c4"), "policy step form");
+    return 0;
+}
 
 // The per-launch state of fa_fedavg_*_rounds: the signal words in device
 // memory, the waiters' timeout record in mapped host memory and the host
@@ -3105,7 +3174,7 @@ struct RoundsState {
 // from the last round) in narrow tiles.  FA status.
 inline int build_step_table(const StepSpec& sp, int rounds, const int64_t* offsets, const int64_t* out_offsets,
                             int64_t ldx, int64_t grid, StepTable& T) {
-    const int64_t ucols = sp.octets() ? 8 : 4;  // columns per octet / quad
+    const int64_t ucols = sp.ucols();  // columns per octet / quad / pair
     const int64_t wide_cols = (int64_t)kBlock * sp.cb * ucols;
     T = StepTable{};
     T.rounds = rounds;
@@ -3125,7 +3194,7 @@ inline int build_step_table(const StepSpec& sp, int rounds, const int64_t* offse
         split[k] = ((w - pool) / wide_cols) * wide_cols;  // the static part ends on a wide-tile boundary
         pool = 0;
     }
-    auto units = [&](int64_t w) { return sp.octets() ? (w >> 3) + ((w & 7) ? 1 : 0) : (w >> 2) + ((w & 3) ? 1 : 0); };
+    auto units = [&](int64_t w) { return (w + ucols - 1) / ucols; };
     int64_t total = 0;
     // static segments first (all of them precede every dynamic one in column
     // order: only a suffix of the step is dynamic), then the dynamic ones
@@ -3257,19 +3326,24 @@ inline int rounds_check(RoundsState& o) {
 // start / done events, the gate wait, the capture refusal, the argument
 // checks).  fp32 and bf16 forms take float32 factors and write out (float32)
 // and / or outb; float16 forms (sp.f16) take binary16 factors and write out as
-// halves, the divisor the half's exact float32 value.
+// halves, the divisor the half's exact float32 value; float64 forms (sp.f64)
+// take double factors and write out as doubles, the divisor ddivisor (the
+// other forms never read it, nor the float64 ones divisor).
 inline int launch_step_spec(RoundsState& R, const StepSpec& sp, hipStream_t st, const void* X, int64_t N,
                             int64_t ldx, const void* a, const void* s, float divisor, void* out, uint16_t* outb,
-                            int rounds, const int64_t* offsets, const int64_t* out_offsets) {
+                            int rounds, const int64_t* offsets, const int64_t* out_offsets, double ddivisor = 0.0) {
     R.launched = false;
     if (rounds < 1 || rounds > kMaxRounds || !offsets) return fail(FA_ERR_ARG, "rounds must be 1..%d", kMaxRounds);
-    const int64_t col_align = sp.octets() ? 8 : 4;
-    // fp32 and float16 rows write out; bf16 rows out and/or outb (ABI 5: out may be null)
+    const int64_t col_align = sp.ucols();
+    // fp32, float16 and float64 rows write out; bf16 rows out and/or outb (ABI 5: out may be null)
     if (!X || !a || N < 1 || (sp.bf16 ? (!out && !outb) : !out))
         return fail(FA_ERR_ARG, sp.bf16 ? "null X/a, no output (out_f32 and out_bf16 both null) or N < 1"
                                         : "null X/a/out or N < 1");
     if (ldx % col_align || !aligned16(X) || !aligned16(out) || (outb && !aligned16(outb)))
         return fail(FA_ERR_ARG, "rounds fold needs 16-B aligned X/out and ldx %% %lld == 0", (long long)col_align);
+    if (sp.f64 && R.sys)
+        return fail(FA_ERR_ARG, "step form %s: float64 rounds are published at agent scope (not a peer exchange's state)",
+                    sp.name);
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
         (void)hipGetLastError();
@@ -3300,6 +3374,9 @@ inline int launch_step_spec(RoundsState& R, const StepSpec& sp, hipStream_t st, 
     const uint16_t *ah = static_cast<const uint16_t*>(a), *sh = static_cast<const uint16_t*>(s);
     float* outf = static_cast<float*>(out);
     uint16_t* outh = static_cast<uint16_t*>(out);
+    const double* Xd = static_cast<const double*>(X);
+    const double *ad = static_cast<const double*>(a), *sd = static_cast<const double*>(s);
+    double* outd = static_cast<double*>(out);
     // the kernel instantiation is found from the form's tile shapes (never by
     // its index): a form whose shapes no instantiation below has is refused
     bool launched = false;
@@ -3316,7 +3393,7 @@ inline int launch_step_spec(RoundsState& R, const StepSpec& sp, hipStream_t st, 
                                R.sig, epoch);                                                                    \
     }
 #define FA_STF(UB, CB, US, CS, BAL, WTM)                                                                         \
-    if (!launched && !sp.octets() && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS && sp.bal == BAL && \
+    if (!launched && !sp.octets() && !sp.f64 && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS && sp.bal == BAL && \
         wtm == WTM) {                                                                                            \
         launched = true;                                                                                         \
         if (s)                                                                                                   \
@@ -3337,6 +3414,17 @@ inline int launch_step_spec(RoundsState& R, const StepSpec& sp, hipStream_t st, 
             hipLaunchKernelGGL((k_fedavg_f16_step<UB, CB, US, CS, false, kBlock, BAL, WTM>), dim3((unsigned)grid), \
                                dim3(kBlock), 0, st, Xb, N, ldx, ah, sh, divisor, outh, T, R.sig, epoch);         \
     }
+#define FA_STD(UB, CB, US, CS, BAL, WTM)                                                                         \
+    if (!launched && sp.f64 && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS && sp.bal == BAL &&      \
+        wtm == WTM) {                                                                                            \
+        launched = true;                                                                                         \
+        if (s)                                                                                                   \
+            hipLaunchKernelGGL((k_fedavg_f64_step<UB, CB, US, CS, true, kBlock, BAL, WTM>), dim3((unsigned)grid), \
+                               dim3(kBlock), 0, st, Xd, N, ldx, ad, sd, ddivisor, outd, T, R.sig, epoch);        \
+        else                                                                                                     \
+            hipLaunchKernelGGL((k_fedavg_f64_step<UB, CB, US, CS, false, kBlock, BAL, WTM>), dim3((unsigned)grid), \
+                               dim3(kBlock), 0, st, Xd, N, ldx, ad, sd, ddivisor, outd, T, R.sig, epoch);        \
+    }
     FA_STB(8, 4, 8, 2, false, kWtAgent)
     FA_STB(8, 4, 8, 4, false, kWtAgent)
     FA_STB(8, 4, 8, 2, true, kWtAgent)
@@ -3348,6 +3436,11 @@ inline int launch_step_spec(RoundsState& R, const StepSpec& sp, hipStream_t st, 
     // float16: agent scope only
     FA_STH(8, 4, 8, 2, true, kWtAgent)
     FA_STH(8, 4, 8, 4, false, kWtAgent)
+    // float64: agent scope only
+    FA_STD(8, 4, 8, 2, true, kWtAgent)
+    FA_STD(8, 4, 16, 1, false, kWtAgent)
+    FA_STD(8, 4, 8, 4, false, kWtAgent)
+#undef FA_STD
 #undef FA_STB
 #undef FA_STF
 #undef FA_STH
@@ -3922,6 +4015,17 @@ inline int launch_step_f16(RoundsState& R, int f, hipStream_t st, const uint16_t
     if (f < 0 || f >= kNumStepFormsF16) return fail(FA_ERR_ARG, "unknown float16 step form %d", f);
     return launch_step_spec(R, kStepSpecsF16[f], st, X, N, ldx, a, s, half_bits_to_float(divisor), out, nullptr,
                             rounds, offsets, out_offsets);
+}
+
+// Form f of kStepSpecsF64 (fa_fedavg_f64_rounds): double factors and divisor,
+// the rest as launch_step.
+inline int launch_step_f64(RoundsState& R, int f, hipStream_t st, const double* X, int64_t N, int64_t ldx,
+                           const double* a, const double* s, double divisor, double* out, int rounds,
+                           const int64_t* offsets, const int64_t* out_offsets) {
+    R.launched = false;
+    if (f < 0 || f >= kNumStepFormsF64) return fail(FA_ERR_ARG, "unknown float64 step form %d", f);
+    return launch_step_spec(R, kStepSpecsF64[f], st, X, N, ldx, a, s, 0.0f, out, nullptr, rounds, offsets,
+                            out_offsets, divisor);
 }
 
 // ---- the 16-bit row-table folds (fa_fedavg_bf16_ptrs, fa_fedavg_f16_ptrs) ----

@@ -296,7 +296,7 @@ class Tuner {
     // ---- step-form decisions ------------------------------------------------
     // key: "<ident> <dtype> <world> <client bucket> <P> <w0,w1,...>" (the
     // caller's device identity, "f32" or "bf16" -- "f32.peer" / "bf16.peer"
-    // for steps whose exchange is the peer copy, "float16" -- the slot widths of its
+    // for steps whose exchange is the peer copy, "float16", "float64" -- the slot widths of its
     // layout).  lookup: 1 one launch, 0 per-round launches, -1 no decision
     // (the file is read on the first lookup; -2: a malformed key).
     int step_lookup(const std::string& key) {
@@ -443,9 +443,10 @@ class Tuner {
         if (key.size() > 500) return false;
         if (sscanf(key.c_str(), "%127s %15s %lld %lld %lld %399s %c", id, dt, &world, &nb, &P, widths, &tail) != 6)
             return false;
-        // "float16": the float16 step (RCCL exchange only; the short "f16" stays malformed, as before it)
+        // "float16" / "float64": the float16 and float64 steps (RCCL exchange only; the short "f16" and
+        // "f64" stay malformed, as before them)
         if ((strcmp(dt, "f32") != 0 && strcmp(dt, "bf16") != 0 && strcmp(dt, "f32.peer") != 0 &&
-             strcmp(dt, "bf16.peer") != 0 && strcmp(dt, "float16") != 0) ||
+             strcmp(dt, "bf16.peer") != 0 && strcmp(dt, "float16") != 0 && strcmp(dt, "float64") != 0) ||
             world < 1 || world > 4096 || nb < 1 || (nb & (nb - 1)) || P < 1)
             return false;
         // widths: 1..8 positive integers separated by commas

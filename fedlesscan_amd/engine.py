@@ -665,6 +665,17 @@ def f16_factors(weights: Sequence, scores: Optional[Sequence] = None, total=None
         return Factors(weights, scores, _F16, total=total)
 
 
+def f64_factors(weights: Sequence, scores: Optional[Sequence] = None, total=None) -> Optional[Factors]:
+    """The float64 factors of a fold over float64 rows that stays float64, or
+    None when numpy would give another result dtype (weights, scores or total
+    of a wider or foreign scalar type: np.longdouble where it is wider than
+    double, complex).  Python numbers, np.float64, np.float32 and numpy
+    integers all keep it float64."""
+    if result_dtype(_F64, list(weights), scores, total) != _F64:
+        return None
+    return Factors(weights, scores, _F64, total=total)
+
+
 def _half_bits(div) -> int:
     """The bit pattern of a binary16 divisor (Factors.div of a float16 fold)."""
     return int(np.asarray(div, dtype=np.float16).view(np.uint16))
@@ -674,8 +685,9 @@ class StagedFactors:
     """Factors uploaded ONCE (one H2D on the current stream) for the several
     folds of one exchange step (fold_staged): the per-round launches of
     ShardedAggregator read them instead of staging their own per launch.
-    dtype: float32 (fp32 / bf16 rows) or float16 (the binary16 factors of a
-    float16 fold, whose divisor travels as its bit pattern)."""
+    dtype: float32 (fp32 / bf16 rows), float16 (the binary16 factors of a
+    float16 fold, whose divisor travels as its bit pattern) or float64 (a
+    float64 fold's, the divisor a Python float)."""
 
     def __init__(self, f: Factors, device):
         self.a, self.s = f.to(torch.device(device))
@@ -688,14 +700,25 @@ def fold_staged(X: torch.Tensor, sf: StagedFactors, *, out: Optional[torch.Tenso
                 out_bf16: Optional[torch.Tensor] = None):
     """fold_stacked with staged factors: fp32 rows into out; bf16 rows into
     out and/or out_bf16 (ABI 5); float16 rows (binary16 factors) into a
-    float16 out.  Returns out or out_bf16 when it is the only output, else
-    (out, out_bf16)."""
+    float16 out; float64 rows (float64 factors) into a float64 out, with
+    fa_fedavg_f64, the kernel fold_stacked runs.  Returns out or out_bf16 when
+    it is the only output, else (out, out_bf16)."""
     N, P, ldx = _check_matrix(X)
     if N != sf.n:
         raise InvalidParameterShapeError(f"{N} rows but {sf.n} staged factors")
     st = stream_ptr(X.device)
-    if (X.dtype == torch.float16) != (sf.dtype == _F16):
+    if (X.dtype == torch.float16) != (sf.dtype == _F16) or (X.dtype == torch.float64) != (sf.dtype == _F64):
         raise InvalidParameterShapeError(f"{X.dtype} rows with staged {sf.dtype} factors")
+    if X.dtype == torch.float64:
+        if torch.cuda.is_current_stream_capturing():
+            raise InvalidParameterShapeError("the float64 fold does not run under stream capture")
+        if out_bf16 is not None:
+            raise InvalidParameterShapeError("out_bf16 is for bfloat16 rows")
+        if out is None or not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
+                               and out.numel() >= P):
+            raise ValueError(f"out must be a contiguous CUDA float64 tensor of >= {P} elements")
+        _lib.call("fa_fedavg_f64", X.data_ptr(), N, P, ldx, sf.a.data_ptr(), _ptr(sf.s), sf.div, out.data_ptr(), st)
+        return out
     if X.dtype == torch.float16:
         if torch.cuda.is_current_stream_capturing():
             raise InvalidParameterShapeError("the float16 fold does not run under stream capture")
@@ -733,7 +756,9 @@ def fold_rounds(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence], 
     fp32 result); float16 X (factors that keep it float16, f16_factors) needs
     a float16 out and takes no out_bf16 (fa_fedavg_f16_rounds: binary16
     products, sums and quotient, the bits of fold_stacked on each round; not
-    with a peer exchange's state).  Returns the rounds state for
+    with a peer exchange's state); float64 X (factors that keep it float64,
+    f64_factors) likewise needs a float64 out (fa_fedavg_f64_rounds: the
+    bits of fa_fedavg_f64 on each round).  Returns the rounds state for
     `wait_round` (the current stream's, or `state`: a peer exchange's, fa_peers_rounds): the exchange of
     round k may start, on another stream, as soon as round k is complete,
     while the launch goes on.  Same bits as fold_stacked on each round's
@@ -747,8 +772,8 @@ def fold_rounds(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence], 
     N, W, ldx = _check_matrix(X)
     if len(weights) != N or (scores is not None and len(scores) != N):
         raise InvalidParameterShapeError(f"{N} rows but {len(weights)} weights")
-    f16 = X.dtype == torch.float16
-    if f16 and out_bf16 is not None:
+    f16, f64 = X.dtype == torch.float16, X.dtype == torch.float64
+    if (f16 or f64) and out_bf16 is not None:
         raise InvalidParameterShapeError("out_bf16 is for bfloat16 rows")
     rounds = len(offsets) - 1
     if out_offsets is not None:
@@ -757,7 +782,7 @@ def fold_rounds(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence], 
         end = max((int(out_offsets[k]) + int(offsets[k + 1]) - int(offsets[k]) for k in range(rounds)), default=0)
     else:
         end = int(offsets[-1]) if len(offsets) else 0
-    for name, t, dt in (("out", out, torch.float16 if f16 else torch.float32),
+    for name, t, dt in (("out", out, X.dtype if f16 or f64 else torch.float32),
                         ("out_bf16", out_bf16, torch.bfloat16)):
         if t is None:
             continue
@@ -769,11 +794,12 @@ def fold_rounds(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence], 
     if out is None and (X.dtype != torch.bfloat16 or out_bf16 is None):
         raise ValueError("fold_rounds needs out (fp32 rows) or out / out_bf16 (bf16 rows)")
     dev = X.device
-    f = factors if factors is not None else (f16_factors if f16 else f32_factors)(weights, scores, total)
+    f = factors if factors is not None else (f16_factors if f16 else f64_factors if f64 else f32_factors)(
+        weights, scores, total)
     if f is None:
         raise InvalidParameterShapeError("the rounds fold takes factors that keep the rows' arithmetic "
                                          "(Python-number weights)")
-    if (np.dtype(f.a.dtype) == _F16) != f16:
+    if (np.dtype(f.a.dtype) == _F16) != f16 or (np.dtype(f.a.dtype) == _F64) != f64:
         raise InvalidParameterShapeError(f"{X.dtype} rows with {f.a.dtype} factors")
     offs = (ctypes.c_int64 * len(offsets))(*[int(o) for o in offsets])
     oo = None if out_offsets is None else (ctypes.c_int64 * rounds)(*[int(o) for o in out_offsets[:rounds]])
@@ -792,8 +818,14 @@ def fold_rounds(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence], 
         a, s = f.to(dev)
         _lib.call("fa_fedavg_f16_rounds", r, X.data_ptr(), N, ldx, a.data_ptr(), _ptr(s), _half_bits(f.div),
                   addr(out), rounds, offs, oo, st)
+    elif f64:
+        # float64 factors: staged here, once for the step's launch (Factors.to)
+        a, s = f.to(dev)
+        _lib.call("fa_fedavg_f64_rounds", r, X.data_ptr(), N, ldx, a.data_ptr(), _ptr(s), float(f.div),
+                  addr(out), rounds, offs, oo, st)
     else:
-        raise InvalidParameterShapeError(f"the rounds fold takes float32, bfloat16 or float16 rows, got {X.dtype}")
+        raise InvalidParameterShapeError(
+            f"the rounds fold takes float32, bfloat16, float16 or float64 rows, got {X.dtype}")
     return r
 
 

@@ -72,14 +72,16 @@ def tail_shares(rounds: int, tail: float, steps: int = 1) -> List[float]:
 # 0.35, 0.125 measured 0.11 ms more fold per C3 rank step on one GPU);
 # bf16: a gentle geometric tail, 1, 0.7, 0.49, 0.34, so that every round
 # still covers the previous round's gather; float16 moves bf16's
-# bytes in and out, so it takes bf16's layout.
-DEFAULT_TAIL = {"f32": (0.125, 1), "bf16": (0.343, 3), "f16": (0.343, 3)}
+# bytes in and out, so it takes bf16's layout; float64 reads N x 8 bytes and
+# gathers (world - 1) x 8 per parameter, fp32's ratio at the same client count,
+# so it takes fp32's layout (derived, not measured).
+DEFAULT_TAIL = {"f32": (0.125, 1), "bf16": (0.343, 3), "f16": (0.343, 3), "f64": (0.125, 1)}
 
 
 def overlap_layout(P: int, world: int, dtype: str = "f32", rounds: int = 4, align: int = ALIGN,
                    quantum: int = 0) -> "SlotLayout":
     """The SlotLayout ShardedAggregator.aggregate_slots should get for a
-    `dtype` ("f32" / "bf16" / "f16") model of P params over `world` ranks (quantum:
+    `dtype` ("f32" / "bf16" / "f16" / "f64") model of P params over `world` ranks (quantum:
     see SlotLayout, e.g. pass_quantum())."""
     tail, steps = DEFAULT_TAIL[dtype]
     return SlotLayout(P, world, rounds, align=align, shares=tail_shares(rounds, tail, steps) if rounds > 1 else None,
@@ -88,9 +90,9 @@ def overlap_layout(P: int, world: int, dtype: str = "f32", rounds: int = 4, alig
 
 def pass_quantum(cus: int, dtype: str = "f32") -> int:
     """Columns one pass of the one-launch step's wide tiles covers (a block per
-    CU, 256 lanes x 4 quads / octets): a round that is a whole number of
-    passes completes with its last pass instead of a tile-time after it."""
-    return cus * 256 * 4 * (8 if dtype in ("bf16", "f16") else 4)
+    CU, 256 lanes x 4 quads / octets / float64 pairs): a round that is a whole
+    number of passes completes with its last pass instead of a tile-time after it."""
+    return cus * 256 * 4 * (8 if dtype in ("bf16", "f16") else 2 if dtype == "f64" else 4)
 
 
 class SlotLayout:
@@ -240,16 +242,16 @@ def step_key(ident: str, bf16, n_clients: int, layout: "SlotLayout", exchange: s
     world size, client-count bucket (the count moves from round to round with
     stragglers; a form's advantage does not), P and the layout's slot widths.
     The dtype: `bf16` as a bool (True bf16, False fp32) or as the name "f32" /
-    "bf16" / "f16", or the keyword `dtype`, which wins; each dtype's decisions
-    have keys of their own (the key spells float16 out: the cache file's
-    step lines take "f32", "bf16" and "float16")."""
+    "bf16" / "f16" / "f64", or the keyword `dtype`, which wins; each dtype's
+    decisions have keys of their own (the key spells float16 and float64 out:
+    the cache file's step lines take "f32", "bf16", "float16" and "float64")."""
     bucket = 1 << max(0, int(n_clients) - 1).bit_length()
     name = dtype if dtype is not None else (bf16 if isinstance(bf16, str) else ("bf16" if bf16 else "f32"))
     if name not in DEFAULT_TAIL:
         raise ValueError(f"step_key: dtype {name!r} is not one of {sorted(DEFAULT_TAIL)}")
-    if name == "f16" and exchange == "peer_copy":
-        raise ValueError("step_key: float16 steps take the RCCL exchange only")
-    dt = ("float16" if name == "f16" else name) + (".peer" if exchange == "peer_copy" else "")
+    if name in ("f16", "f64") and exchange == "peer_copy":
+        raise ValueError(f"step_key: float{name[1:]} steps take the RCCL exchange only")
+    dt = {"f16": "float16", "f64": "float64"}.get(name, name) + (".peer" if exchange == "peer_copy" else "")
     return f"{ident} {dt} {layout.world} {bucket} {layout.P} {','.join(str(w) for w in layout.widths)}"
 
 
@@ -454,7 +456,7 @@ class ShardedAggregator:
             if not X_local.is_cuda:
                 return None
             ident = self.ident = device_ident(X_local.device)
-        dt = "f16" if X_local.dtype == torch.float16 else X_local.dtype == torch.bfloat16
+        dt = {torch.float16: "f16", torch.float64: "f64"}.get(X_local.dtype, X_local.dtype == torch.bfloat16)
         return step_key(ident, dt, int(X_local.shape[0]), layout, self.exchange)
 
     def step_form(self, X_local: torch.Tensor, layout: "SlotLayout") -> Optional[str]:
@@ -559,11 +561,14 @@ class ShardedAggregator:
     def aggregate(self, X_local: torch.Tensor, weights: Sequence, scores: Optional[Sequence] = None,
                   P: Optional[int] = None, total=None) -> torch.Tensor:
         """X_local = this rank's columns [start, end) of the stacked updates, all N clients.
-        float16 rows under factors that keep them float16 give a float16 model."""
+        float16 rows under factors that keep them float16 give a float16 model,
+        float64 rows under factors that keep them float64 a float64 one."""
         f16 = X_local.dtype == torch.float16
         if f16 and self.default_fold:
             # factors that promote the rows: refused on every rank, before any collective
             self._f16_factors(weights, scores, total)
+        if X_local.dtype == torch.float64 and self.default_fold:
+            self._f64_factors(X_local, weights, scores, total)
         if P is None:
             t = torch.tensor([X_local.shape[1]], dtype=torch.int64, device=X_local.device)
             if self.world > 1:
@@ -575,7 +580,8 @@ class ShardedAggregator:
         if hi > lo:
             local = self.fold(X_local, weights, scores, total=total)
         else:
-            local = torch.empty(0, dtype=torch.float16 if f16 else torch.float32, device=X_local.device)
+            local = torch.empty(0, dtype=X_local.dtype if X_local.dtype in (torch.float16, torch.float64)
+                                else torch.float32, device=X_local.device)
         return self.gather(local, P)
 
     @staticmethod
@@ -589,6 +595,21 @@ class ShardedAggregator:
             raise InvalidParameterShapeError("weights/scores promote the float16 fold (numpy scalar types)")
         return f
 
+    @staticmethod
+    def _f64_factors(X_local, weights, scores, total):
+        """The float64 factors of a float64 step (engine.f64_factors).
+        Refused, on every rank and before any collective: factors that give
+        another result dtype (the slots are float64) and CUDA rows under a
+        stream capture (no captured factor fill carries float64)."""
+        from .aggregator.exceptions import InvalidParameterShapeError
+        from .engine import f64_factors
+        f = f64_factors(weights, scores, total)
+        if f is None:
+            raise InvalidParameterShapeError("weights/scores promote the float64 fold (wider or foreign scalar types)")
+        if X_local.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise InvalidParameterShapeError("float64 slots do not fold under stream capture")
+        return f
+
     def aggregate_slots(self, X_local: torch.Tensor, weights: Sequence, scores: Optional[Sequence],
                         layout: "SlotLayout", out: Optional[torch.Tensor] = None, total=None) -> torch.Tensor:
         """Fold round by round and all-gather each round asynchronously, so the
@@ -597,7 +618,9 @@ class ShardedAggregator:
         X_local: [N, layout.local_width], this rank's slots side by side (columns
         past P may hold anything; their outputs are trimmed).  Returns [P]:
         float32 for fp32 updates; float16 for float16 updates (binary16
-        arithmetic throughout, as numpy's; RCCL exchange only); for bf16
+        arithmetic throughout, as numpy's; RCCL exchange only); float64 for
+        float64 updates (numpy's own float64 fold; RCCL exchange only, no
+        stream capture); for bf16
         updates the RNE bf16 model (the fold still accumulates in fp32), so the exchange moves 2 bytes per parameter,
         half the xGMI bytes of the fp32 result.  `fold` must accept out= (and
         out_bf16= for bf16 input), as engine.fold_stacked does.  Raises
@@ -609,24 +632,34 @@ class ShardedAggregator:
             from .aggregator.exceptions import InvalidParameterShapeError
             raise InvalidParameterShapeError('float16 slots take the RCCL exchange (exchange="rccl"): the peer-copy '
                                              "exchange moves float32 and bfloat16 slots only")
+        f64f = None
+        if X_local.dtype == torch.float64:
+            from .aggregator.exceptions import InvalidParameterShapeError
+            if self.exchange == "peer_copy":
+                raise InvalidParameterShapeError('float64 slots take the RCCL exchange (exchange="rccl"): the '
+                                                 "peer-copy exchange moves float32 and bfloat16 slots only")
+            if self.default_fold:
+                f64f = self._f64_factors(X_local, weights, scores, total)
         if not X_local.is_cuda or torch.cuda.is_current_stream_capturing():
             # CPU ranks, or a HIP graph capture (the one launch refuses
             # capture: its epochs would replay): per-round launches, nothing
             # timed or checked
             return self._aggregate_slots(X_local, weights, scores, layout, out, total)
         # the factors, rounded once for the whole step (numpy's weak-scalar
-        # rule, engine.f32_factors / f16_factors): the default fold's slots are
-        # float32 / bf16 / float16 buffers, so promoted factors (numpy-scalar
-        # weights) are refused
+        # rule, engine.f32_factors / f16_factors / f64_factors): the default
+        # fold's slots are float32 / bf16 / float16 / float64 buffers, so
+        # promoted factors (numpy-scalar weights) are refused
         f = None
         if self.default_fold:
             from .aggregator.exceptions import InvalidParameterShapeError
             from .engine import f32_factors
-            if X_local.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            if X_local.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.float64):
                 raise InvalidParameterShapeError(
-                    f"sharded slots take float32, bfloat16 or float16 rows, not {X_local.dtype}")
+                    f"sharded slots take float32, bfloat16, float16 or float64 rows, not {X_local.dtype}")
             if X_local.dtype == torch.float16:
                 f = self._f16_factors(weights, scores, total)
+            elif X_local.dtype == torch.float64:
+                f = f64f
             else:
                 f = f32_factors(weights, scores, total)
             if f is None:
@@ -772,20 +805,26 @@ class ShardedAggregator:
         ranks never split on it."""
         if not (self.default_fold and X_local.is_cuda) or not 1 < layout.rounds <= 8:
             return False
-        if X_local.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        if X_local.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.float64):
             return False
         if X_local.shape[0] < 1 or min(layout.widths) < 1:
             return False
-        align = 8 if X_local.dtype in (torch.bfloat16, torch.float16) else 4
+        align = self._col_align(X_local.dtype)
         return not any(layout.offset(k) % align for k in range(layout.rounds))
+
+    @staticmethod
+    def _col_align(dtype) -> int:
+        """Columns per 16-byte unit of the one-launch step's rows."""
+        return 8 if dtype in (torch.bfloat16, torch.float16) else 2 if dtype == torch.float64 else 4
 
     @staticmethod
     def _aligned(X_local: torch.Tensor) -> torch.Tensor:
         """X_local, or an aligned copy of it when its rows are not 16-B aligned
-        or its pitch is off the octet (bf16, float16) / quad (fp32) grid: the one
-        launch's 16-byte loads need both.  The copy runs on the current stream
-        (the fold stream), in order before the fold that reads it."""
-        align = 8 if X_local.dtype in (torch.bfloat16, torch.float16) else 4
+        or its pitch is off the octet (bf16, float16) / quad (fp32) / pair
+        (float64) grid: the one launch's 16-byte loads need both.  The copy runs
+        on the current stream (the fold stream), in order before the fold that
+        reads it."""
+        align = ShardedAggregator._col_align(X_local.dtype)
         if (X_local.data_ptr() % 16 == 0 and X_local.stride(1) == 1
                 and (X_local.shape[0] == 1 or X_local.stride(0) % align == 0)):
             return X_local
@@ -817,7 +856,7 @@ class ShardedAggregator:
         from . import engine
         dev = X_local.device
         bf16 = X_local.dtype == torch.bfloat16
-        odt = X_local.dtype if X_local.dtype in (torch.bfloat16, torch.float16) else torch.float32
+        odt = X_local.dtype if X_local.dtype in (torch.bfloat16, torch.float16, torch.float64) else torch.float32
         full = out if out is not None else torch.empty(layout.padded_total, dtype=odt, device=dev)
         if full.dtype != odt or full.numel() < layout.padded_total or not full.is_contiguous():
             raise ValueError(f"out needs {layout.padded_total} contiguous {odt} elements")
@@ -827,7 +866,7 @@ class ShardedAggregator:
         e = _timing_pair(fs, folds)
         # all the fold stores: the fp32 result, or for bf16 rows only its
         # RNE-bf16 copy (no fp32 result, ABI 5) -- the form the exchange moves;
-        # float16 rows their float16 result
+        # float16 and float64 rows their result in their own dtype
         kw = {"out_bf16": full} if bf16 else {"out": full}
         r = engine.fold_rounds(X_local, weights, scores, offs, total=total, factors=factors,
                                out_offsets=[lo for lo, _ in own], **kw)
@@ -871,12 +910,12 @@ class ShardedAggregator:
 
     def _aggregate_slots(self, X_local, weights, scores, layout, out, total, folds=None, factors=None):
         bf16 = X_local.dtype == torch.bfloat16
-        odt = X_local.dtype if X_local.dtype in (torch.bfloat16, torch.float16) else torch.float32
+        odt = X_local.dtype if X_local.dtype in (torch.bfloat16, torch.float16, torch.float64) else torch.float32
         full = out if out is not None else torch.empty(layout.padded_total, dtype=odt, device=X_local.device)
         if full.dtype != odt or full.numel() < layout.padded_total or not full.is_contiguous():
             raise ValueError(f"out needs {layout.padded_total} contiguous {odt} elements")
         # each round's fold writes straight into this rank's chunk of the model
-        # (fp32 rows the fp32 result, float16 rows the float16 one, bf16 rows
+        # (fp32 rows the fp32 result, float16 and float64 rows theirs, bf16 rows
         # only its RNE-bf16 copy), and the
         # round's all-gather runs in place: at world 1 nothing is copied
         cur = torch.cuda.current_stream(X_local.device) if X_local.is_cuda else None

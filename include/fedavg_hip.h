@@ -258,6 +258,27 @@ int fa_fedavg_f16_rounds(fa_rounds* r, const uint16_t* X, int64_t N, int64_t ldx
 /* [host] the kernel form fa_fedavg_f16_rounds runs */
 const char* fa_rounds_form_f16(void);
 
+/* The one launch per exchange step for float64 rows (new symbols, ABI still
+ * 7): `_aggregate` of both strategies (fed_avg_aggregator.py:31-41,
+ * stall_aware_aggregation.py:52-66) on a rank's slots of float64 layers -- the
+ * dtype of the reference's own fixture (test/test_aggregation.py:23-38) -- in
+ * the arithmetic of fa_fedavg_f64: t_i = fl64(fl64(x_i * a_i) * s_i), no FMA,
+ * acc = t_0 then fl64(acc + t_i) in client order, the IEEE double divide,
+ * subnormals kept.  Bit for bit fa_fedavg_f64 on each round's columns, every
+ * round of a step in one launch as fa_fedavg_f32_rounds.  a, s [device, N
+ * doubles] (s == NULL for FedAvg) and divisor as for fa_fedavg_f64.  out
+ * [doubles] receives round k at columns [offsets[k], offsets[k+1]) or, with
+ * out_offsets, [out_offsets[k], ...).  offsets and out_offsets % 2 == 0,
+ * 1 <= rounds <= 8, X and out 16-B aligned, ldx % 2 == 0; a capturing stream
+ * -> FA_ERR_ARG.  The rounds are published at agent scope (a state of
+ * fa_peers_rounds, whose rounds other GPUs read, -> FA_ERR_ARG).
+ * fa_rounds_wait / _check / _timeouts serve it as they do the other three. */
+int fa_fedavg_f64_rounds(fa_rounds* r, const double* X, int64_t N, int64_t ldx,
+                         const double* a, const double* s, double divisor, double* out,
+                         int rounds, const int64_t* offsets, const int64_t* out_offsets, void* stream);
+/* [host] the kernel form fa_fedavg_f64_rounds runs */
+const char* fa_rounds_form_f64(void);
+
 /* ---- kernel-free peer exchange of a step (ABI 4; ABI 5: no fence) ----------
  * The reference saves ONE global model per round (aggregation.py:125-138 ->
  * ParameterDao.save, client_daos.py:351-378); at N > 1 every rank folds its

@@ -121,6 +121,13 @@ const char* fa_step_form_name_f16(int form);
 int fa_fedavg_f16_rounds_form(void* r, int form, const uint16_t* X, int64_t N, int64_t ldx, const uint16_t* a,
                               const uint16_t* s, uint16_t divisor, uint16_t* out, int rounds, const int64_t* offsets,
                               const int64_t* out_offsets, void* stream);
+/* The float64 step's forms (a table of their own) and fa_fedavg_f64_rounds
+ * with a chosen one, over a fa_bench_rounds_create state (agent scope). */
+int fa_num_step_forms_f64(void);
+const char* fa_step_form_name_f64(int form);
+int fa_fedavg_f64_rounds_form(void* r, int form, const double* X, int64_t N, int64_t ldx, const double* a,
+                              const double* s, double divisor, double* out, int rounds, const int64_t* offsets,
+                              const int64_t* out_offsets, void* stream);
 /* How the state's launches publish their rounds: 0 agent scope (the default,
  * sc1 tile stores); 1 system scope as a peer exchange's state (fa_peers_rounds:
  * sc0 sc1 tile stores, the policy forms only); 2 system scope as round 5 did
