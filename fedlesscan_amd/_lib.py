@@ -83,6 +83,11 @@ _PROTOS = {
     "fa_fedavg_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f64, _vp, _vp]),
     "fa_fold_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _f64, _int, _vp, _vp]),
     "fa_fedavg_f64_ptrs": (_int, [_vp, _i64, _i64, _vp, _vp, _f64, _int, _vp, _vp]),
+    "fa_layers_plan": (_int, [_vp, _vp, _i64, _int, _i64, _int, _vp, _vp, _vp, _vp]),
+    "fa_fedavg_f32_layers": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _f32, _vp, _vp]),
+    "fa_fedavg_bf16_layers": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "fa_fedavg_f16_layers": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, ctypes.c_uint16, _vp, _vp]),
+    "fa_fedavg_f64_layers": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _f64, _vp, _vp]),
     "fa_fedavg_i32": (_int, [_vp, _i64, _i64, _i64, _vp, _f64, _vp, _vp]),
     "fa_fedavg_i64": (_int, [_vp, _i64, _i64, _i64, _vp, _f64, _vp, _vp]),
     "fa_npz_index": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _int]),
@@ -148,6 +153,7 @@ _BENCH_PROTOS = {
     "fa_rows16_form_name": (ctypes.c_char_p, [_int]),
     "fa_fedavg_bf16_ptrs_form": (_int, [_vp, _i64, _i64, _vp, _vp, _f32, _int, _vp, _vp, _vp, _int]),
     "fa_fedavg_f16_ptrs_form": (_int, [_vp, _i64, _i64, _vp, _vp, ctypes.c_uint16, _int, _vp, _vp, _int]),
+    "fa_fedavg_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp, _vp]),
     "fa_fedavg_bf16_variant": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _int]),
     "fa_num_bf16_variants": (_int, []),
     "fa_bf16_variant_name": (ctypes.c_char_p, [_int]),

@@ -508,6 +508,38 @@ int fa_fedavg_f64_ptrs(const double* const* xi, int64_t N, int64_t P, const doub
     return f64_rows_fold(xi, N, P, a, s, divisor, rows_aligned, out, stream);
 }
 
+// ---- every layer of a device-resident model in one launch (layers_fold) ----
+int fa_layers_plan(const int64_t* cols, const int32_t* aligned, int64_t L, int unit_lg, int64_t cus, int units,
+                   fa_layer_plan* plan, int64_t* tiles, int64_t* elems, int* units_out) {
+    return layers_plan(cols, aligned, L, unit_lg, cus, units, plan, tiles, elems, units_out);
+}
+
+int fa_fedavg_f32_layers(const float* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
+                         int units, const float* a, const float* s, float divisor, float* out, void* stream) {
+    return layers_fold(kLayersF32, "fa_fedavg_f32_layers", (const void* const*)xi, plan, L, N, tiles, units, 0, a, s,
+                       (double)divisor, out, nullptr, stream);
+}
+
+int fa_fedavg_bf16_layers(const uint16_t* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
+                          int units, const float* a, const float* s, float divisor, float* out_f32,
+                          uint16_t* out_bf16, void* stream) {
+    return layers_fold(kLayersBf16, "fa_fedavg_bf16_layers", (const void* const*)xi, plan, L, N, tiles, units, 0, a, s,
+                       (double)divisor, out_f32, out_bf16, stream);
+}
+
+int fa_fedavg_f16_layers(const uint16_t* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
+                         int units, const uint16_t* a, const uint16_t* s, uint16_t divisor, uint16_t* out,
+                         void* stream) {
+    return layers_fold(kLayersF16, "fa_fedavg_f16_layers", (const void* const*)xi, plan, L, N, tiles, units, 0, a, s,
+                       (double)half_bits_to_float(divisor), out, nullptr, stream);
+}
+
+int fa_fedavg_f64_layers(const double* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
+                         int units, const double* a, const double* s, double divisor, double* out, void* stream) {
+    return layers_fold(kLayersF64, "fa_fedavg_f64_layers", (const void* const*)xi, plan, L, N, tiles, units, 0, a, s,
+                       divisor, out, nullptr, stream);
+}
+
 int fa_fedavg_i32(const int32_t* X, int64_t N, int64_t P, int64_t ldx, const int64_t* a, double divisor,
                   double* out, void* stream) {
     int rc = check_common(N, P, ldx, X, a, out);

@@ -639,6 +639,12 @@ int fa_fedavg_f16_ptrs_form(const uint16_t* const* xi, int64_t N, int64_t P, con
                             uint16_t divisor, int rows_aligned, uint16_t* out, void* stream, int form) {
     return f16_rows_fold(xi, N, P, a, s, divisor, rows_aligned, out, stream, form < 0 ? -1 : form);
 }
+int fa_fedavg_layers_form(int dtype, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
+                          int64_t tiles, int units, int64_t grid_cap, const void* a, const void* s, double divisor,
+                          void* out, void* out_bf16, void* stream) {
+    return layers_fold(dtype, "fa_fedavg_layers_form", xi, plan, L, N, tiles, units, grid_cap, a, s, divisor, out,
+                       out_bf16, stream);
+}
 const char* fa_variant_name(int variant) {
     return (variant >= 0 && variant < kNumVariants) ? kVariants[variant] : "";
 }

@@ -46,6 +46,7 @@
 
 #include "fedavg_hip.h"
 #include "octet_grid.hpp"  // kBlock, octet_grid
+#include "layer_plan.hpp"  // the layer-table folds' host planner
 #include "tuner.hpp"
 
 #pragma clang fp contract(off)
@@ -1292,14 +1293,16 @@ __global__ __launch_bounds__(kBlock) void k_fold_f32_rows_scalar(
 // List-of-rows form with every row 16-B aligned (fa_fedavg_f32_ptrs_aligned):
 // the tile structure of the stacked fold (C quads per lane, U rows ahead) with
 // row i's base read from xi[i] (a wave-uniform scalar load).  No branch sits
-// between the loads and their use.
-template <int U, int C, bool SCORED>
+// between the loads and their use.  Q: the quad type the row bases are read
+// as -- gf32x4 (the layer-table fold) makes the row loads global loads, the
+// default leaves them to the compiler (flat loads in k_fold_f32_rows_gs).
+template <int U, int C, bool SCORED, class Q = const f32x4>
 __device__ __forceinline__ void fold_quads_rows(const float* const* __restrict__ xi, int64_t q0, int64_t N,
                                                 const float* __restrict__ a, const float* __restrict__ s,
                                                 float divisor, f32x4* __restrict__ out) {
     f32x4 acc[C];
     {
-        const f32x4* r = reinterpret_cast<const f32x4*>(xi[0]) + q0;
+        Q* r = (Q*)xi[0] + q0;
         const float a0 = a[0], s0 = SCORED ? s[0] : 1.0f;
 #pragma unroll
         for (int c = 0; c < C; ++c) acc[c] = term4<SCORED>(__builtin_nontemporal_load(r + c * kBlock), a0, s0);
@@ -1309,7 +1312,7 @@ __device__ __forceinline__ void fold_quads_rows(const float* const* __restrict__
         f32x4 v[U][C];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const f32x4* r = reinterpret_cast<const f32x4*>(xi[i + u]) + q0;
+            Q* r = (Q*)xi[i + u] + q0;
 #pragma unroll
             for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
         }
@@ -1321,7 +1324,7 @@ __device__ __forceinline__ void fold_quads_rows(const float* const* __restrict__
         }
     }
     for (; i < N; ++i) {
-        const f32x4* r = reinterpret_cast<const f32x4*>(xi[i]) + q0;
+        Q* r = (Q*)xi[i] + q0;
         const float ai = a[i], si = SCORED ? s[i] : 1.0f;
 #pragma unroll
         for (int c = 0; c < C; ++c) acc[c] = add4(acc[c], term4<SCORED>(__builtin_nontemporal_load(r + c * kBlock), ai, si));
@@ -2564,6 +2567,186 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f64_rows_scalar(
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= P) return;
     out[c] = fold_column_f64<SCORED, false, true>(TableRows<gf64, double>{xi, c}, N, a, s, nullptr, divisor);
+}
+
+// ---------------------------------------------------------------------------
+// The layer-table folds (fa_fedavg_*_layers): every layer of a device-resident
+// model in one launch.  xi holds L*N row bases, layer-major; plan[l] gives
+// layer l's column count, its offset in the flat output, its first tile and
+// whether all its rows are 16-B aligned (layer_plan.hpp).  The launch is
+// grid-stride over the tiles of all layers.  Per tile the block finds its
+// layer by a binary search of plan[].tile0 -- the tile index is the same for
+// every lane and the plan is read as constant memory, so the search is scalar
+// loads and scalar compares; a block's tiles ascend, so each search starts at
+// the layer of the block's previous tile -- and then runs the row-table fold's
+// own tile body over xi + l*N with the layer's P, output base and the tile's
+// index within the layer: the bits of k_*_rows_gs on that layer.  A layer with
+// some row off 16-B alignment is tiled one column per lane with the column
+// body (the bits of k_*_rows_scalar).  No arithmetic is new.
+// ---------------------------------------------------------------------------
+static_assert(sizeof(fa_layer_plan) == 4 * sizeof(int64_t), "plan entries are read as four int64");
+typedef __attribute__((address_space(4))) const int64_t ci64;
+struct LayerTile {
+    int64_t l, cols, offset, bid;  // the layer, its columns, its output offset, the tile's index within it
+    bool aligned;
+};
+// the layer of tile `bid`: the last l in [lo, L) with tile0[l] <= bid (tile0[lo] <= bid on entry)
+__device__ __forceinline__ LayerTile layer_tile(const fa_layer_plan* __restrict__ plan, int64_t L, int64_t bid,
+                                                int64_t lo) {
+    int64_t hi = L;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (((ci64*)(plan + mid))[2] <= bid) lo = mid;
+        else hi = mid;
+    }
+    ci64* e = (ci64*)(plan + lo);
+    return {lo, e[0], e[1], bid - e[2], e[3] != 0};
+}
+
+// One fp32 column of a row table: 8 rows of loads ahead of the ordered adds
+// (the body of k_fold_f32_rows_scalar)
+template <bool SCORED>
+__device__ __forceinline__ float fold_column_f32(const float* const* __restrict__ xi, int64_t c, int64_t N,
+                                                 const float* __restrict__ a, const float* __restrict__ s,
+                                                 float divisor) {
+    float acc = term1<SCORED>(((const gf32*)xi[0])[c], a[0], SCORED ? s[0] : 1.0f);
+    int64_t i = 1;
+    for (; i + 8 <= N; i += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load((const gf32*)xi[i + u] + c);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc = acc + term1<SCORED>(v[u], a[i + u], SCORED ? s[i + u] : 1.0f);
+    }
+    for (; i < N; ++i) acc = acc + term1<SCORED>(((const gf32*)xi[i])[c], a[i], SCORED ? s[i] : 1.0f);
+    return acc / divisor;
+}
+
+template <int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fold_f32_layers(
+    const float* const* __restrict__ xi, const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N,
+    const float* __restrict__ a, const float* __restrict__ s, float divisor, float* __restrict__ out,
+    int64_t ntiles) {
+    int64_t l = 0;
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+        const LayerTile t = layer_tile(plan, L, bid, l);
+        l = t.l;
+        const float* const* x = xi + l * N;
+        float* o = out + t.offset;
+        if (!t.aligned) {
+            const int64_t c = t.bid * kBlock + threadIdx.x;
+            if (c < t.cols) o[c] = fold_column_f32<SCORED>(x, c, N, a, s, divisor);
+            continue;
+        }
+        f32x4* O4 = reinterpret_cast<f32x4*>(o);
+        octet_tile<C, kBlock, 2>(
+            t.bid, t.cols,
+            [&](int64_t q) { fold_quads_rows<U, C, SCORED, gf32x4>(x, q, N, a, s, divisor, O4 + q); },
+            [&](int64_t q) { fold_quads_rows<U, 1, SCORED, gf32x4>(x, q, N, a, s, divisor, O4 + q); },
+            [&](int64_t col) {  // the P % 4 columns, as k_fold_f32_rows_gs folds them
+                for (; col < t.cols; ++col) {
+                    float acc = term1<SCORED>(((const gf32*)x[0])[col], a[0], SCORED ? s[0] : 1.0f);
+                    for (int64_t i = 1; i < N; ++i)
+                        acc = acc + term1<SCORED>(((const gf32*)x[i])[col], a[i], SCORED ? s[i] : 1.0f);
+                    o[col] = acc / divisor;
+                }
+            });
+    }
+}
+
+template <int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_bf16_layers(
+    const uint16_t* const* __restrict__ xi, const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N,
+    const float* __restrict__ a, const float* __restrict__ s, float divisor, float* __restrict__ out,
+    uint16_t* __restrict__ outb, int64_t ntiles) {
+    int64_t l = 0;
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+        const LayerTile t = layer_tile(plan, L, bid, l);
+        l = t.l;
+        const uint16_t* const* x = xi + l * N;
+        float* o = out ? out + t.offset : nullptr;
+        uint16_t* ob = outb ? outb + t.offset : nullptr;
+        if (!t.aligned) {
+            const int64_t c = t.bid * kBlock + threadIdx.x;
+            if (c < t.cols) st_column_bf16(fold_column_bf16<SCORED>(TableRows<gu16>{x, c}, N, a, s, divisor), o, ob, c);
+            continue;
+        }
+        octet_tile<C>(
+            t.bid, t.cols,
+            [&](int64_t q) { fold_octets<U, C, SCORED>(TableRows<gu32x4>{x, q}, N, a, s, divisor, o, ob, q); },
+            [&](int64_t q) { fold_octets<U, 1, SCORED>(TableRows<gu32x4>{x, q}, N, a, s, divisor, o, ob, q); },
+            [&](int64_t col) {
+                for (; col < t.cols; ++col)
+                    st_column_bf16(fold_column_bf16<SCORED>(TableRows<gu16>{x, col}, N, a, s, divisor), o, ob, col);
+            });
+    }
+}
+
+template <int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f16_layers(
+    const uint16_t* const* __restrict__ xi, const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N,
+    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out,
+    int64_t ntiles) {
+    int64_t l = 0;
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+        const LayerTile t = layer_tile(plan, L, bid, l);
+        l = t.l;
+        const uint16_t* const* x = xi + l * N;
+        uint16_t* o = out + t.offset;
+        if (!t.aligned) {
+            const int64_t c = t.bid * kBlock + threadIdx.x;
+            if (c < t.cols) o[c] = fold_column_f16<SCORED, false, true>(TableRows<gu16>{x, c}, N, a, s, nullptr, divisor);
+            continue;
+        }
+        u32x4* O8 = reinterpret_cast<u32x4*>(o);
+        octet_tile<C>(
+            t.bid, t.cols,
+            [&](int64_t q) {
+                fold_octets_f16<U, C, SCORED, false, true>(TableRows<gu32x4>{x, q}, N, a, s, nullptr, divisor, O8 + q);
+            },
+            [&](int64_t q) {
+                fold_octets_f16<U, 1, SCORED, false, true>(TableRows<gu32x4>{x, q}, N, a, s, nullptr, divisor, O8 + q);
+            },
+            [&](int64_t col) {
+                for (; col < t.cols; ++col)
+                    o[col] = fold_column_f16<SCORED, false, true>(TableRows<gu16>{x, col}, N, a, s, nullptr, divisor);
+            });
+    }
+}
+
+template <int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f64_layers(
+    const double* const* __restrict__ xi, const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N,
+    const double* __restrict__ a, const double* __restrict__ s, double divisor, double* __restrict__ out,
+    int64_t ntiles) {
+    int64_t l = 0;
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+        const LayerTile t = layer_tile(plan, L, bid, l);
+        l = t.l;
+        const double* const* x = xi + l * N;
+        double* o = out + t.offset;
+        if (!t.aligned) {
+            const int64_t c = t.bid * kBlock + threadIdx.x;
+            if (c < t.cols)
+                o[c] = fold_column_f64<SCORED, false, true>(TableRows<gf64, double>{x, c}, N, a, s, nullptr, divisor);
+            continue;
+        }
+        f64x2* O2 = reinterpret_cast<f64x2*>(o);
+        octet_tile<C, kBlock, 1>(
+            t.bid, t.cols,
+            [&](int64_t q) {
+                fold_pairs_f64<U, C, SCORED, false, true>(TableRows<gf64x2, double>{x, q}, N, a, s, nullptr, divisor,
+                                                          O2 + q);
+            },
+            [&](int64_t q) {
+                fold_pairs_f64<U, 1, SCORED, false, true>(TableRows<gf64x2, double>{x, q}, N, a, s, nullptr, divisor,
+                                                          O2 + q);
+            },
+            [&](int64_t col) {
+                o[col] = fold_column_f64<SCORED, false, true>(TableRows<gf64, double>{x, col}, N, a, s, nullptr,
+                                                              divisor);
+            });
+    }
 }
 
 // numpy integer semantics: product and fold in the input dtype with
@@ -4243,6 +4426,104 @@ inline int f64_rows_fold(const double* const* xi, int64_t N, int64_t P, const do
         default: launch_f64_rows_gs<1>(st, xi, N, P, a, s, divisor, out); break;
     }
     return check_launch("fa_fedavg_f64_ptrs");
+}
+
+// ---- the layer-table folds (fa_fedavg_*_layers) ---------------------------
+// One launcher for the four dtypes.  One form per model, fixed on the host, no
+// tuner kind: 8 rows ahead (the row-table folds' own), units per lane from the
+// caller's plan (pick_layer_units: pick_pairs' rule over the model's tiles),
+// balanced passes over at most one block per CU -- tile_grid, the rule of
+// octet_grid, on the tile total.  Reasoned values, none of them measured.
+// grid_cap > 0 (the bench library): at most that many blocks.
+constexpr int kLayersU = 8;
+enum LayersKind { kLayersF32 = 0, kLayersBf16 = 1, kLayersF16 = 2, kLayersF64 = 3 };
+
+template <int C>
+void launch_layers(int kind, hipStream_t st, unsigned g, const void* const* xi, const fa_layer_plan* plan, int64_t L,
+                   int64_t N, int64_t tiles, const void* a, const void* s, double divisor, void* out, void* outb) {
+#define FA_LAY(K, SC, ...) \
+    hipLaunchKernelGGL((K<kLayersU, C, SC>), dim3(g), dim3(kBlock), 0, st, __VA_ARGS__, tiles)
+    switch (kind) {
+        case kLayersF32: {
+            const float* const* x = (const float* const*)xi;
+            const float *af = (const float*)a, *sf = (const float*)s;
+            if (s) FA_LAY(k_fold_f32_layers, true, x, plan, L, N, af, sf, (float)divisor, (float*)out);
+            else FA_LAY(k_fold_f32_layers, false, x, plan, L, N, af, sf, (float)divisor, (float*)out);
+            break;
+        }
+        case kLayersBf16: {
+            const uint16_t* const* x = (const uint16_t* const*)xi;
+            const float *af = (const float*)a, *sf = (const float*)s;
+            if (s) FA_LAY(k_fedavg_bf16_layers, true, x, plan, L, N, af, sf, (float)divisor, (float*)out, (uint16_t*)outb);
+            else FA_LAY(k_fedavg_bf16_layers, false, x, plan, L, N, af, sf, (float)divisor, (float*)out, (uint16_t*)outb);
+            break;
+        }
+        case kLayersF16: {
+            const uint16_t* const* x = (const uint16_t* const*)xi;
+            const uint16_t *ah = (const uint16_t*)a, *sh = (const uint16_t*)s;
+            if (s) FA_LAY(k_fedavg_f16_layers, true, x, plan, L, N, ah, sh, (float)divisor, (uint16_t*)out);
+            else FA_LAY(k_fedavg_f16_layers, false, x, plan, L, N, ah, sh, (float)divisor, (uint16_t*)out);
+            break;
+        }
+        default: {
+            const double* const* x = (const double* const*)xi;
+            const double *ad = (const double*)a, *sd = (const double*)s;
+            if (s) FA_LAY(k_fedavg_f64_layers, true, x, plan, L, N, ad, sd, divisor, (double*)out);
+            else FA_LAY(k_fedavg_f64_layers, false, x, plan, L, N, ad, sd, divisor, (double*)out);
+            break;
+        }
+    }
+#undef FA_LAY
+}
+
+// divisor: the entry's divisor as a double (exact for a float32 and for the
+// value of a binary16 divisor); out / outb: bf16's optional pair, else out
+inline int layers_fold(int kind, const char* what, const void* const* xi, const fa_layer_plan* plan, int64_t L,
+                       int64_t N, int64_t tiles, int units, int64_t grid_cap, const void* a, const void* s,
+                       double divisor, void* out, void* outb, void* stream) {
+    if (kind < kLayersF32 || kind > kLayersF64) return fail(FA_ERR_ARG, "%s: unknown dtype %d", what, kind);
+    if (L < 0 || N < 0 || tiles < 0)
+        return fail(FA_ERR_ARG, "negative size (L=%lld, N=%lld, tiles=%lld)", (long long)L, (long long)N,
+                    (long long)tiles);
+    if (N == 0) return fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
+    if (units != 1 && units != 2 && units != 4)
+        return fail(FA_ERR_ARG, "%s: %d units per lane (1, 2 or 4)", what, units);
+    if (grid_cap < 0) return fail(FA_ERR_ARG, "%s: negative grid cap", what);
+    if (L == 0 || tiles == 0) { g_err[0] = 0; return FA_OK; }
+    const bool any_out = kind == kLayersBf16 ? (out || outb) : out != nullptr;
+    if (!xi || !plan || !a || !any_out) return fail(FA_ERR_ARG, "null xi/plan/a/out pointer");
+    if (!aligned16(out) || (kind == kLayersBf16 && !aligned16(outb)))
+        return fail(FA_ERR_ARG, "%s needs 16-B aligned outputs", what);
+    if (tiles > (int64_t)0x7FFFFFFF) return fail(FA_ERR_ARG, "too many tiles for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    StreamDevice on_stream_device(stream);
+    int64_t g = tile_grid(tiles, -1, cu_count());
+    if (grid_cap > 0 && g > grid_cap) g = grid_cap;
+    if (kind != kLayersBf16) outb = nullptr;
+    switch (units) {
+        case 4: launch_layers<4>(kind, st, (unsigned)g, xi, plan, L, N, tiles, a, s, divisor, out, outb); break;
+        case 2: launch_layers<2>(kind, st, (unsigned)g, xi, plan, L, N, tiles, a, s, divisor, out, outb); break;
+        default: launch_layers<1>(kind, st, (unsigned)g, xi, plan, L, N, tiles, a, s, divisor, out, outb); break;
+    }
+    return check_launch(what);
+}
+
+inline int layers_plan(const int64_t* cols, const int32_t* aligned, int64_t L, int unit_lg, int64_t cus, int units,
+                       fa_layer_plan* plan, int64_t* tiles, int64_t* elems, int* units_out) {
+    if (L < 0 || cus < 1 || unit_lg < 1 || unit_lg > 3)
+        return fail(FA_ERR_ARG, "fa_layers_plan: L=%lld, cus=%lld, unit_lg=%d", (long long)L, (long long)cus, unit_lg);
+    if (units != 0 && units != 1 && units != 2 && units != 4)
+        return fail(FA_ERR_ARG, "fa_layers_plan: %d units per lane (0, 1, 2 or 4)", units);
+    if (!tiles || !elems || !units_out || (L > 0 && (!cols || !aligned || !plan)))
+        return fail(FA_ERR_ARG, "fa_layers_plan: null pointer");
+    for (int64_t l = 0; l < L; ++l)
+        if (cols[l] < 0) return fail(FA_ERR_ARG, "fa_layers_plan: layer %lld has %lld columns", (long long)l,
+                                     (long long)cols[l]);
+    if (units == 0) units = pick_layer_units(cols, aligned, L, unit_lg, cus);
+    *tiles = fill_layer_plan(cols, aligned, L, units, unit_lg, plan, elems);
+    *units_out = units;
+    g_err[0] = 0;
+    return FA_OK;
 }
 
 }  // namespace

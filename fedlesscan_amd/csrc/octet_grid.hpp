@@ -18,15 +18,22 @@ constexpr int kBlock = 256;  // lanes per block of every fold kernel
 struct OctetGrid {
     int64_t tiles, grid;
 };
-inline OctetGrid octet_grid(int64_t P, int C, int per_cu, int64_t cus, int lg = 3) {
-    const int64_t per_block = (int64_t)kBlock * C, units = (P >> lg) + ((P & (((int64_t)1 << lg) - 1)) ? 1 : 0);
-    const int64_t tiles = (units + per_block - 1) / per_block;
-    if (per_cu == 0) return {tiles, tiles};
+// The grid over `tiles` tiles by the per_cu rule above (0 tiles: an empty grid).
+// octet_grid applies it to the tiles of one row; the layer-table folds
+// (layer_plan.hpp) to the tiles of all the layers of a model.
+inline int64_t tile_grid(int64_t tiles, int per_cu, int64_t cus) {
+    if (tiles <= 0) return 0;
+    if (per_cu == 0) return tiles;
     int64_t g = (int64_t)(per_cu > 0 ? per_cu : -per_cu) * cus;
     if (g > tiles) g = tiles;
     if (per_cu < 0) {
         const int64_t passes = (tiles + g - 1) / g;
         g = (tiles + passes - 1) / passes;
     }
-    return {tiles, g};
+    return g;
+}
+inline OctetGrid octet_grid(int64_t P, int C, int per_cu, int64_t cus, int lg = 3) {
+    const int64_t per_block = (int64_t)kBlock * C, units = (P >> lg) + ((P & (((int64_t)1 << lg) - 1)) ? 1 : 0);
+    const int64_t tiles = (units + per_block - 1) / per_block;
+    return {tiles, tile_grid(tiles, per_cu, cus)};
 }

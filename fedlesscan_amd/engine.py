@@ -866,9 +866,10 @@ _dtype_of = operator.attrgetter("dtype")
 # dtypes the library folds through a device table of row pointers
 _ROW_TABLE_DTYPES = (torch.float32, torch.bfloat16, torch.float16, torch.float64)
 # process-wide route counters (diagnostics, as StreamingFold.stats): 16-bit and
-# float64 folds that ran through a row table, layer groups copied into a
-# stacked matrix
-stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0}
+# float64 folds that ran through a row table (layers: a one-launch model fold
+# counts each of its layers), layer groups copied into a stacked matrix,
+# one-launch model folds (fa_fedavg_*_layers)
+stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0, "layer_table_folds": 0}
 
 
 class RowSet:
@@ -1087,6 +1088,229 @@ def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
 
 
 # ---------------------------------------------------------------------------
+# every layer of a device-resident model in one launch (fa_fedavg_*_layers)
+# ---------------------------------------------------------------------------
+# dtype -> (C entry, columns of a 16-byte unit as a power of two)
+_LAYER_TABLE = {
+    torch.float32: ("fa_fedavg_f32_layers", 2),
+    torch.bfloat16: ("fa_fedavg_bf16_layers", 3),
+    torch.float16: ("fa_fedavg_f16_layers", 3),
+    torch.float64: ("fa_fedavg_f64_layers", 1),
+}
+_shape_of = operator.attrgetter("shape")
+_cu_counts: dict = {}
+
+
+def _cus(dev: torch.device) -> int:
+    k = dev.index if dev.index is not None else torch.cuda.current_device()
+    n = _cu_counts.get(k)
+    if n is None:
+        n = _cu_counts[k] = int(torch.cuda.get_device_properties(k).multi_processor_count)
+    return n
+
+
+def layer_plan(cols: Sequence[int], aligned: Sequence[bool], unit_lg: int, cus: int, units: int = 0):
+    """fa_layers_plan, the host planner of the layer-table folds (no GPU):
+    (plan, tiles, elems, units) with plan an [L, 4] int64 array of (cols,
+    offset, tile0, aligned) rows.  units = 0 applies the rule (the most of 4,
+    2, 1 units per lane whose balanced grid over the model's tiles covers 7/8
+    of `cus` compute units, else 1); 1, 2 or 4 plans for that many."""
+    L = len(cols)
+    c = np.ascontiguousarray(cols, dtype=np.int64)
+    al = np.ascontiguousarray(aligned, dtype=np.int32)
+    plan = np.zeros((L, 4), dtype=np.int64)
+    tiles, elems, u = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+    _lib.call("fa_layers_plan", c.ctypes.data, al.ctypes.data, L, unit_lg, cus, units, plan.ctypes.data,
+              ctypes.addressof(tiles), ctypes.addressof(elems), ctypes.addressof(u))
+    return plan, tiles.value, elems.value, u.value
+
+
+class ModelRowSet:
+    """N clients x L layers already on the GPU, prepared once for repeated
+    one-launch folds (fold_model_rows): what RowSet is for one layer.
+
+    parameters: N sequences of device tensors of one dtype and device;
+    layers: the layer indices to take (default: every layer all clients have).
+    Per layer the clients' tensors must be contiguous and of one shape
+    (InvalidParameterShapeError otherwise).  Building the set gathers the L*N
+    row bases, plans the tiles of all layers with the host planner
+    (fa_layers_plan) and uploads table and plan in ONE copy; fold_model_rows
+    then costs the factor upload and one kernel.  The set keeps the tensors
+    alive; their CONTENTS may change between folds, their storage may not."""
+
+    def __init__(self, parameters: Sequence[Sequence[torch.Tensor]], layers: Optional[Sequence[int]] = None):
+        params = list(parameters)
+        N = len(params)
+        if N == 0:
+            _lib.check(_lib.FA_ERR_NO_CLIENTS, "ModelRowSet")
+        lis = list(range(min(map(len, params)))) if layers is None else list(layers)
+        # one C-level pass per property and layer (as RowSet: no reshape per tensor)
+        cols_of = [list(map(operator.itemgetter(li), params)) for li in lis]
+        t0 = cols_of[0][0] if cols_of else None
+        if t0 is not None and not (isinstance(t0, torch.Tensor) and t0.is_cuda):
+            raise ValueError("layers must be CUDA (HIP) tensors")
+        self.N, self.L, self.layers = N, len(lis), lis
+        self.device = t0.device if t0 is not None else None
+        self.dtype = t0.dtype if t0 is not None else None
+        self.shapes, self.sizes = [], []
+        host_ptrs = np.zeros((self.L, N), dtype=np.int64)
+        for k, col in enumerate(cols_of):
+            shp = col[0].shape
+            if (set(map(_shape_of, col)) != {shp} or set(map(_dtype_of, col)) != {self.dtype}
+                    or not all(map(torch.Tensor.is_contiguous, col))
+                    or set(map(torch.Tensor.get_device, col)) != {t0.get_device()}):
+                raise InvalidParameterShapeError(
+                    f"layer {lis[k]}: all clients' tensors must be contiguous with one shape, dtype and device")
+            self.shapes.append(tuple(shp))
+            self.sizes.append(col[0].numel())
+            host_ptrs[k] = np.fromiter(map(torch.Tensor.data_ptr, col), dtype=np.int64, count=N)
+        self.tensors = cols_of  # keeps the storages alive
+        self.host_ptrs = host_ptrs
+        self.esize = t0.element_size() if t0 is not None else 0
+        self.entry = None
+        self._rowsets: dict = {}
+        self.ptrs = self.plan = self.host_plan = None
+        self.tiles = self.elems = self.units = 0
+        if self.dtype in _LAYER_TABLE and self.L:
+            self.entry, lg = _LAYER_TABLE[self.dtype]
+            sizes = np.asarray(self.sizes, dtype=np.int64)
+            aligned = ~((host_ptrs % 16) != 0).any(axis=1) | (sizes == 0)
+            self.host_plan, self.tiles, self.elems, self.units = layer_plan(sizes, aligned, lg, _cus(self.device))
+            both = torch.from_numpy(np.concatenate([host_ptrs.reshape(-1), self.host_plan.reshape(-1)])).to(self.device)
+            self.ptrs, self.plan = both[:self.L * N], both[self.L * N:]
+        self.offsets = [int(o) for o in self.host_plan[:, 1]] if self.host_plan is not None else []
+
+    def overlaps(self, t: torch.Tensor) -> bool:
+        """Does tensor t share a byte with any client tensor of the set?"""
+        if self.L == 0 or t.numel() == 0:
+            return False
+        lo = t.data_ptr()
+        hi = lo + t.numel() * t.element_size()
+        nbytes = (np.asarray(self.sizes, dtype=np.int64) * self.esize)[:, None]
+        return bool(np.any((self.host_ptrs < hi) & (lo < self.host_ptrs + nbytes)))
+
+    def rowset(self, k: int) -> RowSet:
+        """The k-th layer of the set as a RowSet over this set's own device
+        table (no upload, so it also serves under a stream capture): the
+        per-layer route of fold_model_rows."""
+        rs = self._rowsets.get(k)
+        if rs is None:
+            rows = [t.reshape(-1) for t in self.tensors[k]]
+            if self.ptrs is None or self.sizes[k] == 0:
+                rs = RowSet(rows)
+            else:
+                rs = RowSet.__new__(RowSet)
+                rs.rows, rs.N, rs.P, rs.device, rs.dtype = rows, self.N, self.sizes[k], self.device, self.dtype
+                rs.view = None
+                rs.ptrs = self.ptrs[k * self.N:(k + 1) * self.N]
+                rs.host_ptrs = self.host_ptrs[k]
+                rs.aligned = bool(self.host_plan[k, 3])
+            self._rowsets[k] = rs
+        return rs
+
+    def split(self, flat: torch.Tensor) -> List[torch.Tensor]:
+        """The layers of a flat result, as views shaped like the layers."""
+        return [flat[o:o + n].reshape(s) for o, n, s in zip(self.offsets, self.sizes, self.shapes)]
+
+
+def layer_table_enabled() -> bool:
+    """aggregate_layers folds a device group of two or more layers in one
+    launch (fold_model_rows) unless FEDAVG_LAYER_TABLE=0 (read per call),
+    which keeps one fold_rows per layer."""
+    return os.environ.get("FEDAVG_LAYER_TABLE", "1") != "0"
+
+
+def _layer_factors(dt: torch.dtype, weights, scores, total) -> Optional[Factors]:
+    """The factors fold_rows would fold rows of dtype dt with, or None where
+    it would leave the row table (numpy promotes the result)."""
+    if dt == torch.float32:
+        return f32_factors(weights, scores, total)
+    if dt == torch.bfloat16:
+        return Factors.weak_f32(weights, scores, total) or Factors(weights, scores, np.dtype(np.float32), total=total)
+    if dt == torch.float16:
+        return f16_factors(weights, scores, total)
+    return f64_factors(weights, scores, total)
+
+
+def fold_model_rows(model, weights: Sequence, scores: Optional[Sequence] = None, *,
+                    out: Optional[torch.Tensor] = None, total=None, want_bf16: bool = False,
+                    out_bf16: Optional[torch.Tensor] = None):
+    """fold_rows over every layer of a device-resident model in ONE launch.
+
+    model: a ModelRowSet (prepared once, reusable) or N lists of device
+    tensors (a ModelRowSet is built for this call).  Returns a list of L
+    tensors shaped like the layers: views of one flat result in which layer k
+    starts at model.offsets[k], a multiple of 64 elements.  Each holds, bit for
+    bit, what fold_rows gives for that layer alone, with fold_rows' factor
+    rules per dtype.  out / out_bf16: flat buffers of model.elems elements to
+    fold into; want_bf16 / out_bf16 (bf16 layers): as fold_rows, a pair of
+    lists (fp32 layers, RNE bf16 layers), or the bf16 list alone when only
+    out_bf16 was given.  Where fold_rows would leave the row table (factors
+    that promote the result, a dtype without a table, a stream capture in
+    progress) every layer goes through fold_rows on its own, over the set's
+    own table and into fresh tensors (out / out_bf16 are refused there)."""
+    ms = model if isinstance(model, ModelRowSet) else ModelRowSet(model)
+    N = ms.N
+    if len(weights) != N or (scores is not None and len(scores) != N):
+        raise InvalidParameterShapeError(f"{N} clients but {len(weights)} weights"
+                                         + ("" if scores is None else f" / {len(scores)} scores"))
+    bf16 = ms.dtype == torch.bfloat16
+    if (out_bf16 is not None or want_bf16) and not bf16:
+        raise InvalidParameterShapeError("want_bf16 / out_bf16 are for bfloat16 layers")
+    f = None
+    if ms.entry is not None and not torch.cuda.is_current_stream_capturing():
+        f = _layer_factors(ms.dtype, weights, scores, total)
+    if f is None:
+        if out is not None or out_bf16 is not None:
+            raise InvalidParameterShapeError("out / out_bf16 need the layer-table route (no promotion, no capture)")
+        res = [fold_rows(ms.rowset(k), weights, scores, total=total, want_bf16=want_bf16) for k in range(ms.L)]
+        if want_bf16:
+            return ([r[0].reshape(s) for r, s in zip(res, ms.shapes)],
+                    [r[1].reshape(s) for r, s in zip(res, ms.shapes)])
+        return [r.reshape(s) for r, s in zip(res, ms.shapes)]
+    dev, E = ms.device, ms.elems
+    res_dt = torch.float32 if bf16 else ms.dtype
+    _check_out("out", out, res_dt, E)
+    _check_out("out_bf16", out_bf16, torch.bfloat16, E)
+
+    def usable(t):  # the table lives in device memory: the library cannot see an alias
+        return t is not None and t.data_ptr() % 16 == 0 and not ms.overlaps(t)
+
+    dst, dstb = out, out_bf16
+    out = out if usable(out) else None
+    outb = out_bf16 if usable(out_bf16) else None
+    if outb is None and (want_bf16 or dstb is not None):
+        outb = torch.empty(E, dtype=torch.bfloat16, device=dev)
+    if out is None and (dst is not None or outb is None or want_bf16):
+        out = torch.empty(E, dtype=res_dt, device=dev)
+    a, s = f.to(dev)
+    args = [ms.ptrs.data_ptr(), ms.plan.data_ptr(), ms.L, N, ms.tiles, ms.units, a.data_ptr(), _ptr(s)]
+    if bf16:
+        _lib.call(ms.entry, *args, float(f.div), _ptr(out), _ptr(outb), stream_ptr(dev))
+    elif ms.dtype == torch.float16:
+        _lib.call(ms.entry, *args, _half_bits(f.div), out.data_ptr(), stream_ptr(dev))
+    else:
+        _lib.call(ms.entry, *args, float(f.div), out.data_ptr(), stream_ptr(dev))
+    stats["layer_table_folds"] += 1
+    folded = sum(1 for n in ms.sizes if n)  # layers folded through a table, as fold_rows counts them
+    if ms.dtype == torch.float64:
+        stats["rows64_folds"] += folded
+    elif ms.dtype != torch.float32:
+        stats["rows16_folds"] += folded
+    if dst is not None and dst is not out:
+        dst.reshape(-1)[:E].copy_(out)
+        out = dst
+    if dstb is not None and dstb is not outb:
+        dstb.reshape(-1)[:E].copy_(outb)
+        outb = dstb
+    if want_bf16:
+        return ms.split(out.reshape(-1)), ms.split(outb.reshape(-1))
+    if out_bf16 is not None:
+        return ms.split(outb.reshape(-1)) if out is None else (ms.split(out.reshape(-1)), ms.split(outb.reshape(-1)))
+    return ms.split(out.reshape(-1))
+
+
+# ---------------------------------------------------------------------------
 # per-layer (reference-shaped) aggregation
 # ---------------------------------------------------------------------------
 def _layer_meta(parameters, n_eff):
@@ -1221,7 +1445,14 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
                 parameters[i][li].is_contiguous() for i in range(n_eff) for li in lis):
             # device fp32 / bf16 layers, and float16 / float64 layers whose result
             # stays in their dtype: fold each layer straight from the clients' own tensors
-            # through a row-pointer list -- no stacking copy
+            # through a row-pointer list -- no stacking copy.  Two or more layers: one
+            # table of every layer's rows and one launch (FEDAVG_LAYER_TABLE=0: a
+            # fold per layer); the same bits either way
+            if len(lis) >= 2 and layer_table_enabled() and not torch.cuda.is_current_stream_capturing():
+                res = fold_model_rows(ModelRowSet(parameters[:n_eff], lis), w, sc, total=sum(total_weights))
+                for li, r in zip(lis, res):
+                    outs[li] = r
+                continue
             for li in lis:
                 rows = [parameters[i][li].reshape(-1) for i in range(n_eff)]
                 outs[li] = fold_rows(rows, w, sc, total=sum(total_weights)).reshape(shapes[li])

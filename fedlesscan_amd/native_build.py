@@ -27,6 +27,7 @@ SRC = os.path.join(CSRC, "fedavg.hip")
 BENCH_SRC = os.path.join(CSRC, "fedavg_bench.hip")
 KERNELS = os.path.join(CSRC, "fold_kernels.hpp")
 OCTET_GRID = os.path.join(CSRC, "octet_grid.hpp")
+LAYER_PLAN = os.path.join(CSRC, "layer_plan.hpp")
 TUNER = os.path.join(CSRC, "tuner.hpp")
 HOST_SRCS = [os.path.join(CSRC, f) for f in ("ingest_host.cpp", "bson_host.cpp", "ingest_pipe.cpp")]
 HDR = os.path.join(REPO, "include", "fedavg_hip.h")
@@ -38,9 +39,9 @@ HOSTFAST_SRC = os.path.join(CSRC, "hostfast.c")
 HOSTFAST = os.path.join(OUT_DIR, "_hostfast" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))  # = _lib.HOSTFAST_PATH
 # library -> (sources compiled into it, files it depends on)
 TARGETS = {
-    LIB: ([SRC, *HOST_SRCS], [SRC, KERNELS, OCTET_GRID, TUNER, HDR, *HOST_SRCS, os.path.join(CSRC, "host_copy.hpp"),
+    LIB: ([SRC, *HOST_SRCS], [SRC, KERNELS, OCTET_GRID, LAYER_PLAN, TUNER, HDR, *HOST_SRCS, os.path.join(CSRC, "host_copy.hpp"),
                               os.path.join(CSRC, "peer_exchange.hpp")]),
-    BENCH_LIB: ([BENCH_SRC], [BENCH_SRC, KERNELS, OCTET_GRID, TUNER, HDR, BENCH_HDR]),
+    BENCH_LIB: ([BENCH_SRC], [BENCH_SRC, KERNELS, OCTET_GRID, LAYER_PLAN, TUNER, HDR, BENCH_HDR]),
     HOSTFAST: ([HOSTFAST_SRC], [HOSTFAST_SRC]),
 }
 ARCH = os.environ.get("FEDAVG_OFFLOAD_ARCH", "gfx950")

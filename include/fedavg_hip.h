@@ -477,6 +477,65 @@ int fa_fedavg_f64_ptrs(const double* const* xi, int64_t N, int64_t P,
                        const double* a, const double* s, double divisor, int rows_aligned,
                        double* out, void* stream);
 
+/* ---- every layer of a device-resident model in one launch (new symbols, ABI
+ * still 7) -------------------------------------------------------------------
+ * The reference folds a model layer by layer over the clients' lists of
+ * arrays (fed_avg_aggregator.py:24-42: `layer * num_examples` per client and
+ * layer, :32-35; reduce(np.add) and the divide per layer, :38-41).  The
+ * row-table folds above take one layer per launch; these take all L layers:
+ *   xi    [device] L*N row bases, layer-major: xi[l*N + i] = client i's layer l
+ *   plan  [device] L entries (fa_layer_plan), as fa_layers_plan wrote them
+ *   tiles, units  the tile total and the units per lane of that plan
+ * One grid-stride launch over the `tiles` tiles of all layers, balanced passes
+ * over at most one block per CU.  A block finds the layer of a tile by a
+ * search of plan[].tile0 (wave-uniform loads) and runs the row-table fold's
+ * own tile body over xi + l*N with the layer's column count and output base,
+ * so layer l of `out` (plan[l].cols elements at plan[l].offset) holds, bit for
+ * bit, what fa_fedavg_*_ptrs gives for that layer alone: strict client order,
+ * acc = t_0, separate multiply and add, the dtype's own divide, subnormals
+ * kept, final stores non-temporal.  A layer with aligned == 0 (some row off
+ * 16-B alignment) is folded one column per lane in the same launch.  Factors
+ * are [device] arrays in the dtype's own convention (float32 for fp32 and
+ * bf16 rows; binary16 bit patterns, the divisor too, for float16; double for
+ * float64); bf16 takes the optional out_f32 / out_bf16 pair, at least one.
+ * Every out is one flat array of the plan's `elems` elements, 16-B aligned;
+ * the elements between a layer's end and the next offset are not written.
+ * No allocation, no synchronisation.  Checked before any launch: negative
+ * L / N / tiles, units outside {1, 2, 4}, a NULL xi / plan / a / out with
+ * tiles > 0, an out off 16-B alignment -> FA_ERR_ARG; N == 0 ->
+ * FA_ERR_NO_CLIENTS.  L == 0 or tiles == 0 launches nothing.  The plan and
+ * the table live in device memory: the library cannot check them against
+ * tiles and units, nor see an alias (no output may overlap a row).  Not
+ * covered: a tuner kind (one fixed geometry: 8 rows ahead, units by
+ * fa_layers_plan's rule), help for stream capture, integer layers, the
+ * sharded step, several GPUs. */
+typedef struct fa_layer_plan {
+    int64_t cols;    /* columns of the layer                                  */
+    int64_t offset;  /* its first element in the flat output (multiple of 64) */
+    int64_t tile0;   /* its first tile (prefix sum of the layers' tiles)      */
+    int64_t aligned; /* != 0: every row of the layer is 16-B aligned          */
+} fa_layer_plan;
+/* The host planner (touches no GPU).  cols[l], aligned[l]: the layers;
+ * unit_lg: the columns of a 16-byte unit as a power of two (2 fp32, 3 bf16 /
+ * float16, 1 float64); cus: the compute units the launch will have; units:
+ * 1, 2 or 4 units per lane, or 0 for the rule -- the most of 4, 2, 1 whose
+ * balanced grid over the model's total tiles still covers 7/8 of the CUs,
+ * else 1.  Writes plan[0..L), *tiles (= tile0 of an L-th layer), *elems (the
+ * flat output's length) and *units_out.  An aligned layer has
+ * ceil(ceil(cols / unit) / (256 * units)) tiles, any other ceil(cols / 256). */
+int fa_layers_plan(const int64_t* cols, const int32_t* aligned, int64_t L, int unit_lg, int64_t cus, int units,
+                   fa_layer_plan* plan, int64_t* tiles, int64_t* elems, int* units_out);
+int fa_fedavg_f32_layers(const float* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
+                         int units, const float* a, const float* s, float divisor, float* out, void* stream);
+int fa_fedavg_bf16_layers(const uint16_t* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
+                          int units, const float* a, const float* s, float divisor, float* out_f32,
+                          uint16_t* out_bf16, void* stream);
+int fa_fedavg_f16_layers(const uint16_t* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
+                         int units, const uint16_t* a, const uint16_t* s, uint16_t divisor, uint16_t* out,
+                         void* stream);
+int fa_fedavg_f64_layers(const double* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
+                         int units, const double* a, const double* s, double divisor, double* out, void* stream);
+
 /* Integer updates: numpy keeps `layer * n` and the np.add fold in the integer
  * dtype (wrapping) and true-divides into float64 (fed_avg_aggregator.py:33,39).
  * a = integer cardinalities [device, int64]; out float64. */

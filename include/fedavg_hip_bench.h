@@ -15,6 +15,8 @@
 
 #include <stdint.h>
 
+#include "fedavg_hip.h" /* fa_layer_plan */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -83,6 +85,18 @@ int fa_fedavg_bf16_ptrs_form(const uint16_t* const* xi, int64_t N, int64_t P, co
                              int form);
 int fa_fedavg_f16_ptrs_form(const uint16_t* const* xi, int64_t N, int64_t P, const uint16_t* a, const uint16_t* s,
                             uint16_t divisor, int rows_aligned, uint16_t* out, void* stream, int form);
+/* The layer-table folds (fa_fedavg_*_layers) with the units per lane of the
+ * caller's plan (fa_layers_plan with units = 1, 2 or 4) and a cap on the grid
+ * (grid_cap > 0: at most that many blocks, so small models take several
+ * grid-stride passes; 0: the product's grid).  dtype: 0 fp32, 1 bf16,
+ * 2 float16, 3 float64; xi, a, s and out are that entry's arrays; divisor is
+ * the entry's divisor as a double (float16: the value of the binary16
+ * divisor); out_bf16 is read for bf16 only (out then is the optional fp32
+ * output).  Argument checks and status codes as the product entries; an
+ * unknown dtype or a negative grid_cap -> FA_ERR_ARG. */
+int fa_fedavg_layers_form(int dtype, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
+                          int64_t tiles, int units, int64_t grid_cap, const void* a, const void* s, double divisor,
+                          void* out, void* out_bf16, void* stream);
 /* Same for the bf16 fold (variant 0 = fa_fedavg_bf16). */
 int fa_fedavg_bf16_variant(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
                            const float* a, const float* s, float divisor,
