@@ -137,6 +137,11 @@ _BENCH_PROTOS = {
     "fa_num_variants": (_int, []),
     "fa_variant_name": (ctypes.c_char_p, [_int]),
     "fa_f32_pick_name": (ctypes.c_char_p, [_i64, _i64, _i64]),
+    "fa_bench_set_cus": (_int, [_int]),
+    "fa_bench_fold_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _vp]),
+    "fa_bench_fold_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, ctypes.c_uint16, _int, _vp, _vp]),
+    "fa_bench_fold_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _f64, _int, _vp, _vp]),
+    "fa_bench_fedavg_f64_ptrs": (_int, [_vp, _i64, _i64, _vp, _vp, _f64, _int, _vp, _vp]),
     "fa_num_f32_forms": (_int, []),
     "fa_f32_form_name": (ctypes.c_char_p, [_int]),
     "fa_fedavg_f32_form": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _int]),

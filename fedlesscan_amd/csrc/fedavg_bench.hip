@@ -236,18 +236,17 @@ constexpr int kNumPtrsVariants = sizeof(kPtrsVariants) / sizeof(kPtrsVariants[0]
 // kernels; for a plain (non-cooperative) launch that only costs balance.
 template <int U, int C, bool NT, bool SC, bool ACC, bool FIN>
 int resident_blocks() {
-    static thread_local int cache[16] = {0};
+    static thread_local int cache[16] = {0};  // blocks per CU; the CU count is cu_count()'s (fa_bench_set_cus)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (cache[dev] > 0) return cache[dev];
-    int cus = 256, per_cu = 4;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    if (cache[dev] > 0) return cache[dev] * cu_count();
+    int per_cu = 4;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_fold_f32_balanced<U, C, NT, SC, ACC, FIN>, kBlock,
                                                      0) != hipSuccess ||
         per_cu < 1)
         per_cu = 4;
-    cache[dev] = cus * per_cu;
-    return cache[dev];
+    cache[dev] = per_cu;
+    return per_cu * cu_count();
 }
 
 template <int U, int C, bool NT, bool SC, bool ACC, bool FIN>
@@ -492,6 +491,34 @@ int fa_num_variants(void) { return kNumVariants; }
 const char* fa_f32_pick_name(int64_t N, int64_t P, int64_t cus) {
     if (N < 1 || P < 1) return "";
     return f32_pick_name(pick_f32(N, P, cus));
+}
+int fa_bench_set_cus(int cus) {
+    static std::mutex mu;
+    static int tuner_mode = 1;  // this library's tuner mode from before the override
+    std::lock_guard<std::mutex> lk(mu);
+    if (cus < 0) cus = 0;
+    const int prev = g_cu_override.exchange(cus);
+    // no form is measured, and so none recorded or written to the cache file,
+    // at a CU count the device does not have: the policy form while it holds
+    if (cus > 0 && prev == 0) tuner_mode = g_tuner.set_mode(0);
+    else if (cus == 0 && prev > 0) g_tuner.set_mode(tuner_mode);
+    return prev;
+}
+int fa_bench_fold_f32(const float* X, int64_t N, int64_t P, int64_t ldx, const float* a, const float* s,
+                      const float* acc_in, float divisor, int finalize, float* out, void* stream) {
+    return fold_f32_auto(X, N, P, ldx, a, s, acc_in, divisor, finalize, out, stream);
+}
+int fa_bench_fold_f16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
+                      const uint16_t* acc_in, uint16_t divisor, int finalize, uint16_t* out, void* stream) {
+    return f16_fold(X, N, P, ldx, a, s, acc_in, divisor, finalize, out, stream);
+}
+int fa_bench_fold_f64(const double* X, int64_t N, int64_t P, int64_t ldx, const double* a, const double* s,
+                      const double* acc_in, double divisor, int finalize, double* out, void* stream) {
+    return f64_fold(X, N, P, ldx, a, s, acc_in, divisor, finalize, out, stream);
+}
+int fa_bench_fedavg_f64_ptrs(const double* const* xi, int64_t N, int64_t P, const double* a, const double* s,
+                             double divisor, int rows_aligned, double* out, void* stream) {
+    return f64_rows_fold(xi, N, P, a, s, divisor, rows_aligned, out, stream);
 }
 int fa_num_f32_forms(void) { return kNumF32Picks; }
 const char* fa_f32_form_name(int form) { return (form >= 0 && form < kNumF32Picks) ? f32_pick_name((F32Pick)form) : ""; }

@@ -2266,6 +2266,37 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_bf16_scalar(
 // ---------------------------------------------------------------------------
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
+// The IEEE double divide of the float64 folds.  The compiler's expansion of a
+// double divide (a reciprocal refined by fused multiply-adds, scaled back at
+// the end) rounds every normal quotient correctly, but it decides the rounding
+// of a subnormal quotient on a value that is only close to the true one: a
+// quotient on, or within a hair of, the midpoint of two subnormals can come out
+// one unit off (-49104 x 2^-1074 / 3168 = -15.5 x 2^-1074 came out as -15 x
+// 2^-1074 on MI355X; IEEE 754 and numpy round the tie to -16).  Only a
+// subnormal quotient can sit on a midpoint (from 2^-1022 on a midpoint has 54
+// bits, and no quotient of two doubles has), so those alone are redone: with
+// |acc / d| = (A / D) x 2^-1074, D in [1/2, 1), and n = |q| / 2^-1074 the
+// candidate, the sign of A - (n +- 1/2) D -- one fused multiply-add, exact in
+// its sign, n +- 1/2 having at most 53 bits -- says whether the true quotient
+// lies beyond a midpoint, and a zero is a tie, which goes to the even n.
+__device__ __forceinline__ double div_d1(double acc, double d) {
+    const double q = acc / d;
+    if (!(__builtin_fabs(q) < 0x1p-1022) || acc == 0.0 || __builtin_isinf(d)) return q;
+    int ea = 0, ed = 0;
+    const double ma = __builtin_frexp(__builtin_fabs(acc), &ea), D = __builtin_frexp(__builtin_fabs(d), &ed);
+    const double A = __builtin_ldexp(ma, ea - ed + 1074);
+    double n = __builtin_ldexp(__builtin_fabs(q), 1074);  // an integer below 2^52
+    const double hi = __builtin_fma(-(n + 0.5), D, A);
+    if (hi > 0.0 || (hi == 0.0 && ((long long)n & 1))) {
+        n += 1.0;
+    } else if (hi < 0.0 && n >= 1.0) {
+        const double lo = __builtin_fma(-(n - 0.5), D, A);
+        if (lo < 0.0 || (lo == 0.0 && ((long long)n & 1))) n -= 1.0;
+    }
+    return __builtin_copysign(__builtin_ldexp(n, -1074), q);
+}
+__device__ __forceinline__ f64x2 div_d2(f64x2 acc, double d) { return f64x2{div_d1(acc.x, d), div_d1(acc.y, d)}; }
+
 // float64: a lane owns 2 columns (one 16-byte load per row), U rows ahead;
 // the odd last column (P % 2) goes to the lane with q == P/2.
 template <int U, bool SCORED>
@@ -2296,7 +2327,7 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f64_v2(
             if constexpr (SCORED) t = t * s[i];
             acc = acc + t;
         }
-        __builtin_nontemporal_store(acc / divisor, reinterpret_cast<f64x2*>(out) + q);
+        __builtin_nontemporal_store(div_d2(acc, divisor), reinterpret_cast<f64x2*>(out) + q);
     } else if (q == nq && (P & 1)) {
         const int64_t c = P - 1;
         double acc = X[c] * a[0];
@@ -2306,7 +2337,7 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f64_v2(
             if constexpr (SCORED) t = t * s[i];
             acc = acc + t;
         }
-        out[c] = acc / divisor;
+        out[c] = div_d1(acc, divisor);
     }
 }
 
@@ -2326,7 +2357,7 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f64(
         if constexpr (SCORED) t = t * s[i];
         acc = acc + t;
     }
-    out[c] = acc / divisor;
+    out[c] = div_d1(acc, divisor);
 }
 
 // ---------------------------------------------------------------------------
@@ -2368,7 +2399,7 @@ __device__ __forceinline__ double term_d1(double x, double a, double s) {
 }
 template <bool FIN>
 __device__ __forceinline__ void st_d2(f64x2* out, f64x2 acc, double divisor) {
-    if constexpr (FIN) __builtin_nontemporal_store(acc / divisor, out);
+    if constexpr (FIN) __builtin_nontemporal_store(div_d2(acc, divisor), out);
     else *out = acc;
 }
 
@@ -2395,7 +2426,7 @@ __device__ __forceinline__ double fold_column_f64(Rows src, int64_t N, const dou
             acc = acc + term_d1<SCORED>(v[u], factor_d(a, i + u), SCORED ? factor_d(s, i + u) : 1.0);
     }
     for (; i < N; ++i) acc = acc + term_d1<SCORED>(*src.row(i), factor_d(a, i), SCORED ? factor_d(s, i) : 1.0);
-    return FIN ? acc / divisor : acc;
+    return FIN ? div_d1(acc, divisor) : acc;
 }
 
 // The float64 pair fold: the lane's C pairs of the rows of src, in row order;
@@ -2448,7 +2479,7 @@ __device__ __forceinline__ void fold_pairs_f64(Rows src, int64_t N, const double
 #pragma unroll
         for (int c = 0; c < C; ++c)
             st16_wt<WT>(rs, (int)(16 * ((int)threadIdx.x + c * kBlock)),
-                        __builtin_bit_cast(u32x4, f64x2(acc[c] / divisor)));
+                        __builtin_bit_cast(u32x4, div_d2(acc[c], divisor)));
         return;
     }
 #pragma unroll
@@ -2813,8 +2844,18 @@ struct StreamDevice {
     StreamDevice& operator=(const StreamDevice&) = delete;
 };
 
-// Compute units of the current device (cached per device).
+// A pretended CU count for every launch geometry of this library's copy (0: the
+// device's own).  Only the bench library has a setter (fa_bench_set_cus): at 2
+// CUs a 100K-column model is dozens of tiles per block, so the tests walk a
+// block from tile to tile, and a band form through several bands, at shapes
+// that take milliseconds.  The product library never writes it.
+std::atomic<int> g_cu_override{0};
+
+// Compute units of the current device (cached per device; the override is
+// consulted first and never cached).
 int cu_count() {
+    const int over = g_cu_override.load(std::memory_order_relaxed);
+    if (over > 0) return over;
     static thread_local int cache[16] = {0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;

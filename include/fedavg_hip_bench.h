@@ -55,6 +55,28 @@ const char* fa_variant_name(int variant);
  * N clients x P params (16-B aligned rows) on a GPU with `cus` compute units
  * (<= 0: the current device's), e.g. "tile_4k", "gs_bands_16k"; "" if N or P < 1. */
 const char* fa_f32_pick_name(int64_t N, int64_t P, int64_t cus);
+/* [host, no GPU needed] Pretend the device has `cus` compute units (cus > 0)
+ * in every launch geometry and shape policy of THIS library, or use the real
+ * count again (0; a negative value counts as 0).  Returns the previous value.
+ * Process-wide, not per device or thread; not cached anywhere, so it holds
+ * from the next call on.  For the tests: at 2 CUs a block of every
+ * grid-stride, band and step form folds several tiles of a 100K-column model.
+ * While an override holds, this library's tuner keeps the policy form (nothing
+ * is measured, recorded or written to the tuner cache at a CU count the device
+ * does not have); clearing it restores the tuner's previous mode.  The product
+ * library has no such entry and never sees the override. */
+int fa_bench_set_cus(int cus);
+/* The product's fa_fold_f32 / fa_fold_f16 / fa_fold_f64 and fa_fedavg_f64_ptrs
+ * run from this library (same arguments, checks and host function), so that
+ * fa_bench_set_cus reaches their launch geometry. */
+int fa_bench_fold_f32(const float* X, int64_t N, int64_t P, int64_t ldx, const float* a, const float* s,
+                      const float* acc_in, float divisor, int finalize, float* out, void* stream);
+int fa_bench_fold_f16(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
+                      const uint16_t* acc_in, uint16_t divisor, int finalize, uint16_t* out, void* stream);
+int fa_bench_fold_f64(const double* X, int64_t N, int64_t P, int64_t ldx, const double* a, const double* s,
+                      const double* acc_in, double divisor, int finalize, double* out, void* stream);
+int fa_bench_fedavg_f64_ptrs(const double* const* xi, int64_t N, int64_t P, const double* a, const double* s,
+                             double divisor, int rows_aligned, double* out, void* stream);
 /* One kernel form of the product's fp32 / bf16 fold, by index (the forms the
  * shape policy and the tuner choose between: fa_num_*_forms, fa_*_form_name);
  * a plain one-shot fold.  Lets the tests check every form the tuner may pick. */
