@@ -420,8 +420,7 @@ int fold_f32_variant(const float* X, int64_t N, int64_t P, int64_t ldx, const fl
         case 90: rc = FA_VD(8, 32, 32, 3); break;
 #undef FA_VD
         case 91:
-            if (sc) launch_scalar<true, false, true>(st, X, N, P, ldx, a, s, acc_in, divisor, out);
-            else launch_scalar<false, false, true>(st, X, N, P, ldx, a, s, acc_in, divisor, out);
+            launch_scalar(st, sc, false, true, X, N, P, ldx, a, s, acc_in, divisor, out);
             break;
 #define FA_VT(U, C, NTS) launch_tile_flags<U, C, NTS>(st, sc, acc, fin, X, N, P, ldx, a, s, acc_in, divisor, out)
         case 92: rc = FA_VT(8, 1, false); break;
@@ -582,7 +581,7 @@ int fa_fedavg_rounds_form(void* r, int form, const void* X, int64_t N, int64_t l
     if (form < 0 || form >= kNumStepForms) return fail(FA_ERR_ARG, "unknown step form %d", form);
     StreamDevice on_stream_device(stream);
     return launch_step(*static_cast<RoundsState*>(r), form, (hipStream_t)stream, X, N, ldx, a, s, divisor, out,
-                       kStepSpecs[form].bf16 ? out_bf16 : nullptr, rounds, offsets);
+                       kStepSpecs[form].dtype == StepDtype::kBf16 ? out_bf16 : nullptr, rounds, offsets);
 }
 
 int fa_num_step_forms_f16(void) { return kNumStepFormsF16; }

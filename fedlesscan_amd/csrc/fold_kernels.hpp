@@ -42,6 +42,7 @@
 #include <mutex>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "fedavg_hip.h"
@@ -68,6 +69,26 @@ int check_launch(const char* what) {
     if (e != hipSuccess) return fail(FA_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     g_err[0] = 0;
     return FA_OK;
+}
+
+// A fold's (scored, accumulate, finalize) switches as template arguments:
+// f(SC, ACC, FIN) gets the std::bool_constant of each (SC.value in a template
+// argument list).  ALLF: every combination -- only the auto variants need them
+// (fa_fold_*); !ALLF: a plain fold with the divide (acc == false, fin == true,
+// whatever was passed: the tuning variants), so they instantiate two.
+template <bool ALLF = true, class F>
+void with_flags(bool sc, bool acc, bool fin, F f) {
+    constexpr std::true_type Y{};
+    constexpr std::false_type N{};
+    if constexpr (!ALLF) {
+        if (sc) f(Y, N, Y); else f(N, N, Y);
+    } else if (sc) {
+        if (acc) { if (fin) f(Y, Y, Y); else f(Y, Y, N); }
+        else     { if (fin) f(Y, N, Y); else f(Y, N, N); }
+    } else {
+        if (acc) { if (fin) f(N, Y, Y); else f(N, Y, N); }
+        else     { if (fin) f(N, N, Y); else f(N, N, N); }
+    }
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -872,19 +893,10 @@ int launch_ring_flags(hipStream_t st, bool sc, bool acc, bool fin, const float* 
     if (blocks * NW * 64 > (int64_t)0xFFFFFFFF)
         return fail(FA_ERR_ARG, "P=%lld too large for a ring launch", (long long)P);
     const dim3 grid((unsigned)blocks), block(NW * 64);
-#define FA_RG(SC, ACC, FIN) \
-    hipLaunchKernelGGL((k_fold_f32_ring<NW, R, TQ, S, SC, ACC, FIN>), grid, block, 0, st, X, N, P, ldx, a, s, \
-                       acc_in, d, out)
-    if constexpr (!ALLF) {
-        if (sc) FA_RG(true, false, true); else FA_RG(false, false, true);
-    } else if (sc) {
-        if (acc) { if (fin) FA_RG(true, true, true); else FA_RG(true, true, false); }
-        else     { if (fin) FA_RG(true, false, true); else FA_RG(true, false, false); }
-    } else {
-        if (acc) { if (fin) FA_RG(false, true, true); else FA_RG(false, true, false); }
-        else     { if (fin) FA_RG(false, false, true); else FA_RG(false, false, false); }
-    }
-#undef FA_RG
+    with_flags<ALLF>(sc, acc, fin, [&](auto SC, auto ACC, auto FIN) {
+        hipLaunchKernelGGL((k_fold_f32_ring<NW, R, TQ, S, SC.value, ACC.value, FIN.value>), grid, block, 0, st, X, N, P,
+                           ldx, a, s, acc_in, d, out);
+    });
     return FA_OK;
 }
 
@@ -1387,10 +1399,10 @@ __device__ __forceinline__ void st16(void* p, u32x4 v) { __builtin_nontemporal_s
 // ---------------------------------------------------------------------------
 // The 16-bit octet family (bf16 and float16: 8 columns per 16-byte load).  One
 // body per arithmetic serves every caller: an octet fold and a column fold for
-// bf16 (f32 accumulators), an octet fold and a column fold for float16 (packed
-// halves, with the ACC / FIN switches of the chunked fold), and one tile
-// dispatcher.  What differs between the callers is where row i starts, which
-// is a row source: a pitched matrix or a table of row bases.  bf16_tile, the
+// bf16 (f32 accumulators, here), the native-arithmetic unit fold and column
+// fold for float16 (packed halves; shared with float64, further down), and one
+// tile dispatcher.  What differs between the callers is where row i starts,
+// which is a row source: a pitched matrix or a table of row bases.  bf16_tile, the
 // stacked bf16 tile that also runs inside the one-launch step, keeps its tile
 // dispatch and its tail-column loop written out: through the shared ones the
 // compiler laid its kernels out differently, and the one-octet form measured
@@ -1651,279 +1663,6 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_bf16_rows_scalar(
 }
 
 // ---------------------------------------------------------------------------
-// float16: the reference's own arithmetic (numpy keeps a float16 layer float16
-// under Python-number weights), so every product, sum and the quotient round to
-// binary16.  The octet structure of the bf16 fold with packed-half arithmetic:
-// the 16-byte load IS the operand (8 halves in 4 registers, no unpack), the
-// accumulator is 4 packed registers per octet, v_pk_mul_f16 / v_pk_add_f16 do
-// two columns each (-ffp-contract=off keeps them apart).  The quotient is the
-// IEEE float32 divide of the exactly converted operands, rounded once to half:
-// float32 carries 24 >= 2 * 11 + 2 bits, so that double rounding equals the
-// correctly rounded binary16 quotient (numpy computes it the same way).  The
-// divisor arrives as a float32 kernel argument (the half's exact value), which
-// also keeps the compiler from narrowing the divide to its own half expansion.
-// ---------------------------------------------------------------------------
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ _Float16 h_bits(uint16_t b) { return __builtin_bit_cast(_Float16, b); }
-__device__ __forceinline__ uint16_t bits_h(_Float16 h) { return __builtin_bit_cast(uint16_t, h); }
-// Factor i of a binary16 factor array, through the scalar cache.  gfx950 has no
-// 16-bit scalar load, and a 16-bit vector load puts a wave-uniform value on the
-// row loads' counter (measured: the fold then ran 4-27 % behind the bf16 fold,
-// whose float32 factors are scalar loads).  So: the aligned dword that holds
-// the half -- the same 4-byte word, hence the same page and allocation granule
-// as the half itself -- and the half picked from it.  The factors are inputs
-// no launch writes, so the dword is read as constant memory: a scalar load
-// wherever it stands (behind a scheduling barrier the compiler otherwise falls
-// back to a vector load).
-typedef __attribute__((address_space(4))) const uint32_t cu32;
-__device__ __forceinline__ _Float16 factor_h(const uint16_t* __restrict__ a, int64_t i) {
-    const uint16_t* q = a + i;
-    const uint32_t w = *(cu32*)reinterpret_cast<const uint32_t*>(__builtin_align_down(q, 4));
-    return h_bits((uint16_t)(__builtin_is_aligned(q, 4) ? w : (w >> 16)));
-}
-template <class Ptr>  // const u32x4* or const gu32x4*
-__device__ __forceinline__ f16x8 ld_h8(Ptr p) { return __builtin_bit_cast(f16x8, __builtin_nontemporal_load(p)); }
-
-template <bool SCORED>
-__device__ __forceinline__ f16x8 term_h8(f16x8 x, _Float16 a, _Float16 s) {
-    f16x8 t = x * a;
-    if constexpr (SCORED) t = t * s;
-    return t;
-}
-template <bool SCORED>
-__device__ __forceinline__ _Float16 term_h1(_Float16 x, _Float16 a, _Float16 s) {
-    _Float16 t = x * a;
-    if constexpr (SCORED) t = t * s;
-    return t;
-}
-__device__ __forceinline__ f16x8 div_h8(f16x8 acc, float d) {
-    return __builtin_convertvector(__builtin_convertvector(acc, f32x8) / d, f16x8);
-}
-__device__ __forceinline__ _Float16 div_h1(_Float16 acc, float d) { return (_Float16)((float)acc / d); }
-
-// The float16 folds carry the ACC / FIN switches of the fp32 fold_quads (the
-// chunked fold, fa_fold_f16, uses them; every other caller is !ACC, FIN):
-//   ACC: the fold continues from acc_in (halves; may alias out: a lane reads
-//        its own octets before it writes them); !ACC: acc = t_0, not 0 + t_0,
-//        so a column of -0.0 stays -0.0.
-//   FIN: out = fl16(acc / divisor) (div_h8); !FIN: out = acc as halves.  Every
-//        add already rounds to binary16, so the halves carried from one chunk
-//        to the next are the accumulator itself: any cut of the rows gives the
-//        bits of one fa_fedavg_f16 over all of them.
-// The partial accumulator is stored with plain stores (the next chunk's fold
-// reads it back), the final result non-temporally.
-template <bool FIN>
-__device__ __forceinline__ void st_h8(u32x4* out, f16x8 acc, float divisor) {
-    if constexpr (FIN) st16(out, __builtin_bit_cast(u32x4, div_h8(acc, divisor)));
-    else *out = __builtin_bit_cast(u32x4, acc);
-}
-
-// One float16 column (a P % 8 tail lane, the one-column kernels)
-template <bool SCORED, bool ACC, bool FIN, class Rows>
-__device__ __forceinline__ uint16_t fold_column_f16(Rows src, int64_t N, const uint16_t* __restrict__ a,
-                                                    const uint16_t* __restrict__ s, const uint16_t* acc_in,
-                                                    float divisor) {
-    _Float16 acc;
-    int64_t i = 0;
-    if constexpr (ACC) {
-        acc = h_bits(*acc_in);
-    } else {
-        acc = term_h1<SCORED>(h_bits(*src.row(0)), factor_h(a, 0), SCORED ? factor_h(s, 0) : (_Float16)1);
-        i = 1;
-    }
-    for (; i < N; ++i)
-        acc = acc + term_h1<SCORED>(h_bits(*src.row(i)), factor_h(a, i), SCORED ? factor_h(s, i) : (_Float16)1);
-    return bits_h(FIN ? div_h1(acc, divisor) : acc);
-}
-
-// The float16 octet fold: the lane's C octets of the rows of src, in row
-// order; acc_in and out point at the lane's first octet.  WT (the one-launch
-// step, final results only): the quotient octets stored write-through over
-// the tile's wave-uniform base, as fold_octets stores outb -- no non-temporal
-// store there (no valid producer form for a round another stream reads).
-template <int U, int C, bool SCORED, bool ACC, bool FIN, int WT = 0, class Rows>
-__device__ __forceinline__ void fold_octets_f16(Rows src, int64_t N, const uint16_t* __restrict__ a,
-                                                const uint16_t* __restrict__ s, const u32x4* acc_in, float divisor,
-                                                u32x4* out) {
-    static_assert(!WT || (!ACC && FIN), "write-through stores are for final results");
-    f16x8 acc[C];
-    int64_t i = 0;
-    if constexpr (ACC) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = __builtin_bit_cast(f16x8, acc_in[c * kBlock]);
-    } else {
-        const auto* r = src.row(0);
-        const _Float16 a0 = factor_h(a, 0), s0 = SCORED ? factor_h(s, 0) : (_Float16)1;
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = term_h8<SCORED>(ld_h8(r + c * kBlock), a0, s0);
-        i = 1;
-    }
-    for (; i + U <= N; i += U) {
-        u32x4 v[U][C];
-        octets_ld<U, C>(v, src, i);
-        // 2 rows x 8 octets (and the deep unrolls, as the bf16 fold): every
-        // load of the group issued before the first add, the factors' scalar
-        // loads behind them.  Left to itself the scheduler interleaved the
-        // short packed-half adds and their waits with the row loads of this
-        // form (256 x 100M: 4.7 TB/s, 6.8 with the barrier).  The 8-row forms
-        // keep the compiler's schedule: behind a barrier their eight factor
-        // loads wait one after another (1024 x 67K: 0.116 against 0.093 ms)
-        if constexpr (U >= 16 || (U == 2 && C == 8)) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const _Float16 ai = factor_h(a, i + u), si = SCORED ? factor_h(s, i + u) : (_Float16)1;
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(__builtin_bit_cast(f16x8, v[u][c]), ai, si);
-        }
-    }
-    for (; i < N; ++i) {
-        const auto* r = src.row(i);
-        const _Float16 ai = factor_h(a, i), si = SCORED ? factor_h(s, i) : (_Float16)1;
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_h8<SCORED>(ld_h8(r + c * kBlock), ai, si);
-    }
-    if constexpr (WT) {  // the base: the tile's first octet (out - threadIdx.x, shared by every lane)
-        const __amdgpu_buffer_rsrc_t rs = wt_rsrc(reinterpret_cast<const void*>(
-            (uintptr_t)uniform64((int64_t)(uintptr_t)(out - threadIdx.x))));
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-            st16_wt<WT>(rs, (int)(16 * ((int)threadIdx.x + c * kBlock)),
-                        __builtin_bit_cast(u32x4, div_h8(acc[c], divisor)));
-        return;
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) st_h8<FIN>(out + c * kBlock, acc[c], divisor);
-}
-
-// One octet tile of a stacked float16 matrix (acc_in may alias out)
-template <int U, int C, bool SCORED, bool ACC, bool FIN, int WT = 0>
-__device__ __forceinline__ void f16_tile(int64_t bid, const uint16_t* __restrict__ X, int64_t N, int64_t P,
-                                         int64_t ldx, const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
-                                         const uint16_t* acc_in, float divisor, uint16_t* out) {
-    const int64_t ldo = ldx >> 3;
-    const u32x4* X8 = reinterpret_cast<const u32x4*>(X);
-    const u32x4* A8 = reinterpret_cast<const u32x4*>(acc_in);
-    u32x4* O8 = reinterpret_cast<u32x4*>(out);
-    octet_tile<C>(
-        bid, P,
-        [&](int64_t o) {
-            fold_octets_f16<U, C, SCORED, ACC, FIN, WT>(PitchedRows<u32x4>{X8 + o, ldo}, N, a, s,
-                                                        ACC ? A8 + o : nullptr, divisor, O8 + o);
-        },
-        [&](int64_t o) {
-            fold_octets_f16<U, 1, SCORED, ACC, FIN, WT>(PitchedRows<u32x4>{X8 + o, ldo}, N, a, s,
-                                                        ACC ? A8 + o : nullptr, divisor, O8 + o);
-        },
-        [&](int64_t col) {
-            for (; col < P; ++col)
-                out[col] = fold_column_f16<SCORED, ACC, FIN>(PitchedRows<uint16_t>{X + col, ldx}, N, a, s,
-                                                             ACC ? acc_in + col : nullptr, divisor);
-            // WT: these few plain stores are written back before the block publishes
-            wt_tail_release<WT>();
-        });
-}
-
-template <int U, int C, bool SCORED>
-__global__ __launch_bounds__(kBlock) void k_fedavg_f16_v8(
-    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
-    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
-    f16_tile<U, C, SCORED, false, true>(blockIdx.x, X, N, P, ldx, a, s, nullptr, divisor, out);
-}
-
-// grid-stride over octet tiles, as k_fedavg_bf16_gs
-template <int U, int C, bool SCORED>
-__global__ __launch_bounds__(kBlock) void k_fedavg_f16_gs(
-    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
-    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out,
-    int64_t ntiles) {
-    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
-        f16_tile<U, C, SCORED, false, true>(bid, X, N, P, ldx, a, s, nullptr, divisor, out);
-}
-
-// float16, one column per lane: any alignment / pitch
-template <bool SCORED>
-__global__ __launch_bounds__(kBlock) void k_fedavg_f16_scalar(
-    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
-    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
-    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (c >= P) return;
-    out[c] = fold_column_f16<SCORED, false, true>(PitchedRows<uint16_t>{X + c, ldx}, N, a, s, nullptr, divisor);
-}
-
-// float16 chunked fold (fa_fold_f16): the ACC / FIN forms of the same tile,
-// grid-stride with balanced passes set by the launch.
-template <int U, int C, bool SCORED, bool ACC, bool FIN>
-__global__ __launch_bounds__(kBlock) void k_fold_f16_gs(
-    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
-    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
-    const uint16_t* acc_in, float divisor, uint16_t* out, int64_t ntiles) {  // acc_in may alias out
-    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
-        f16_tile<U, C, SCORED, ACC, FIN>(bid, X, N, P, ldx, a, s, acc_in, divisor, out);
-}
-
-// chunked fold, one column per lane: rows, accumulator or output at any 2-B
-// offset, any pitch
-template <bool SCORED, bool ACC, bool FIN>
-__global__ __launch_bounds__(kBlock) void k_fold_f16_scalar(
-    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
-    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
-    const uint16_t* acc_in, float divisor, uint16_t* out) {  // acc_in may alias out
-    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (c >= P) return;
-    out[c] = fold_column_f16<SCORED, ACC, FIN>(PitchedRows<uint16_t>{X + c, ldx}, N, a, s,
-                                               ACC ? acc_in + c : nullptr, divisor);
-}
-
-// float16 list-of-rows form with every row 16-B aligned (fa_fedavg_f16_ptrs,
-// rows_aligned != 0): the stacked fold's body over a row table, hence its bits
-// over the same rows.  Grid-stride over octet tiles.
-template <int U, int C, bool SCORED>
-__global__ __launch_bounds__(kBlock) void k_fedavg_f16_rows_gs(
-    const uint16_t* const* __restrict__ xi, int64_t N, int64_t P, const uint16_t* __restrict__ a,
-    const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out, int64_t ntiles) {
-    u32x4* O8 = reinterpret_cast<u32x4*>(out);
-    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
-        octet_tile<C>(
-            bid, P,
-            [&](int64_t o) {
-                fold_octets_f16<U, C, SCORED, false, true>(TableRows<gu32x4>{xi, o}, N, a, s, nullptr, divisor, O8 + o);
-            },
-            [&](int64_t o) {
-                fold_octets_f16<U, 1, SCORED, false, true>(TableRows<gu32x4>{xi, o}, N, a, s, nullptr, divisor, O8 + o);
-            },
-            [&](int64_t col) {
-                for (; col < P; ++col)
-                    out[col] = fold_column_f16<SCORED, false, true>(TableRows<gu16>{xi, col}, N, a, s, nullptr, divisor);
-            });
-}
-
-// float16 list-of-rows form, rows at any 2-B offset: one column per lane, 8
-// rows of loads ahead of the ordered adds, the arithmetic of fold_column_f16
-template <bool SCORED>
-__global__ __launch_bounds__(kBlock) void k_fedavg_f16_rows_scalar(
-    const uint16_t* const* __restrict__ xi, int64_t N, int64_t P, const uint16_t* __restrict__ a,
-    const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
-    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (c >= P) return;
-    const TableRows<gu16> src{xi, c};
-    _Float16 acc = term_h1<SCORED>(h_bits(*src.row(0)), factor_h(a, 0), SCORED ? factor_h(s, 0) : (_Float16)1);
-    int64_t i = 1;
-    for (; i + 8 <= N; i += 8) {
-        uint16_t v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load(src.row(i + u));
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            acc = acc + term_h1<SCORED>(h_bits(v[u]), factor_h(a, i + u), SCORED ? factor_h(s, i + u) : (_Float16)1);
-    }
-    for (; i < N; ++i)
-        acc = acc + term_h1<SCORED>(h_bits(*src.row(i)), factor_h(a, i), SCORED ? factor_h(s, i) : (_Float16)1);
-    out[c] = bits_h(div_h1(acc, divisor));
-}
-
-// ---------------------------------------------------------------------------
 // One launch per exchange step (round 4, fa_fedavg_*_rounds).  Per-round
 // dynamic launches pay a tile-time of tail per round (the last tiles of a
 // round run on a few blocks while the others idle; measured: 256 x the C4
@@ -2147,10 +1886,39 @@ __device__ __forceinline__ void step_tiles(const StepTable& T, unsigned int* sig
     step_reset(sig);
 }
 
-// wide tiles: UB rows ahead x CB octets (quads) per lane; narrow: US x CS;
-// BAL: balanced rounds (step_tiles_bal).  One schedule per instantiation: both
-// inlined into one kernel made it ~4 % slower (code size: the unrolled tile
-// body four times over; profiles/r05_step/)
+// The schedule of every step kernel.  wide tiles: UB rows ahead x CB octets
+// (quads, pairs) per lane; narrow: US x CS; BAL: balanced rounds
+// (step_tiles_bal).  One schedule per instantiation: both inlined into one
+// kernel made it ~4 % slower (code size: the unrolled tile body four times
+// over; profiles/r05_step/)
+template <bool BAL, class Wide, class Narrow>
+__device__ __forceinline__ void step_run(const StepTable& T, unsigned int* sig, unsigned int epoch, Wide wide,
+                                         Narrow narrow) {
+    if constexpr (BAL) {
+        step_tiles_bal(T, sig, epoch, wide, narrow);
+    } else {
+        step_tiles(T, sig, epoch, [&](int g, int64_t bid) {
+            if (T.small[g]) narrow(g, bid);
+            else wide(g, bid);
+        });
+    }
+}
+// The same with the kernel's tile written once: tile(U, C, g, bid) takes its
+// shape as integral constants (decltype(U)::value rows ahead, decltype(C)::value
+// units per lane).
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <int UB, int CB, int US, int CS, bool BAL, class Tile>
+__device__ __forceinline__ void step_run(const StepTable& T, unsigned int* sig, unsigned int epoch, Tile tile) {
+    step_run<BAL>(
+        T, sig, epoch, [&](int g, int64_t bid) { tile(int_c<UB>{}, int_c<CB>{}, g, bid); },
+        [&](int g, int64_t bid) { tile(int_c<US>{}, int_c<CS>{}, g, bid); });
+}
+
+// The bf16 step keeps its schedule dispatch written out: through step_run the
+// compiler ordered two independent instructions of every tile's write-through
+// store the other way round, and every stacked bf16 kernel is held to the
+// instructions it had (profiles/native_refactor/).
 template <int UB, int CB, int US, int CS, bool SCORED, int B, bool BAL = false, int WTM = kWtAgent>
 __global__ __launch_bounds__(B) void k_fedavg_bf16_step(
     const uint16_t* __restrict__ X, int64_t N, int64_t ldx, const float* __restrict__ a,
@@ -2180,51 +1948,11 @@ template <int UB, int CB, int US, int CS, bool SCORED, int B, bool BAL = false, 
 __global__ __launch_bounds__(B) void k_fold_f32_step(
     const float* __restrict__ X, int64_t N, int64_t ldx, const float* __restrict__ a, const float* __restrict__ s,
     float divisor, float* __restrict__ out, StepTable T, unsigned int* sig, unsigned int epoch) {
-    auto wide = [&](int g, int64_t bid) {
+    step_run<UB, CB, US, CS, BAL>(T, sig, epoch, [&](auto U, auto C, int g, int64_t bid) {
         const int64_t c0 = T.col0[g];
-        fold_tile<UB, CB, true, SCORED, false, true, true, B, WTM>(bid, X + c0, N, T.width[g], ldx, a, s, nullptr,
-                                                                   divisor, out + T.ocol0[g]);
-    };
-    auto narrow = [&](int g, int64_t bid) {
-        const int64_t c0 = T.col0[g];
-        fold_tile<US, CS, true, SCORED, false, true, true, B, WTM>(bid, X + c0, N, T.width[g], ldx, a, s, nullptr,
-                                                                   divisor, out + T.ocol0[g]);
-    };
-    if constexpr (BAL) {
-        step_tiles_bal(T, sig, epoch, wide, narrow);
-    } else {
-        step_tiles(T, sig, epoch, [&](int g, int64_t bid) {
-            if (T.small[g]) narrow(g, bid);
-            else wide(g, bid);
-        });
-    }
-}
-
-// The float16 step: the schedules of k_fedavg_bf16_step over the float16 tile
-// (binary16 products, sums and quotient: the bits of fa_fedavg_f16 on each
-// round's columns), every quotient octet stored write-through.
-template <int UB, int CB, int US, int CS, bool SCORED, int B, bool BAL = false, int WTM = kWtAgent>
-__global__ __launch_bounds__(B) void k_fedavg_f16_step(
-    const uint16_t* __restrict__ X, int64_t N, int64_t ldx, const uint16_t* __restrict__ a,
-    const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out, StepTable T, unsigned int* sig,
-    unsigned int epoch) {
-    static_assert(B == kBlock, "octet tiles are kBlock lanes wide");
-    auto wide = [&](int g, int64_t bid) {
-        f16_tile<UB, CB, SCORED, false, true, WTM>(bid, X + T.col0[g], N, T.width[g], ldx, a, s, nullptr, divisor,
-                                                   out + T.ocol0[g]);
-    };
-    auto narrow = [&](int g, int64_t bid) {
-        f16_tile<US, CS, SCORED, false, true, WTM>(bid, X + T.col0[g], N, T.width[g], ldx, a, s, nullptr, divisor,
-                                                   out + T.ocol0[g]);
-    };
-    if constexpr (BAL) {
-        step_tiles_bal(T, sig, epoch, wide, narrow);
-    } else {
-        step_tiles(T, sig, epoch, [&](int g, int64_t bid) {
-            if (T.small[g]) narrow(g, bid);
-            else wide(g, bid);
-        });
-    }
+        fold_tile<decltype(U)::value, decltype(C)::value, true, SCORED, false, true, true, B, WTM>(
+            bid, X + c0, N, T.width[g], ldx, a, s, nullptr, divisor, out + T.ocol0[g]);
+    });
 }
 
 // Poll round flag `flag` until it reaches `epoch` (wrapping compare), then
@@ -2361,196 +2089,387 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f64(
 }
 
 // ---------------------------------------------------------------------------
-// The float64 pair family (fa_fold_f64, fa_fedavg_f64_ptrs): the arithmetic of
-// k_fedavg_f64_v2 -- double multiply, double add, the IEEE double divide, no
-// FMA -- over a row source, written the way fold_octets_f16 is.  A 16-byte
-// load holds a pair of columns; a lane owns C pairs spaced kBlock lanes apart
-// and issues U rows x C pairs of non-temporal loads ahead of the ordered adds.
-// The ACC / FIN switches are those of the float16 folds:
+// The native-arithmetic folds (float16 and float64): every product, every sum
+// and the quotient round to the element's own format, as the reference does
+// (numpy keeps a float16 layer float16 under Python-number weights, and a
+// float64 layer is double throughout); no FMA (-ffp-contract=off keeps multiply
+// and add apart).  One body per job -- a unit fold, a column fold, a stacked
+// tile, a row-table tile -- written over an arithmetic, of which there are two:
+//   HalfArith    8 columns per 16-byte unit (an octet).  The load IS the
+//     operand: 8 halves in 4 registers, no unpack, the accumulator 4 packed
+//     registers per octet, v_pk_mul_f16 / v_pk_add_f16 two columns each.  The
+//     quotient is the IEEE float32 divide of the exactly converted operands,
+//     rounded once to half: float32 carries 24 >= 2 * 11 + 2 bits, so that
+//     double rounding equals the correctly rounded binary16 quotient (numpy
+//     computes it the same way).  The divisor arrives as a float32 kernel
+//     argument (the half's exact value), which also keeps the compiler from
+//     narrowing the divide to its own half expansion.
+//   DoubleArith  2 columns per unit (a pair): the arithmetic of
+//     k_fedavg_f64_v2 -- double multiply, double add, div_d1.
+// A lane owns C units spaced kBlock lanes apart and issues U rows x C units of
+// non-temporal loads ahead of the ordered adds; where row i starts is a row
+// source (PitchedRows, TableRows).  The switches of the fp32 fold_quads (the
+// chunked folds fa_fold_f16 / fa_fold_f64 use them; every other caller is
+// !ACC, FIN):
 //   ACC: the fold continues from acc_in (may alias out: a lane reads its own
-//        pairs before it writes them); !ACC: acc = t_0, not 0 + t_0, so a
+//        units before it writes them); !ACC: acc = t_0, not 0 + t_0, so a
 //        column of -0.0 stays -0.0.
-//   FIN: out = fl64(acc / divisor); !FIN: out = acc.  Every add rounds to
-//        binary64, so the doubles carried from one chunk to the next are the
-//        accumulator itself: any cut of the rows gives the bits of one
-//        fa_fedavg_f64 over all of them.
+//   FIN: out = fl(acc / divisor); !FIN: out = acc.  Every add already rounds to
+//        the element's format, so the values carried from one chunk to the next
+//        are the accumulator itself: any cut of the rows gives the bits of one
+//        fa_fedavg_f16 / fa_fedavg_f64 over all of them.
+//   WT (the one-launch step, final results only): the quotient units stored
+//        write-through over the tile's wave-uniform base, as fold_octets stores
+//        outb -- no non-temporal store there (no valid producer form for a
+//        round another stream reads).
 // The partial accumulator is stored with plain stores (the next chunk's fold
-// reads it back), the final result non-temporally.  Row-table bases are read
-// as global-memory pointers (TableRows, for the reason written above it); the
-// factors are inputs no launch writes and are read as constant memory, so
-// they are scalar loads wherever they stand.
+// reads it back), the final result non-temporally.  The factors are inputs no
+// launch writes and are read as constant memory, so they are scalar loads
+// wherever they stand (behind a scheduling barrier the compiler otherwise falls
+// back to a vector load, which puts a wave-uniform value on the row loads'
+// counter).
 // ---------------------------------------------------------------------------
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(4))) const uint32_t cu32;
 typedef __attribute__((address_space(1))) const f64x2 gf64x2;
 typedef __attribute__((address_space(1))) const double gf64;
 typedef __attribute__((address_space(4))) const double cf64;
-__device__ __forceinline__ double factor_d(const double* __restrict__ a, int64_t i) { return *(cf64*)(a + i); }
 
-template <bool SCORED>
-__device__ __forceinline__ f64x2 term_d2(f64x2 x, double a, double s) {
-    f64x2 t = x * a;
+struct HalfArith {
+    typedef uint16_t E;    // an element, a factor: the half's bits
+    typedef _Float16 S;    // one column's arithmetic
+    typedef f16x8 V;       // a unit's arithmetic
+    typedef u32x4 Unit;    // a unit as loaded and stored
+    typedef gu32x4 GUnit;  // ... and as global memory (TableRows)
+    typedef gu16 GE;
+    typedef float D;       // the divisor
+    static constexpr int LG = 3;          // columns per unit, as a power of two
+    static constexpr bool kAhead = false;  // a tile's tail columns, an unaligned layer's: one row at a time
+    // 2 rows x 8 octets (and the deep unrolls, as the bf16 fold): every load of
+    // the group issued before the first add, the factors' scalar loads behind
+    // them.  Left to itself the scheduler interleaved the short packed-half
+    // adds and their waits with the row loads of this form (256 x 100M: 4.7
+    // TB/s, 6.8 with the barrier).  The 8-row forms keep the compiler's
+    // schedule: behind a barrier their eight factor loads wait one after
+    // another (1024 x 67K: 0.116 against 0.093 ms)
+    static constexpr bool barrier(int U, int C) { return U >= 16 || (U == 2 && C == 8); }
+    // gfx950 has no 16-bit scalar load, and a 16-bit vector load of a factor
+    // measured 4-27 % behind the bf16 fold, whose float32 factors are scalar
+    // loads.  So: the aligned dword that holds the half -- the same 4-byte
+    // word, hence the same page and allocation granule as the half itself --
+    // and the half picked from it.
+    static __device__ __forceinline__ S factor(const E* __restrict__ a, int64_t i) {
+        const E* q = a + i;
+        const uint32_t w = *(cu32*)reinterpret_cast<const uint32_t*>(__builtin_align_down(q, 4));
+        return val((E)(__builtin_is_aligned(q, 4) ? w : (w >> 16)));
+    }
+    static __device__ __forceinline__ S one() { return (S)1; }
+    static __device__ __forceinline__ S val(E b) { return __builtin_bit_cast(S, b); }
+    static __device__ __forceinline__ E bits(S h) { return __builtin_bit_cast(E, h); }
+    static __device__ __forceinline__ V vec(Unit u) { return __builtin_bit_cast(V, u); }
+    static __device__ __forceinline__ Unit unit(V v) { return __builtin_bit_cast(Unit, v); }
+    static __device__ __forceinline__ V div(V acc, D d) {
+        return __builtin_convertvector(__builtin_convertvector(acc, f32x8) / d, V);
+    }
+    static __device__ __forceinline__ S div(S acc, D d) { return (S)((float)acc / d); }
+};
+struct DoubleArith {
+    typedef double E;
+    typedef double S;
+    typedef f64x2 V;
+    typedef f64x2 Unit;
+    typedef gf64x2 GUnit;
+    typedef gf64 GE;
+    typedef double D;
+    static constexpr int LG = 1;
+    static constexpr bool kAhead = true;  // the P % 2 column: 8 rows of loads ahead
+    static constexpr bool barrier(int, int) { return false; }
+    static __device__ __forceinline__ S factor(const E* __restrict__ a, int64_t i) { return *(cf64*)(a + i); }
+    static __device__ __forceinline__ S one() { return 1.0; }
+    static __device__ __forceinline__ S val(E x) { return x; }
+    static __device__ __forceinline__ E bits(S x) { return x; }
+    static __device__ __forceinline__ V vec(Unit u) { return u; }
+    static __device__ __forceinline__ Unit unit(V v) { return v; }
+    static __device__ __forceinline__ V div(V acc, D d) { return div_d2(acc, d); }
+    static __device__ __forceinline__ S div(S acc, D d) { return div_d1(acc, d); }
+};
+
+// t_i = fl(fl(x*a) * s) of a unit or a column: two roundings, left to right
+template <bool SCORED, class X, class F>
+__device__ __forceinline__ X term(X x, F a, F s) {
+    X t = x * a;
     if constexpr (SCORED) t = t * s;
     return t;
 }
-template <bool SCORED>
-__device__ __forceinline__ double term_d1(double x, double a, double s) {
-    double t = x * a;
-    if constexpr (SCORED) t = t * s;
-    return t;
-}
-template <bool FIN>
-__device__ __forceinline__ void st_d2(f64x2* out, f64x2 acc, double divisor) {
-    if constexpr (FIN) __builtin_nontemporal_store(div_d2(acc, divisor), out);
-    else *out = acc;
+template <class A, bool FIN>
+__device__ __forceinline__ void st_unit(typename A::Unit* out, typename A::V acc, typename A::D divisor) {
+    if constexpr (FIN) __builtin_nontemporal_store(A::unit(A::div(acc, divisor)), out);
+    else *out = A::unit(acc);
 }
 
-// One float64 column (the P % 2 tail lane, the one-column kernels): 8 rows of
-// loads ahead of the ordered adds
-template <bool SCORED, bool ACC, bool FIN, class Rows>
-__device__ __forceinline__ double fold_column_f64(Rows src, int64_t N, const double* __restrict__ a,
-                                                  const double* __restrict__ s, const double* acc_in,
-                                                  double divisor) {
-    double acc;
+// One column (a tile's tail lane, the one-column kernels).  AHEAD: 8 rows of
+// loads ahead of the ordered adds.
+template <class A, bool SCORED, bool ACC, bool FIN, bool AHEAD, class Rows>
+__device__ __forceinline__ typename A::E fold_column(Rows src, int64_t N, const typename A::E* __restrict__ a,
+                                                     const typename A::E* __restrict__ s,
+                                                     const typename A::E* acc_in, typename A::D divisor) {
+    typename A::S acc;
     int64_t i = 0;
     if constexpr (ACC) {
-        acc = *acc_in;
+        acc = A::val(*acc_in);
     } else {
-        acc = term_d1<SCORED>(*src.row(0), factor_d(a, 0), SCORED ? factor_d(s, 0) : 1.0);
+        acc = term<SCORED>(A::val(*src.row(0)), A::factor(a, 0), SCORED ? A::factor(s, 0) : A::one());
         i = 1;
     }
-    for (; i + 8 <= N; i += 8) {
-        double v[8];
+    if constexpr (AHEAD) {
+        for (; i + 8 <= N; i += 8) {
+            typename A::E v[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load(src.row(i + u));
+            for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load(src.row(i + u));
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-            acc = acc + term_d1<SCORED>(v[u], factor_d(a, i + u), SCORED ? factor_d(s, i + u) : 1.0);
+            for (int u = 0; u < 8; ++u)
+                acc = acc + term<SCORED>(A::val(v[u]), A::factor(a, i + u), SCORED ? A::factor(s, i + u) : A::one());
+        }
     }
-    for (; i < N; ++i) acc = acc + term_d1<SCORED>(*src.row(i), factor_d(a, i), SCORED ? factor_d(s, i) : 1.0);
-    return FIN ? div_d1(acc, divisor) : acc;
+    for (; i < N; ++i)
+        acc = acc + term<SCORED>(A::val(*src.row(i)), A::factor(a, i), SCORED ? A::factor(s, i) : A::one());
+    return A::bits(FIN ? A::div(acc, divisor) : acc);
 }
 
-// The float64 pair fold: the lane's C pairs of the rows of src, in row order;
-// acc_in and out point at the lane's first pair.  WT (the one-launch step,
-// final results only): the quotient pairs stored write-through over the
-// tile's wave-uniform base, as fold_octets_f16 stores its octets -- no
-// non-temporal store there (no valid producer form for a round another stream
-// reads).
-template <int U, int C, bool SCORED, bool ACC, bool FIN, int WT = 0, class Rows>
-__device__ __forceinline__ void fold_pairs_f64(Rows src, int64_t N, const double* __restrict__ a,
-                                               const double* __restrict__ s, const f64x2* acc_in, double divisor,
-                                               f64x2* out) {
+// The unit fold: the lane's C units of the rows of src, in row order; acc_in
+// and out point at the lane's first unit.
+template <class A, int U, int C, bool SCORED, bool ACC, bool FIN, int WT = 0, class Rows>
+__device__ __forceinline__ void fold_units(Rows src, int64_t N, const typename A::E* __restrict__ a,
+                                           const typename A::E* __restrict__ s, const typename A::Unit* acc_in,
+                                           typename A::D divisor, typename A::Unit* out) {
     static_assert(!WT || (!ACC && FIN), "write-through stores are for final results");
-    f64x2 acc[C];
+    typedef typename A::S S;
+    typename A::V acc[C];
     int64_t i = 0;
     if constexpr (ACC) {
 #pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = acc_in[c * kBlock];
+        for (int c = 0; c < C; ++c) acc[c] = A::vec(acc_in[c * kBlock]);
     } else {
         const auto* r = src.row(0);
-        const double a0 = factor_d(a, 0), s0 = SCORED ? factor_d(s, 0) : 1.0;
+        const S a0 = A::factor(a, 0), s0 = SCORED ? A::factor(s, 0) : A::one();
 #pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = term_d2<SCORED>(__builtin_nontemporal_load(r + c * kBlock), a0, s0);
+        for (int c = 0; c < C; ++c) acc[c] = term<SCORED>(A::vec(__builtin_nontemporal_load(r + c * kBlock)), a0, s0);
         i = 1;
     }
     for (; i + U <= N; i += U) {
-        f64x2 v[U][C];
+        typename A::Unit v[U][C];
+        // octets go through octets_ld, pairs are loaded in place: each side as
+        // it was before the two folds shared this body, so that the compiler
+        // lays the row group out as it did (through octets_ld the float64
+        // kernels came out restructured, and the float16 ones without it;
+        // profiles/native_refactor/)
+        if constexpr (A::LG == 3) {
+            octets_ld<U, C>(v, src, i);
+        } else {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const auto* r = src.row(i + u);
+            for (int u = 0; u < U; ++u) {
+                const auto* r = src.row(i + u);
 #pragma unroll
-            for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
+                for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
+            }
         }
+        if constexpr (A::barrier(U, C)) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const double ai = factor_d(a, i + u), si = SCORED ? factor_d(s, i + u) : 1.0;
+            const S ai = A::factor(a, i + u), si = SCORED ? A::factor(s, i + u) : A::one();
 #pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_d2<SCORED>(v[u][c], ai, si);
+            for (int c = 0; c < C; ++c) acc[c] = acc[c] + term<SCORED>(A::vec(v[u][c]), ai, si);
         }
     }
     for (; i < N; ++i) {
         const auto* r = src.row(i);
-        const double ai = factor_d(a, i), si = SCORED ? factor_d(s, i) : 1.0;
+        const S ai = A::factor(a, i), si = SCORED ? A::factor(s, i) : A::one();
 #pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = acc[c] + term_d2<SCORED>(__builtin_nontemporal_load(r + c * kBlock), ai, si);
+        for (int c = 0; c < C; ++c)
+            acc[c] = acc[c] + term<SCORED>(A::vec(__builtin_nontemporal_load(r + c * kBlock)), ai, si);
     }
-    if constexpr (WT) {  // the base: the tile's first pair (out - threadIdx.x, shared by every lane)
+    if constexpr (WT) {  // the base: the tile's first unit (out - threadIdx.x, shared by every lane)
         const __amdgpu_buffer_rsrc_t rs = wt_rsrc(reinterpret_cast<const void*>(
             (uintptr_t)uniform64((int64_t)(uintptr_t)(out - threadIdx.x))));
 #pragma unroll
         for (int c = 0; c < C; ++c)
             st16_wt<WT>(rs, (int)(16 * ((int)threadIdx.x + c * kBlock)),
-                        __builtin_bit_cast(u32x4, div_d2(acc[c], divisor)));
+                        __builtin_bit_cast(u32x4, A::div(acc[c], divisor)));
         return;
     }
 #pragma unroll
-    for (int c = 0; c < C; ++c) st_d2<FIN>(out + c * kBlock, acc[c], divisor);
+    for (int c = 0; c < C; ++c) st_unit<A, FIN>(out + c * kBlock, acc[c], divisor);
 }
 
-// One pair tile of a stacked float64 matrix (acc_in may alias out): the tiling
-// of octet_tile with pairs in place of octets
-template <int U, int C, bool SCORED, bool ACC, bool FIN, int WT = 0>
-__device__ __forceinline__ void f64_tile(int64_t bid, const double* __restrict__ X, int64_t N, int64_t P,
-                                         int64_t ldx, const double* __restrict__ a, const double* __restrict__ s,
-                                         const double* acc_in, double divisor, double* out) {
-    const int64_t ldp = ldx >> 1;
-    const f64x2* X2 = reinterpret_cast<const f64x2*>(X);
-    const f64x2* A2 = reinterpret_cast<const f64x2*>(acc_in);
-    f64x2* O2 = reinterpret_cast<f64x2*>(out);
-    octet_tile<C, kBlock, 1>(
+// The trailing P % (1 << LG) columns from col on: up to 7 of an octet, the one
+// of a pair
+template <class A, class F>
+__device__ __forceinline__ void tail_columns(int64_t col, int64_t P, F f) {
+    if constexpr (A::LG == 1) {
+        f(col);
+    } else {
+        for (; col < P; ++col) f(col);
+    }
+}
+
+// One tile of a stacked matrix (acc_in may alias out)
+template <class A, int U, int C, bool SCORED, bool ACC, bool FIN, int WT = 0>
+__device__ __forceinline__ void native_tile(int64_t bid, const typename A::E* __restrict__ X, int64_t N, int64_t P,
+                                            int64_t ldx, const typename A::E* __restrict__ a,
+                                            const typename A::E* __restrict__ s, const typename A::E* acc_in,
+                                            typename A::D divisor, typename A::E* out) {
+    typedef typename A::Unit Unit;
+    const int64_t ldu = ldx >> A::LG;
+    const Unit* XU = reinterpret_cast<const Unit*>(X);
+    const Unit* AU = reinterpret_cast<const Unit*>(acc_in);
+    Unit* OU = reinterpret_cast<Unit*>(out);
+    octet_tile<C, kBlock, A::LG>(
         bid, P,
         [&](int64_t o) {
-            fold_pairs_f64<U, C, SCORED, ACC, FIN, WT>(PitchedRows<f64x2>{X2 + o, ldp}, N, a, s,
-                                                       ACC ? A2 + o : nullptr, divisor, O2 + o);
+            fold_units<A, U, C, SCORED, ACC, FIN, WT>(PitchedRows<Unit>{XU + o, ldu}, N, a, s, ACC ? AU + o : nullptr,
+                                                      divisor, OU + o);
         },
         [&](int64_t o) {
-            fold_pairs_f64<U, 1, SCORED, ACC, FIN, WT>(PitchedRows<f64x2>{X2 + o, ldp}, N, a, s,
-                                                       ACC ? A2 + o : nullptr, divisor, O2 + o);
+            fold_units<A, U, 1, SCORED, ACC, FIN, WT>(PitchedRows<Unit>{XU + o, ldu}, N, a, s, ACC ? AU + o : nullptr,
+                                                      divisor, OU + o);
         },
-        [&](int64_t col) {  // the P % 2 column
-            out[col] = fold_column_f64<SCORED, ACC, FIN>(PitchedRows<double>{X + col, ldx}, N, a, s,
-                                                         ACC ? acc_in + col : nullptr, divisor);
-            // WT: this one plain store is written back before the block publishes
+        [&](int64_t col) {
+            tail_columns<A>(col, P, [&](int64_t c) {
+                out[c] = fold_column<A, SCORED, ACC, FIN, A::kAhead>(PitchedRows<typename A::E>{X + c, ldx}, N, a, s,
+                                                                     ACC ? acc_in + c : nullptr, divisor);
+            });
+            // WT: these few plain stores are written back before the block publishes
             wt_tail_release<WT>();
         });
 }
 
-// float64 chunked fold (fa_fold_f64): grid-stride over pair tiles with
-// balanced passes set by the launch
+// One tile of a row table with every row 16-B aligned: the stacked tile's body
+// over the table, hence its bits over the same rows
+template <class A, int U, int C, bool SCORED>
+__device__ __forceinline__ void native_rows_tile(int64_t bid, const typename A::E* const* __restrict__ xi, int64_t N,
+                                                 int64_t P, const typename A::E* __restrict__ a,
+                                                 const typename A::E* __restrict__ s, typename A::D divisor,
+                                                 typename A::E* __restrict__ out) {
+    typedef typename A::E E;
+    typename A::Unit* OU = reinterpret_cast<typename A::Unit*>(out);
+    octet_tile<C, kBlock, A::LG>(
+        bid, P,
+        [&](int64_t o) {
+            fold_units<A, U, C, SCORED, false, true>(TableRows<typename A::GUnit, E>{xi, o}, N, a, s, nullptr, divisor,
+                                                     OU + o);
+        },
+        [&](int64_t o) {
+            fold_units<A, U, 1, SCORED, false, true>(TableRows<typename A::GUnit, E>{xi, o}, N, a, s, nullptr, divisor,
+                                                     OU + o);
+        },
+        [&](int64_t col) {
+            tail_columns<A>(col, P, [&](int64_t c) {
+                out[c] = fold_column<A, SCORED, false, true, A::kAhead>(TableRows<typename A::GE, E>{xi, c}, N, a, s,
+                                                                        nullptr, divisor);
+            });
+        });
+}
+
+// ---- float16 kernels ------------------------------------------------------
+// one block per octet tile
+template <int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f16_v8(
+    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
+    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
+    native_tile<HalfArith, U, C, SCORED, false, true>(blockIdx.x, X, N, P, ldx, a, s, nullptr, divisor, out);
+}
+
+// grid-stride over octet tiles, as k_fedavg_bf16_gs
+template <int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f16_gs(
+    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
+    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out,
+    int64_t ntiles) {
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        native_tile<HalfArith, U, C, SCORED, false, true>(bid, X, N, P, ldx, a, s, nullptr, divisor, out);
+}
+
+// float16, one column per lane: any alignment / pitch
+template <bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f16_scalar(
+    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
+    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P) return;
+    out[c] = fold_column<HalfArith, SCORED, false, true, false>(PitchedRows<uint16_t>{X + c, ldx}, N, a, s, nullptr,
+                                                                divisor);
+}
+
+// float16 chunked fold (fa_fold_f16): the ACC / FIN forms of the same tile,
+// grid-stride with balanced passes set by the launch.
+template <int U, int C, bool SCORED, bool ACC, bool FIN>
+__global__ __launch_bounds__(kBlock) void k_fold_f16_gs(
+    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
+    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
+    const uint16_t* acc_in, float divisor, uint16_t* out, int64_t ntiles) {  // acc_in may alias out
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        native_tile<HalfArith, U, C, SCORED, ACC, FIN>(bid, X, N, P, ldx, a, s, acc_in, divisor, out);
+}
+
+// chunked fold, one column per lane: rows, accumulator or output at any 2-B
+// offset, any pitch
+template <bool SCORED, bool ACC, bool FIN>
+__global__ __launch_bounds__(kBlock) void k_fold_f16_scalar(
+    const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
+    const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
+    const uint16_t* acc_in, float divisor, uint16_t* out) {  // acc_in may alias out
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P) return;
+    out[c] = fold_column<HalfArith, SCORED, ACC, FIN, false>(PitchedRows<uint16_t>{X + c, ldx}, N, a, s,
+                                                             ACC ? acc_in + c : nullptr, divisor);
+}
+
+// float16 list-of-rows form with every row 16-B aligned (fa_fedavg_f16_ptrs,
+// rows_aligned != 0), grid-stride over octet tiles
+template <int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f16_rows_gs(
+    const uint16_t* const* __restrict__ xi, int64_t N, int64_t P, const uint16_t* __restrict__ a,
+    const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out, int64_t ntiles) {
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        native_rows_tile<HalfArith, U, C, SCORED>(bid, xi, N, P, a, s, divisor, out);
+}
+
+// float16 list-of-rows form, rows at any 2-B offset: one column per lane, 8
+// rows of loads ahead of the ordered adds
+template <bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_f16_rows_scalar(
+    const uint16_t* const* __restrict__ xi, int64_t N, int64_t P, const uint16_t* __restrict__ a,
+    const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P) return;
+    out[c] = fold_column<HalfArith, SCORED, false, true, true>(TableRows<gu16>{xi, c}, N, a, s, nullptr, divisor);
+}
+
+// The float16 step: the schedules of k_fedavg_bf16_step over the float16 tile
+// (the bits of fa_fedavg_f16 on each round's columns), every quotient octet
+// stored write-through.
+template <int UB, int CB, int US, int CS, bool SCORED, int B, bool BAL = false, int WTM = kWtAgent>
+__global__ __launch_bounds__(B) void k_fedavg_f16_step(
+    const uint16_t* __restrict__ X, int64_t N, int64_t ldx, const uint16_t* __restrict__ a,
+    const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out, StepTable T, unsigned int* sig,
+    unsigned int epoch) {
+    static_assert(B == kBlock, "octet tiles are kBlock lanes wide");
+    step_run<UB, CB, US, CS, BAL>(T, sig, epoch, [&](auto U, auto C, int g, int64_t bid) {
+        native_tile<HalfArith, decltype(U)::value, decltype(C)::value, SCORED, false, true, WTM>(
+            bid, X + T.col0[g], N, T.width[g], ldx, a, s, nullptr, divisor, out + T.ocol0[g]);
+    });
+}
+
+// ---- float64 kernels: the float16 ones over pairs ----------------------------
+// float64 chunked fold (fa_fold_f64)
 template <int U, int C, bool SCORED, bool ACC, bool FIN>
 __global__ __launch_bounds__(kBlock) void k_fold_f64_gs(
     const double* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
     const double* __restrict__ a, const double* __restrict__ s,
     const double* acc_in, double divisor, double* out, int64_t ntiles) {  // acc_in may alias out
     for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
-        f64_tile<U, C, SCORED, ACC, FIN>(bid, X, N, P, ldx, a, s, acc_in, divisor, out);
-}
-
-// The float64 step: the schedules of k_fedavg_f16_step over the float64 pair
-// tile (double products, ordered double sums, the IEEE double divide: the bits
-// of fa_fedavg_f64 on each round's columns), every quotient pair stored
-// write-through; agent scope only.
-template <int UB, int CB, int US, int CS, bool SCORED, int B, bool BAL = false, int WTM = kWtAgent>
-__global__ __launch_bounds__(B) void k_fedavg_f64_step(
-    const double* __restrict__ X, int64_t N, int64_t ldx, const double* __restrict__ a,
-    const double* __restrict__ s, double divisor, double* __restrict__ out, StepTable T, unsigned int* sig,
-    unsigned int epoch) {
-    static_assert(B == kBlock, "pair tiles are kBlock lanes wide");
-    auto wide = [&](int g, int64_t bid) {
-        f64_tile<UB, CB, SCORED, false, true, WTM>(bid, X + T.col0[g], N, T.width[g], ldx, a, s, nullptr, divisor,
-                                                   out + T.ocol0[g]);
-    };
-    auto narrow = [&](int g, int64_t bid) {
-        f64_tile<US, CS, SCORED, false, true, WTM>(bid, X + T.col0[g], N, T.width[g], ldx, a, s, nullptr, divisor,
-                                                   out + T.ocol0[g]);
-    };
-    if constexpr (BAL) {
-        step_tiles_bal(T, sig, epoch, wide, narrow);
-    } else {
-        step_tiles(T, sig, epoch, [&](int g, int64_t bid) {
-            if (T.small[g]) narrow(g, bid);
-            else wide(g, bid);
-        });
-    }
+        native_tile<DoubleArith, U, C, SCORED, ACC, FIN>(bid, X, N, P, ldx, a, s, acc_in, divisor, out);
 }
 
 // chunked fold, one column per lane: rows, accumulator or output at any 8-B
@@ -2562,32 +2481,18 @@ __global__ __launch_bounds__(kBlock) void k_fold_f64_scalar(
     const double* acc_in, double divisor, double* out) {  // acc_in may alias out
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= P) return;
-    out[c] = fold_column_f64<SCORED, ACC, FIN>(PitchedRows<double>{X + c, ldx}, N, a, s,
-                                               ACC ? acc_in + c : nullptr, divisor);
+    out[c] = fold_column<DoubleArith, SCORED, ACC, FIN, true>(PitchedRows<double>{X + c, ldx}, N, a, s,
+                                                              ACC ? acc_in + c : nullptr, divisor);
 }
 
 // float64 list-of-rows form with every row 16-B aligned (fa_fedavg_f64_ptrs,
-// rows_aligned != 0): the pair fold over a row table, grid-stride over pair tiles
+// rows_aligned != 0), grid-stride over pair tiles
 template <int U, int C, bool SCORED>
 __global__ __launch_bounds__(kBlock) void k_fedavg_f64_rows_gs(
     const double* const* __restrict__ xi, int64_t N, int64_t P, const double* __restrict__ a,
     const double* __restrict__ s, double divisor, double* __restrict__ out, int64_t ntiles) {
-    f64x2* O2 = reinterpret_cast<f64x2*>(out);
     for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
-        octet_tile<C, kBlock, 1>(
-            bid, P,
-            [&](int64_t o) {
-                fold_pairs_f64<U, C, SCORED, false, true>(TableRows<gf64x2, double>{xi, o}, N, a, s, nullptr, divisor,
-                                                          O2 + o);
-            },
-            [&](int64_t o) {
-                fold_pairs_f64<U, 1, SCORED, false, true>(TableRows<gf64x2, double>{xi, o}, N, a, s, nullptr, divisor,
-                                                          O2 + o);
-            },
-            [&](int64_t col) {
-                out[col] = fold_column_f64<SCORED, false, true>(TableRows<gf64, double>{xi, col}, N, a, s, nullptr,
-                                                                divisor);
-            });
+        native_rows_tile<DoubleArith, U, C, SCORED>(bid, xi, N, P, a, s, divisor, out);
 }
 
 // float64 list-of-rows form, rows at any 8-B offset: one column per lane
@@ -2597,7 +2502,22 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f64_rows_scalar(
     const double* __restrict__ s, double divisor, double* __restrict__ out) {
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= P) return;
-    out[c] = fold_column_f64<SCORED, false, true>(TableRows<gf64, double>{xi, c}, N, a, s, nullptr, divisor);
+    out[c] = fold_column<DoubleArith, SCORED, false, true, true>(TableRows<gf64, double>{xi, c}, N, a, s, nullptr,
+                                                                 divisor);
+}
+
+// The float64 step (the bits of fa_fedavg_f64 on each round's columns), every
+// quotient pair stored write-through; agent scope only.
+template <int UB, int CB, int US, int CS, bool SCORED, int B, bool BAL = false, int WTM = kWtAgent>
+__global__ __launch_bounds__(B) void k_fedavg_f64_step(
+    const double* __restrict__ X, int64_t N, int64_t ldx, const double* __restrict__ a,
+    const double* __restrict__ s, double divisor, double* __restrict__ out, StepTable T, unsigned int* sig,
+    unsigned int epoch) {
+    static_assert(B == kBlock, "pair tiles are kBlock lanes wide");
+    step_run<UB, CB, US, CS, BAL>(T, sig, epoch, [&](auto U, auto C, int g, int64_t bid) {
+        native_tile<DoubleArith, decltype(U)::value, decltype(C)::value, SCORED, false, true, WTM>(
+            bid, X + T.col0[g], N, T.width[g], ldx, a, s, nullptr, divisor, out + T.ocol0[g]);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2713,36 +2633,41 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_bf16_layers(
     }
 }
 
+// The float16 and float64 layer-table kernels: one loop -- the layer_tile
+// search, the unaligned layer's column path, the tile call -- over the column
+// body and the row-table tile of their own kernels (an unaligned float16 layer:
+// one row at a time, as k_fedavg_f16_scalar).  The fp32 and bf16 kernels above
+// keep the loop written out: through a shared one the compiler laid their
+// preheaders and exits out differently (profiles/native_refactor/).
+template <class A, int U, int C, bool SCORED>
+__device__ __forceinline__ void native_layers(const typename A::E* const* __restrict__ xi,
+                                              const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N,
+                                              const typename A::E* __restrict__ a, const typename A::E* __restrict__ s,
+                                              typename A::D divisor, typename A::E* __restrict__ out, int64_t ntiles) {
+    typedef typename A::E E;
+    int64_t l = 0;
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+        const LayerTile t = layer_tile(plan, L, bid, l);
+        l = t.l;
+        const E* const* x = xi + l * N;
+        E* o = out + t.offset;
+        if (!t.aligned) {
+            const int64_t c = t.bid * kBlock + threadIdx.x;
+            if (c < t.cols)
+                o[c] = fold_column<A, SCORED, false, true, A::kAhead>(TableRows<typename A::GE, E>{x, c}, N, a, s,
+                                                                      nullptr, divisor);
+            continue;
+        }
+        native_rows_tile<A, U, C, SCORED>(t.bid, x, N, t.cols, a, s, divisor, o);
+    }
+}
+
 template <int U, int C, bool SCORED>
 __global__ __launch_bounds__(kBlock) void k_fedavg_f16_layers(
     const uint16_t* const* __restrict__ xi, const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N,
     const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out,
     int64_t ntiles) {
-    int64_t l = 0;
-    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-        const LayerTile t = layer_tile(plan, L, bid, l);
-        l = t.l;
-        const uint16_t* const* x = xi + l * N;
-        uint16_t* o = out + t.offset;
-        if (!t.aligned) {
-            const int64_t c = t.bid * kBlock + threadIdx.x;
-            if (c < t.cols) o[c] = fold_column_f16<SCORED, false, true>(TableRows<gu16>{x, c}, N, a, s, nullptr, divisor);
-            continue;
-        }
-        u32x4* O8 = reinterpret_cast<u32x4*>(o);
-        octet_tile<C>(
-            t.bid, t.cols,
-            [&](int64_t q) {
-                fold_octets_f16<U, C, SCORED, false, true>(TableRows<gu32x4>{x, q}, N, a, s, nullptr, divisor, O8 + q);
-            },
-            [&](int64_t q) {
-                fold_octets_f16<U, 1, SCORED, false, true>(TableRows<gu32x4>{x, q}, N, a, s, nullptr, divisor, O8 + q);
-            },
-            [&](int64_t col) {
-                for (; col < t.cols; ++col)
-                    o[col] = fold_column_f16<SCORED, false, true>(TableRows<gu16>{x, col}, N, a, s, nullptr, divisor);
-            });
-    }
+    native_layers<HalfArith, U, C, SCORED>(xi, plan, L, N, a, s, divisor, out, ntiles);
 }
 
 template <int U, int C, bool SCORED>
@@ -2750,34 +2675,7 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f64_layers(
     const double* const* __restrict__ xi, const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N,
     const double* __restrict__ a, const double* __restrict__ s, double divisor, double* __restrict__ out,
     int64_t ntiles) {
-    int64_t l = 0;
-    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-        const LayerTile t = layer_tile(plan, L, bid, l);
-        l = t.l;
-        const double* const* x = xi + l * N;
-        double* o = out + t.offset;
-        if (!t.aligned) {
-            const int64_t c = t.bid * kBlock + threadIdx.x;
-            if (c < t.cols)
-                o[c] = fold_column_f64<SCORED, false, true>(TableRows<gf64, double>{x, c}, N, a, s, nullptr, divisor);
-            continue;
-        }
-        f64x2* O2 = reinterpret_cast<f64x2*>(o);
-        octet_tile<C, kBlock, 1>(
-            t.bid, t.cols,
-            [&](int64_t q) {
-                fold_pairs_f64<U, C, SCORED, false, true>(TableRows<gf64x2, double>{x, q}, N, a, s, nullptr, divisor,
-                                                          O2 + q);
-            },
-            [&](int64_t q) {
-                fold_pairs_f64<U, 1, SCORED, false, true>(TableRows<gf64x2, double>{x, q}, N, a, s, nullptr, divisor,
-                                                          O2 + q);
-            },
-            [&](int64_t col) {
-                o[col] = fold_column_f64<SCORED, false, true>(TableRows<gf64, double>{x, col}, N, a, s, nullptr,
-                                                              divisor);
-            });
-    }
+    native_layers<DoubleArith, U, C, SCORED>(xi, plan, L, N, a, s, divisor, out, ntiles);
 }
 
 // numpy integer semantics: product and fold in the input dtype with
@@ -3059,16 +2957,10 @@ int launch_tile_flags(hipStream_t st, bool sc, bool acc, bool fin, const float* 
     const int64_t tiles = (units + per_block - 1) / per_block;
     if (tiles > 0x7FFFFFFF) return fail(FA_ERR_ARG, "P=%lld too large for a tile launch", (long long)P);
     const dim3 grid((unsigned)tiles), block(kBlock);
-#define FA_T(SC, ACC, FIN) \
-    hipLaunchKernelGGL((k_fold_f32_tile<U, C, true, SC, ACC, FIN, NTS>), grid, block, 0, st, X, N, P, ldx, a, s, acc_in, d, out)
-    if (sc) {
-        if (acc) { if (fin) FA_T(true, true, true); else FA_T(true, true, false); }
-        else     { if (fin) FA_T(true, false, true); else FA_T(true, false, false); }
-    } else {
-        if (acc) { if (fin) FA_T(false, true, true); else FA_T(false, true, false); }
-        else     { if (fin) FA_T(false, false, true); else FA_T(false, false, false); }
-    }
-#undef FA_T
+    with_flags(sc, acc, fin, [&](auto SC, auto ACC, auto FIN) {
+        hipLaunchKernelGGL((k_fold_f32_tile<U, C, true, SC.value, ACC.value, FIN.value, NTS>), grid, block, 0, st, X, N,
+                           P, ldx, a, s, acc_in, d, out);
+    });
     return FA_OK;
 }
 
@@ -3078,17 +2970,9 @@ int launch_tile_flags(hipStream_t st, bool sc, bool acc, bool fin, const float* 
 template <int U, int C, bool NTS, int B = kBlock, bool ALLF = false>
 void launch_gs_flags(hipStream_t st, int per_cu, bool sc, bool acc, bool fin, const float* X, int64_t N, int64_t P,
                      int64_t ldx, const float* a, const float* s, const float* acc_in, float d, float* out) {
-#define FA_G(SC, ACC, FIN) launch_gs<U, C, true, SC, ACC, FIN, NTS, B>(st, per_cu, X, N, P, ldx, a, s, acc_in, d, out)
-    if constexpr (!ALLF) {
-        if (sc) FA_G(true, false, true); else FA_G(false, false, true);
-    } else if (sc) {
-        if (acc) { if (fin) FA_G(true, true, true); else FA_G(true, true, false); }
-        else     { if (fin) FA_G(true, false, true); else FA_G(true, false, false); }
-    } else {
-        if (acc) { if (fin) FA_G(false, true, true); else FA_G(false, true, false); }
-        else     { if (fin) FA_G(false, false, true); else FA_G(false, false, false); }
-    }
-#undef FA_G
+    with_flags<ALLF>(sc, acc, fin, [&](auto SC, auto ACC, auto FIN) {
+        launch_gs<U, C, true, SC.value, ACC.value, FIN.value, NTS, B>(st, per_cu, X, N, P, ldx, a, s, acc_in, d, out);
+    });
 }
 
 // Column bands: the fold as several back-to-back balanced grid-stride
@@ -3116,11 +3000,12 @@ void launch_gs_bands(hipStream_t st, int passes, bool sc, bool acc, bool fin, co
     }
 }
 
-template <bool SC, bool ACC, bool FIN>
-void launch_scalar(hipStream_t st, const float* X, int64_t N, int64_t P, int64_t ldx, const float* a,
-                   const float* s, const float* acc_in, float d, float* out) {
-    hipLaunchKernelGGL((k_fold_f32_scalar<SC, ACC, FIN>), grid_for(P), dim3(kBlock), 0, st, X, N, P, ldx,
-                       a, s, acc_in, d, out);
+inline void launch_scalar(hipStream_t st, bool sc, bool acc, bool fin, const float* X, int64_t N, int64_t P,
+                          int64_t ldx, const float* a, const float* s, const float* acc_in, float d, float* out) {
+    with_flags(sc, acc, fin, [&](auto SC, auto ACC, auto FIN) {
+        hipLaunchKernelGGL((k_fold_f32_scalar<SC.value, ACC.value, FIN.value>), grid_for(P), dim3(kBlock), 0, st, X, N,
+                           P, ldx, a, s, acc_in, d, out);
+    });
 }
 
 // Even-split fold (k_fold_f32_even): G blocks, per = ceil(nq / G) quads each.
@@ -3132,19 +3017,10 @@ void launch_even_flags(hipStream_t st, int64_t G, bool sc, bool acc, bool fin, c
     int64_t per = (nq + G - 1) / G;
     if (per < 1) per = 1;
     const int64_t grid = nq > 0 ? (nq + per - 1) / per : 1;  // no empty trailing blocks
-#define FA_E(SC, ACC, FIN)                                                                                   \
-    hipLaunchKernelGGL((k_fold_f32_even<U, C, SC, ACC, FIN>), dim3((unsigned)grid), dim3(kBlock), 0, st, X, N, P, \
-                       ldx, a, s, acc_in, d, out, per)
-    if constexpr (!ALLF) {
-        if (sc) FA_E(true, false, true); else FA_E(false, false, true);
-    } else if (sc) {
-        if (acc) { if (fin) FA_E(true, true, true); else FA_E(true, true, false); }
-        else     { if (fin) FA_E(true, false, true); else FA_E(true, false, false); }
-    } else {
-        if (acc) { if (fin) FA_E(false, true, true); else FA_E(false, true, false); }
-        else     { if (fin) FA_E(false, false, true); else FA_E(false, false, false); }
-    }
-#undef FA_E
+    with_flags<ALLF>(sc, acc, fin, [&](auto SC, auto ACC, auto FIN) {
+        hipLaunchKernelGGL((k_fold_f32_even<U, C, SC.value, ACC.value, FIN.value>), dim3((unsigned)grid), dim3(kBlock),
+                           0, st, X, N, P, ldx, a, s, acc_in, d, out, per);
+    });
 }
 
 // Quads per lane of the even split: the fewest that cover a block's range in
@@ -3177,19 +3053,10 @@ int launch_lds_flags(hipStream_t st, bool sc, bool acc, bool fin, const float* X
     if (blocks * NW * 64 > (int64_t)0xFFFFFFFF)  // work-items per launch dimension
         return fail(FA_ERR_ARG, "P=%lld too large for an LDS-staged launch", (long long)P);
     const dim3 grid((unsigned)blocks), block(NW * 64);
-#define FA_L(SC, ACC, FIN)                                                                                   \
-    hipLaunchKernelGGL((k_fold_f32_lds<NW, R, TQ, SC, ACC, FIN, DEPTH, ROWS, COLF, LOPT, DW>), grid, block, 0, st, X, N, P, ldx, a, s, \
-                       acc_in, d, out)
-    if constexpr (!ALLF) {
-        if (sc) FA_L(true, false, true); else FA_L(false, false, true);
-    } else if (sc) {
-        if (acc) { if (fin) FA_L(true, true, true); else FA_L(true, true, false); }
-        else     { if (fin) FA_L(true, false, true); else FA_L(true, false, false); }
-    } else {
-        if (acc) { if (fin) FA_L(false, true, true); else FA_L(false, true, false); }
-        else     { if (fin) FA_L(false, false, true); else FA_L(false, false, false); }
-    }
-#undef FA_L
+    with_flags<ALLF>(sc, acc, fin, [&](auto SC, auto ACC, auto FIN) {
+        hipLaunchKernelGGL((k_fold_f32_lds<NW, R, TQ, SC.value, ACC.value, FIN.value, DEPTH, ROWS, COLF, LOPT, DW>),
+                           grid, block, 0, st, X, N, P, ldx, a, s, acc_in, d, out);
+    });
     return FA_OK;
 }
 
@@ -3265,18 +3132,18 @@ void launch_octet_bands(const Fold& f, hipStream_t st, int passes, const uint16_
 // statically, and a dynamic pool of narrow tiles (US x CS) over the step's
 // last columns, sized in passes of the grid over wide tiles (pool100 = 100:
 // one pass; 0: every tile static).  256-thread blocks, one per CU.
+// The rows' dtype; factors and results: float32 for kF32 and kBf16 (which may
+// also write an RNE bf16 copy), the rows' own for kF16 and kF64.
+enum class StepDtype { kF32, kBf16, kF16, kF64 };
 struct StepSpec {
     const char* name;
-    bool bf16;
+    StepDtype dtype;
     int ub, cb, us, cs, pool100;
     bool last_only = false;   // the pool never reaches past the last round's columns
     bool round_tail = false;  // each round but the last: whole passes of wide tiles, the rest in narrow static tiles
     bool bal = false;         // balanced rounds: each round's wide tiles over its own balanced block count
-    bool f16 = false;         // float16 rows, factors and result (kStepSpecsF16); bf16 is false there
-    bool f64 = false;         // float64 rows, factors and result (kStepSpecsF64); bf16 and f16 are false there
-    constexpr bool octets() const { return bf16 || f16; }  // 16-bit elements
     // columns per 16-byte unit: an octet of 16-bit elements, a quad of fp32, a pair of float64
-    constexpr int ucols() const { return octets() ? 8 : f64 ? 2 : 4; }
+    constexpr int ucols() const { return dtype == StepDtype::kF32 ? 4 : dtype == StepDtype::kF64 ? 2 : 8; }
 };
 // The policy's two forms and one comparison form per dtype beside the round-4
 // bf16 policy (the bench library and the GPU tests run every one).  Round 4
@@ -3304,14 +3171,23 @@ struct StepSpec {
 //   f32_step_bal_u8c4                comparison: the fp32 step with balanced
 //     rounds
 constexpr StepSpec kStepSpecs[] = {
-    {"bf16_step_bal_u8c4", true, 8, 4, 8, 2, 0, true, false, true},
-    {"f32_step_sd_u8c4_p75", false, 8, 4, 16, 1, 75},
-    {"bf16_step_rt_u8c4n8c2_p100_last", true, 8, 4, 8, 2, 100, true, true},
-    {"bf16_step_static_u8c4", true, 8, 4, 8, 4, 0},
-    {"f32_step_bal_u8c4", false, 8, 4, 16, 1, 0, true, false, true},
+    {"bf16_step_bal_u8c4", StepDtype::kBf16, 8, 4, 8, 2, 0, true, false, true},
+    {"f32_step_sd_u8c4_p75", StepDtype::kF32, 8, 4, 16, 1, 75},
+    {"bf16_step_rt_u8c4n8c2_p100_last", StepDtype::kBf16, 8, 4, 8, 2, 100, true, true},
+    {"bf16_step_static_u8c4", StepDtype::kBf16, 8, 4, 8, 4, 0},
+    {"f32_step_bal_u8c4", StepDtype::kF32, 8, 4, 16, 1, 0, true, false, true},
 };
+// Form f of a table, or null: the one bounds check; and its name ("" if none)
+template <int K>
+constexpr const StepSpec* step_form(const StepSpec (&specs)[K], int f) {
+    return (f >= 0 && f < K) ? &specs[f] : nullptr;
+}
+template <int K>
+constexpr const char* step_form_name(const StepSpec (&specs)[K], int f) {
+    return step_form(specs, f) ? specs[f].name : "";
+}
 constexpr int kNumStepForms = (int)(sizeof(kStepSpecs) / sizeof(kStepSpecs[0]));
-inline const char* step_form_name(int f) { return (f >= 0 && f < kNumStepForms) ? kStepSpecs[f].name : ""; }
+inline const char* step_form_name(int f) { return step_form_name(kStepSpecs, f); }
 constexpr bool name_eq(const char* a, const char* b) { return *a == *b && (*a == 0 || name_eq(a + 1, b + 1)); }
 constexpr int step_form_index(const char* name) {
     for (int i = 0; i < kNumStepForms; ++i)
@@ -3332,11 +3208,11 @@ inline int pick_step(bool bf16) {
 //     own balanced block count, no dynamic pool
 //   f16_step_static_u8c4  comparison: every tile static
 constexpr StepSpec kStepSpecsF16[] = {
-    {"f16_step_bal_u8c4", false, 8, 4, 8, 2, 0, true, false, true, true},
-    {"f16_step_static_u8c4", false, 8, 4, 8, 4, 0, false, false, false, true},
+    {"f16_step_bal_u8c4", StepDtype::kF16, 8, 4, 8, 2, 0, true, false, true},
+    {"f16_step_static_u8c4", StepDtype::kF16, 8, 4, 8, 4, 0},
 };
 constexpr int kNumStepFormsF16 = (int)(sizeof(kStepSpecsF16) / sizeof(kStepSpecsF16[0]));
-inline const char* step_form_name_f16(int f) { return (f >= 0 && f < kNumStepFormsF16) ? kStepSpecsF16[f].name : ""; }
+inline const char* step_form_name_f16(int f) { return step_form_name(kStepSpecsF16, f); }
 inline int pick_step_f16() {
     static_assert(name_eq(kStepSpecsF16[0].name, "f16_step_bal_u8c4"), "policy step form");
     return 0;
@@ -3353,12 +3229,12 @@ inline int pick_step_f16() {
 // The policy (pick_step_f64): whichever of the first two measured faster by
 // more than the other's spread, else the balanced form.
 constexpr StepSpec kStepSpecsF64[] = {
-    {"f64_step_bal_u8c4", false, 8, 4, 8, 2, 0, true, false, true, false, true},
-    {"f64_step_sd_u8c4_p75", false, 8, 4, 16, 1, 75, false, false, false, false, true},
-    {"f64_step_static_u8c4", false, 8, 4, 8, 4, 0, false, false, false, false, true},
+    {"f64_step_bal_u8c4", StepDtype::kF64, 8, 4, 8, 2, 0, true, false, true},
+    {"f64_step_sd_u8c4_p75", StepDtype::kF64, 8, 4, 16, 1, 75},
+    {"f64_step_static_u8c4", StepDtype::kF64, 8, 4, 8, 4, 0},
 };
 constexpr int kNumStepFormsF64 = (int)(sizeof(kStepSpecsF64) / sizeof(kStepSpecsF64[0]));
-inline const char* step_form_name_f64(int f) { return (f >= 0 && f < kNumStepFormsF64) ? kStepSpecsF64[f].name : ""; }
+inline const char* step_form_name_f64(int f) { return step_form_name(kStepSpecsF64, f); }
 inline int pick_step_f64() {
     static_assert(name_eq(kStepSpecsF64[0].name, "f64_step_bal_u8c4"), "policy step form");
     return 0;
@@ -3549,23 +3425,24 @@ inline int rounds_check(RoundsState& o) {
 // [offsets[k], offsets[k+1]): the protocol every dtype shares (the epoch, the
 // start / done events, the gate wait, the capture refusal, the argument
 // checks).  fp32 and bf16 forms take float32 factors and write out (float32)
-// and / or outb; float16 forms (sp.f16) take binary16 factors and write out as
-// halves, the divisor the half's exact float32 value; float64 forms (sp.f64)
-// take double factors and write out as doubles, the divisor ddivisor (the
-// other forms never read it, nor the float64 ones divisor).
+// and / or outb; float16 forms take binary16 factors and write out as halves;
+// float64 forms take double factors and write out as doubles.  divisor: the
+// entry's divisor as a double (exact for a float32 and for the value of a
+// binary16 divisor), narrowed to the kernel's argument at the launch.
 inline int launch_step_spec(RoundsState& R, const StepSpec& sp, hipStream_t st, const void* X, int64_t N,
-                            int64_t ldx, const void* a, const void* s, float divisor, void* out, uint16_t* outb,
-                            int rounds, const int64_t* offsets, const int64_t* out_offsets, double ddivisor = 0.0) {
+                            int64_t ldx, const void* a, const void* s, double divisor, void* out, uint16_t* outb,
+                            int rounds, const int64_t* offsets, const int64_t* out_offsets) {
     R.launched = false;
+    const bool bf16 = sp.dtype == StepDtype::kBf16;
     if (rounds < 1 || rounds > kMaxRounds || !offsets) return fail(FA_ERR_ARG, "rounds must be 1..%d", kMaxRounds);
     const int64_t col_align = sp.ucols();
     // fp32, float16 and float64 rows write out; bf16 rows out and/or outb (ABI 5: out may be null)
-    if (!X || !a || N < 1 || (sp.bf16 ? (!out && !outb) : !out))
-        return fail(FA_ERR_ARG, sp.bf16 ? "null X/a, no output (out_f32 and out_bf16 both null) or N < 1"
-                                        : "null X/a/out or N < 1");
+    if (!X || !a || N < 1 || (bf16 ? (!out && !outb) : !out))
+        return fail(FA_ERR_ARG, bf16 ? "null X/a, no output (out_f32 and out_bf16 both null) or N < 1"
+                                     : "null X/a/out or N < 1");
     if (ldx % col_align || !aligned16(X) || !aligned16(out) || (outb && !aligned16(outb)))
         return fail(FA_ERR_ARG, "rounds fold needs 16-B aligned X/out and ldx %% %lld == 0", (long long)col_align);
-    if (sp.f64 && R.sys)
+    if (sp.dtype == StepDtype::kF64 && R.sys)
         return fail(FA_ERR_ARG, "step form %s: float64 rounds are published at agent scope (not a peer exchange's state)",
                     sp.name);
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -3604,51 +3481,21 @@ inline int launch_step_spec(RoundsState& R, const StepSpec& sp, hipStream_t st, 
     // the kernel instantiation is found from the form's tile shapes (never by
     // its index): a form whose shapes no instantiation below has is refused
     bool launched = false;
-#define FA_STB(UB, CB, US, CS, BAL, WTM)                                                                         \
-    if (!launched && sp.bf16 && !sp.f16 && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS &&           \
+#define FA_ST(DT, K, UB, CB, US, CS, BAL, WTM, ...)                                                              \
+    if (!launched && sp.dtype == StepDtype::DT && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS &&    \
         sp.bal == BAL && wtm == WTM) {                                                                           \
         launched = true;                                                                                         \
         if (s)                                                                                                   \
-            hipLaunchKernelGGL((k_fedavg_bf16_step<UB, CB, US, CS, true, kBlock, BAL, WTM>), dim3((unsigned)grid), \
-                               dim3(kBlock), 0, st, Xb, N, ldx, af, sf, divisor, outf, outb, T, R.sig, epoch);   \
+            hipLaunchKernelGGL((K<UB, CB, US, CS, true, kBlock, BAL, WTM>), dim3((unsigned)grid), dim3(kBlock), 0, st, \
+                               __VA_ARGS__, T, R.sig, epoch);                                                    \
         else                                                                                                     \
-            hipLaunchKernelGGL((k_fedavg_bf16_step<UB, CB, US, CS, false, kBlock, BAL, WTM>),                    \
-                               dim3((unsigned)grid), dim3(kBlock), 0, st, Xb, N, ldx, af, sf, divisor, outf, outb, T, \
-                               R.sig, epoch);                                                                    \
+            hipLaunchKernelGGL((K<UB, CB, US, CS, false, kBlock, BAL, WTM>), dim3((unsigned)grid), dim3(kBlock), 0, \
+                               st, __VA_ARGS__, T, R.sig, epoch);                                                \
     }
-#define FA_STF(UB, CB, US, CS, BAL, WTM)                                                                         \
-    if (!launched && !sp.octets() && !sp.f64 && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS && sp.bal == BAL && \
-        wtm == WTM) {                                                                                            \
-        launched = true;                                                                                         \
-        if (s)                                                                                                   \
-            hipLaunchKernelGGL((k_fold_f32_step<UB, CB, US, CS, true, kBlock, BAL, WTM>), dim3((unsigned)grid),  \
-                               dim3(kBlock), 0, st, Xf, N, ldx, af, sf, divisor, outf, T, R.sig, epoch);         \
-        else                                                                                                     \
-            hipLaunchKernelGGL((k_fold_f32_step<UB, CB, US, CS, false, kBlock, BAL, WTM>), dim3((unsigned)grid), \
-                               dim3(kBlock), 0, st, Xf, N, ldx, af, sf, divisor, outf, T, R.sig, epoch);         \
-    }
-#define FA_STH(UB, CB, US, CS, BAL, WTM)                                                                         \
-    if (!launched && sp.f16 && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS && sp.bal == BAL &&      \
-        wtm == WTM) {                                                                                            \
-        launched = true;                                                                                         \
-        if (s)                                                                                                   \
-            hipLaunchKernelGGL((k_fedavg_f16_step<UB, CB, US, CS, true, kBlock, BAL, WTM>), dim3((unsigned)grid), \
-                               dim3(kBlock), 0, st, Xb, N, ldx, ah, sh, divisor, outh, T, R.sig, epoch);         \
-        else                                                                                                     \
-            hipLaunchKernelGGL((k_fedavg_f16_step<UB, CB, US, CS, false, kBlock, BAL, WTM>), dim3((unsigned)grid), \
-                               dim3(kBlock), 0, st, Xb, N, ldx, ah, sh, divisor, outh, T, R.sig, epoch);         \
-    }
-#define FA_STD(UB, CB, US, CS, BAL, WTM)                                                                         \
-    if (!launched && sp.f64 && sp.ub == UB && sp.cb == CB && sp.us == US && sp.cs == CS && sp.bal == BAL &&      \
-        wtm == WTM) {                                                                                            \
-        launched = true;                                                                                         \
-        if (s)                                                                                                   \
-            hipLaunchKernelGGL((k_fedavg_f64_step<UB, CB, US, CS, true, kBlock, BAL, WTM>), dim3((unsigned)grid), \
-                               dim3(kBlock), 0, st, Xd, N, ldx, ad, sd, ddivisor, outd, T, R.sig, epoch);        \
-        else                                                                                                     \
-            hipLaunchKernelGGL((k_fedavg_f64_step<UB, CB, US, CS, false, kBlock, BAL, WTM>), dim3((unsigned)grid), \
-                               dim3(kBlock), 0, st, Xd, N, ldx, ad, sd, ddivisor, outd, T, R.sig, epoch);        \
-    }
+#define FA_STB(...) FA_ST(kBf16, k_fedavg_bf16_step, __VA_ARGS__, Xb, N, ldx, af, sf, (float)divisor, outf, outb)
+#define FA_STF(...) FA_ST(kF32, k_fold_f32_step, __VA_ARGS__, Xf, N, ldx, af, sf, (float)divisor, outf)
+#define FA_STH(...) FA_ST(kF16, k_fedavg_f16_step, __VA_ARGS__, Xb, N, ldx, ah, sh, (float)divisor, outh)
+#define FA_STD(...) FA_ST(kF64, k_fedavg_f64_step, __VA_ARGS__, Xd, N, ldx, ad, sd, divisor, outd)
     FA_STB(8, 4, 8, 2, false, kWtAgent)
     FA_STB(8, 4, 8, 4, false, kWtAgent)
     FA_STB(8, 4, 8, 2, true, kWtAgent)
@@ -3668,6 +3515,7 @@ inline int launch_step_spec(RoundsState& R, const StepSpec& sp, hipStream_t st, 
 #undef FA_STB
 #undef FA_STF
 #undef FA_STH
+#undef FA_ST
     if (!launched)
         return fail(FA_ERR_ARG, "step form %s: no kernel for its tile shapes%s", sp.name,
                     wtm == kWtSystem ? " with system-coherent stores (the policy forms only)" : "");
@@ -3681,13 +3529,22 @@ inline int launch_step_spec(RoundsState& R, const StepSpec& sp, hipStream_t st, 
     R.launched = true;
     return FA_OK;
 }
+// Form f of a table (kind: "", "float16 " or "float64 ", for the message)
+template <int K>
+int launch_step_form(RoundsState& R, const StepSpec (&specs)[K], const char* kind, int f, hipStream_t st,
+                     const void* X, int64_t N, int64_t ldx, const void* a, const void* s, double divisor, void* out,
+                     uint16_t* outb, int rounds, const int64_t* offsets, const int64_t* out_offsets) {
+    R.launched = false;
+    const StepSpec* sp = step_form(specs, f);
+    if (!sp) return fail(FA_ERR_ARG, "unknown %sstep form %d", kind, f);
+    return launch_step_spec(R, *sp, st, X, N, ldx, a, s, divisor, out, outb, rounds, offsets, out_offsets);
+}
 // Form f of kStepSpecs (fp32 and bf16 rows)
 inline int launch_step(RoundsState& R, int f, hipStream_t st, const void* X, int64_t N, int64_t ldx,
                        const float* a, const float* s, float divisor, float* out, uint16_t* outb, int rounds,
                        const int64_t* offsets, const int64_t* out_offsets = nullptr) {
-    R.launched = false;
-    if (f < 0 || f >= kNumStepForms) return fail(FA_ERR_ARG, "unknown step form %d", f);
-    return launch_step_spec(R, kStepSpecs[f], st, X, N, ldx, a, s, divisor, out, outb, rounds, offsets, out_offsets);
+    return launch_step_form(R, kStepSpecs, "", f, st, X, N, ldx, a, s, divisor, out, outb, rounds, offsets,
+                            out_offsets);
 }
 
 // ---- the pointer-table fold's forms (fa_fedavg_f32_ptrs_aligned) ----------
@@ -3897,15 +3754,7 @@ inline int launch_f32_pick(F32Pick pick, hipStream_t st, bool sc, bool acc, bool
             rc = launch_lds_flags<8, 64, 32, 1, true>(st, sc, acc, fin, X, N, P, ldx, a, s, acc_in, divisor, out);
             break;
         case F32Pick::kColumn:
-#define FA_SC(SC, ACC, FIN) launch_scalar<SC, ACC, FIN>(st, X, N, P, ldx, a, s, acc_in, divisor, out)
-            if (sc) {
-                if (acc) { if (fin) FA_SC(true, true, true); else FA_SC(true, true, false); }
-                else     { if (fin) FA_SC(true, false, true); else FA_SC(true, false, false); }
-            } else {
-                if (acc) { if (fin) FA_SC(false, true, true); else FA_SC(false, true, false); }
-                else     { if (fin) FA_SC(false, false, true); else FA_SC(false, false, false); }
-            }
-#undef FA_SC
+            launch_scalar(st, sc, acc, fin, X, N, P, ldx, a, s, acc_in, divisor, out);
             break;
         case F32Pick::kTileC1:  // plain stores (non-temporal ones cost 3-10 % here)
             rc = launch_tile_flags<4, 1, false>(st, sc, acc, fin, X, N, P, ldx, a, s, acc_in, divisor, out);
@@ -3978,15 +3827,7 @@ inline int fold_f32_auto(const float* X, int64_t N, int64_t P, int64_t ldx, cons
         return check_launch("fold_f32 (4-byte loads)");
     }
     if (!vec) {
-#define FA_SC(SC, ACC, FIN) launch_scalar<SC, ACC, FIN>(st, X, N, P, ldx, a, s, acc_in, divisor, out)
-        if (sc) {
-            if (acc) { if (fin) FA_SC(true, true, true); else FA_SC(true, true, false); }
-            else     { if (fin) FA_SC(true, false, true); else FA_SC(true, false, false); }
-        } else {
-            if (acc) { if (fin) FA_SC(false, true, true); else FA_SC(false, true, false); }
-            else     { if (fin) FA_SC(false, false, true); else FA_SC(false, false, false); }
-        }
-#undef FA_SC
+        launch_scalar(st, sc, acc, fin, X, N, P, ldx, a, s, acc_in, divisor, out);
         return check_launch("k_fold_f32_scalar");
     }
     const F32Pick policy = pick_f32(N, P);
@@ -4181,21 +4022,15 @@ inline int f16_auto(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const 
 // pitch that is no multiple of 8: one column per lane.
 constexpr int kFoldF16U = 4, kFoldF16C = 2;
 
-template <bool SC, bool ACC, bool FIN>
-void launch_fold_f16(hipStream_t st, bool vec, const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
-                     const uint16_t* a, const uint16_t* s, const uint16_t* acc_in, float d, uint16_t* out) {
-    if (!vec) {
-        hipLaunchKernelGGL((k_fold_f16_scalar<SC, ACC, FIN>), grid_for(P), dim3(kBlock), 0, st, X, N, P, ldx, a, s,
-                           acc_in, d, out);
-        return;
-    }
-    const OctetGrid g = octet_grid(P, kFoldF16C, -1, cu_count());  // at most one block per CU, balanced passes
-    hipLaunchKernelGGL((k_fold_f16_gs<kFoldF16U, kFoldF16C, SC, ACC, FIN>), dim3((unsigned)g.grid), dim3(kBlock), 0,
-                       st, X, N, P, ldx, a, s, acc_in, d, out, g.tiles);
-}
-
-inline int f16_fold(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
-                    const uint16_t* acc_in, uint16_t divisor, int finalize, uint16_t* out, void* stream) {
+// The chunked native folds (fa_fold_f16, fa_fold_f64): the checks, the vector
+// path's alignment rule (rows, accumulator and output 16-B aligned, the pitch
+// a multiple of the unit's columns), the flag dispatch.  launch(st, vec, SC,
+// ACC, FIN) enqueues the entry's own kernel: the tiled one, or (!vec) one
+// column per lane.  capturable == false: refused under graph capture.
+template <class A, class Launch>
+int native_fold(const char* what, bool capturable, const typename A::E* X, int64_t N, int64_t P, int64_t ldx,
+                const typename A::E* a, const typename A::E* s, const typename A::E* acc_in, int finalize,
+                typename A::E* out, void* stream, Launch launch) {
     if (!(acc_in && N == 0)) {
         int rc = check_common(N, P, ldx, X, a, out);
         if (rc) return rc;
@@ -4206,28 +4041,39 @@ inline int f16_fold(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const 
     }
     if (P == 0) { g_err[0] = 0; return FA_OK; }
     hipStream_t st = (hipStream_t)stream;
-    {
-        // the factors are halves and fa_factors_fill, the captured staging,
-        // carries float32 only: a graph could not own this fold's factors
+    if (!capturable) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
-        else if (cs != hipStreamCaptureStatusNone)
-            return fail(FA_ERR_ARG, "fa_fold_f16 does not run under graph capture");
+        else if (cs != hipStreamCaptureStatusNone) return fail(FA_ERR_ARG, "%s does not run under graph capture", what);
     }
     StreamDevice on_stream_device(stream);
+    const bool acc = acc_in != nullptr;
+    const bool vec = (N == 0 || aligned16(X)) && (ldx % (1 << A::LG) == 0) && aligned16(out) &&
+                     (!acc || aligned16(acc_in));
+    with_flags(s != nullptr, acc, finalize != 0,
+               [&](auto SC, auto ACC, auto FIN) { launch(st, vec, SC, ACC, FIN); });
+    return check_launch(what);
+}
+
+// Not under graph capture: the factors are halves and fa_factors_fill, the
+// captured staging, carries float32 only: a graph could not own this fold's
+// factors.
+inline int f16_fold(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const uint16_t* a, const uint16_t* s,
+                    const uint16_t* acc_in, uint16_t divisor, int finalize, uint16_t* out, void* stream) {
     const float d = half_bits_to_float(divisor);
-    const bool sc = s != nullptr, acc = acc_in != nullptr, fin = finalize != 0;
-    const bool vec = (N == 0 || aligned16(X)) && (ldx % 8 == 0) && aligned16(out) && (!acc || aligned16(acc_in));
-#define FA_FH(SC, ACC, FIN) launch_fold_f16<SC, ACC, FIN>(st, vec, X, N, P, ldx, a, s, acc_in, d, out)
-    if (sc) {
-        if (acc) { if (fin) FA_FH(true, true, true); else FA_FH(true, true, false); }
-        else     { if (fin) FA_FH(true, false, true); else FA_FH(true, false, false); }
-    } else {
-        if (acc) { if (fin) FA_FH(false, true, true); else FA_FH(false, true, false); }
-        else     { if (fin) FA_FH(false, false, true); else FA_FH(false, false, false); }
-    }
-#undef FA_FH
-    return check_launch("fa_fold_f16");
+    return native_fold<HalfArith>(
+        "fa_fold_f16", false, X, N, P, ldx, a, s, acc_in, finalize, out, stream,
+        [&](hipStream_t st, bool vec, auto SC, auto ACC, auto FIN) {
+            if (!vec) {
+                hipLaunchKernelGGL((k_fold_f16_scalar<SC.value, ACC.value, FIN.value>), grid_for(P), dim3(kBlock), 0,
+                                   st, X, N, P, ldx, a, s, acc_in, d, out);
+                return;
+            }
+            const OctetGrid g = octet_grid(P, kFoldF16C, -1, cu_count());  // at most one block per CU, balanced passes
+            hipLaunchKernelGGL((k_fold_f16_gs<kFoldF16U, kFoldF16C, SC.value, ACC.value, FIN.value>),
+                               dim3((unsigned)g.grid), dim3(kBlock), 0, st, X, N, P, ldx, a, s, acc_in, d, out,
+                               g.tiles);
+        });
 }
 
 // Form f of kStepSpecsF16 (fa_fedavg_f16_rounds): binary16 factors and divisor
@@ -4235,10 +4081,8 @@ inline int f16_fold(const uint16_t* X, int64_t N, int64_t P, int64_t ldx, const 
 inline int launch_step_f16(RoundsState& R, int f, hipStream_t st, const uint16_t* X, int64_t N, int64_t ldx,
                            const uint16_t* a, const uint16_t* s, uint16_t divisor, uint16_t* out, int rounds,
                            const int64_t* offsets, const int64_t* out_offsets) {
-    R.launched = false;
-    if (f < 0 || f >= kNumStepFormsF16) return fail(FA_ERR_ARG, "unknown float16 step form %d", f);
-    return launch_step_spec(R, kStepSpecsF16[f], st, X, N, ldx, a, s, half_bits_to_float(divisor), out, nullptr,
-                            rounds, offsets, out_offsets);
+    return launch_step_form(R, kStepSpecsF16, "float16 ", f, st, X, N, ldx, a, s, half_bits_to_float(divisor), out,
+                            nullptr, rounds, offsets, out_offsets);
 }
 
 // Form f of kStepSpecsF64 (fa_fedavg_f64_rounds): double factors and divisor,
@@ -4246,10 +4090,8 @@ inline int launch_step_f16(RoundsState& R, int f, hipStream_t st, const uint16_t
 inline int launch_step_f64(RoundsState& R, int f, hipStream_t st, const double* X, int64_t N, int64_t ldx,
                            const double* a, const double* s, double divisor, double* out, int rounds,
                            const int64_t* offsets, const int64_t* out_offsets) {
-    R.launched = false;
-    if (f < 0 || f >= kNumStepFormsF64) return fail(FA_ERR_ARG, "unknown float64 step form %d", f);
-    return launch_step_spec(R, kStepSpecsF64[f], st, X, N, ldx, a, s, 0.0f, out, nullptr, rounds, offsets,
-                            out_offsets, divisor);
+    return launch_step_form(R, kStepSpecsF64, "float64 ", f, st, X, N, ldx, a, s, divisor, out, nullptr, rounds,
+                            offsets, out_offsets);
 }
 
 // ---- the 16-bit row-table folds (fa_fedavg_bf16_ptrs, fa_fedavg_f16_ptrs) ----
@@ -4279,29 +4121,24 @@ inline Rows16Form pick_rows16(int64_t N, int64_t P) {
     }
 }
 
-// at most one block per CU, balanced passes
+// A row-table kernel (its scored or its plain instantiation) over tiles of C
+// units of 1 << lg columns: at most one block per CU, balanced passes
+template <class K, class... Args>
+void launch_rows_gs(hipStream_t st, K scored, K plain, bool sc, int C, int lg, int64_t P, Args... args) {
+    const OctetGrid g = octet_grid(P, C, -1, cu_count(), lg);
+    hipLaunchKernelGGL(sc ? scored : plain, dim3((unsigned)g.grid), dim3(kBlock), 0, st, args..., g.tiles);
+}
 template <int U, int C>
 void launch_bf16_rows_gs(hipStream_t st, const uint16_t* const* xi, int64_t N, int64_t P, const float* a,
                          const float* s, float d, float* out, uint16_t* outb) {
-    const OctetGrid g = octet_grid(P, C, -1, cu_count());
-    if (s)
-        hipLaunchKernelGGL((k_fedavg_bf16_rows_gs<U, C, true>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, xi, N, P,
-                           a, s, d, out, outb, g.tiles);
-    else
-        hipLaunchKernelGGL((k_fedavg_bf16_rows_gs<U, C, false>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, xi, N, P,
-                           a, s, d, out, outb, g.tiles);
+    launch_rows_gs(st, k_fedavg_bf16_rows_gs<U, C, true>, k_fedavg_bf16_rows_gs<U, C, false>, s != nullptr, C, 3, P, xi,
+                   N, P, a, s, d, out, outb);
 }
-
 template <int U, int C>
 void launch_f16_rows_gs(hipStream_t st, const uint16_t* const* xi, int64_t N, int64_t P, const uint16_t* a,
                         const uint16_t* s, float d, uint16_t* out) {
-    const OctetGrid g = octet_grid(P, C, -1, cu_count());
-    if (s)
-        hipLaunchKernelGGL((k_fedavg_f16_rows_gs<U, C, true>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, xi, N, P,
-                           a, s, d, out, g.tiles);
-    else
-        hipLaunchKernelGGL((k_fedavg_f16_rows_gs<U, C, false>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, xi, N, P,
-                           a, s, d, out, g.tiles);
+    launch_rows_gs(st, k_fedavg_f16_rows_gs<U, C, true>, k_fedavg_f16_rows_gs<U, C, false>, s != nullptr, C, 3, P, xi,
+                   N, P, a, s, d, out);
 }
 
 // form < 0: the policy (rows_aligned picks the octet tiling or the column
@@ -4381,66 +4218,35 @@ inline int pick_pairs(int64_t P, int64_t cus) {
     return 1;
 }
 
-template <int C, bool SC, bool ACC, bool FIN>
-void launch_fold_f64_gs(hipStream_t st, const double* X, int64_t N, int64_t P, int64_t ldx, const double* a,
-                        const double* s, const double* acc_in, double d, double* out) {
-    const OctetGrid g = octet_grid(P, C, -1, cu_count(), 1);
-    hipLaunchKernelGGL((k_fold_f64_gs<kFoldF64U, C, SC, ACC, FIN>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, X, N,
-                       P, ldx, a, s, acc_in, d, out, g.tiles);
-}
-
-template <bool SC, bool ACC, bool FIN>
-void launch_fold_f64(hipStream_t st, bool vec, const double* X, int64_t N, int64_t P, int64_t ldx, const double* a,
-                     const double* s, const double* acc_in, double d, double* out) {
-    if (!vec) {
-        hipLaunchKernelGGL((k_fold_f64_scalar<SC, ACC, FIN>), grid_for(P), dim3(kBlock), 0, st, X, N, P, ldx, a, s,
-                           acc_in, d, out);
-        return;
-    }
-    switch (pick_pairs(P, cu_count())) {
-        case 4: launch_fold_f64_gs<4, SC, ACC, FIN>(st, X, N, P, ldx, a, s, acc_in, d, out); break;
-        case 2: launch_fold_f64_gs<2, SC, ACC, FIN>(st, X, N, P, ldx, a, s, acc_in, d, out); break;
-        default: launch_fold_f64_gs<1, SC, ACC, FIN>(st, X, N, P, ldx, a, s, acc_in, d, out); break;
-    }
-}
-
 inline int f64_fold(const double* X, int64_t N, int64_t P, int64_t ldx, const double* a, const double* s,
                     const double* acc_in, double divisor, int finalize, double* out, void* stream) {
-    if (!(acc_in && N == 0)) {
-        int rc = check_common(N, P, ldx, X, a, out);
-        if (rc) return rc;
-    } else if (P < 0) {
-        return fail(FA_ERR_ARG, "negative size (N=0, P=%lld)", (long long)P);
-    } else if (P > 0 && !out) {
-        return fail(FA_ERR_ARG, "null out pointer");
-    }
-    if (P == 0) { g_err[0] = 0; return FA_OK; }
-    hipStream_t st = (hipStream_t)stream;
-    StreamDevice on_stream_device(stream);
-    const bool sc = s != nullptr, acc = acc_in != nullptr, fin = finalize != 0;
-    const bool vec = (N == 0 || aligned16(X)) && (ldx % 2 == 0) && aligned16(out) && (!acc || aligned16(acc_in));
-#define FA_FD(SC, ACC, FIN) launch_fold_f64<SC, ACC, FIN>(st, vec, X, N, P, ldx, a, s, acc_in, divisor, out)
-    if (sc) {
-        if (acc) { if (fin) FA_FD(true, true, true); else FA_FD(true, true, false); }
-        else     { if (fin) FA_FD(true, false, true); else FA_FD(true, false, false); }
-    } else {
-        if (acc) { if (fin) FA_FD(false, true, true); else FA_FD(false, true, false); }
-        else     { if (fin) FA_FD(false, false, true); else FA_FD(false, false, false); }
-    }
-#undef FA_FD
-    return check_launch("fa_fold_f64");
+    return native_fold<DoubleArith>(
+        "fa_fold_f64", true, X, N, P, ldx, a, s, acc_in, finalize, out, stream,
+        [&](hipStream_t st, bool vec, auto SC, auto ACC, auto FIN) {
+            if (!vec) {
+                hipLaunchKernelGGL((k_fold_f64_scalar<SC.value, ACC.value, FIN.value>), grid_for(P), dim3(kBlock), 0,
+                                   st, X, N, P, ldx, a, s, acc_in, divisor, out);
+                return;
+            }
+            auto gs = [&](auto C) {
+                const OctetGrid g = octet_grid(P, C.value, -1, cu_count(), 1);
+                hipLaunchKernelGGL((k_fold_f64_gs<kFoldF64U, C.value, SC.value, ACC.value, FIN.value>),
+                                   dim3((unsigned)g.grid), dim3(kBlock), 0, st, X, N, P, ldx, a, s, acc_in, divisor, out,
+                                   g.tiles);
+            };
+            switch (pick_pairs(P, cu_count())) {
+                case 4: gs(int_c<4>{}); break;
+                case 2: gs(int_c<2>{}); break;
+                default: gs(int_c<1>{}); break;
+            }
+        });
 }
 
 template <int C>
 void launch_f64_rows_gs(hipStream_t st, const double* const* xi, int64_t N, int64_t P, const double* a,
                         const double* s, double d, double* out) {
-    const OctetGrid g = octet_grid(P, C, -1, cu_count(), 1);
-    if (s)
-        hipLaunchKernelGGL((k_fedavg_f64_rows_gs<kRowsF64U, C, true>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, xi,
-                           N, P, a, s, d, out, g.tiles);
-    else
-        hipLaunchKernelGGL((k_fedavg_f64_rows_gs<kRowsF64U, C, false>), dim3((unsigned)g.grid), dim3(kBlock), 0, st, xi,
-                           N, P, a, s, d, out, g.tiles);
+    launch_rows_gs(st, k_fedavg_f64_rows_gs<kRowsF64U, C, true>, k_fedavg_f64_rows_gs<kRowsF64U, C, false>,
+                   s != nullptr, C, 1, P, xi, N, P, a, s, d, out);
 }
 
 inline int f64_rows_fold(const double* const* xi, int64_t N, int64_t P, const double* a, const double* s,

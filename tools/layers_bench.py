@@ -4,8 +4,8 @@ row-table route it replaces, on multi-layer models whose every client layer is
 a separately allocated device tensor.
 
 Models: the four layer lists of SURVEY.md App. D (Keras get_weights() order).
-Per model, dtype (fp32, bf16) and client count it times, as GPU-event spans
-around the Python call on the current stream (host work included whenever the
+Per model, dtype (fp32 and bf16; --dtypes also takes f16, f64) and client
+count it times, as GPU-event spans around the Python call on the current stream (host work included whenever the
 GPU waits for it):
   a_per_layer_ms   aggregate_layers, FEDAVG_LAYER_TABLE=0   one fold_rows per layer (the route before)
   b_table_ms       aggregate_layers, FEDAVG_LAYER_TABLE=1   table and plan built in the call, one launch
@@ -51,7 +51,7 @@ if not torch.cuda.is_available():
     sys.exit("layers_bench needs a GPU")
 dev = torch.device("cuda", 0)
 SEED = 9
-DT = {"f32": torch.float32, "bf16": torch.bfloat16}
+DT = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "f64": torch.float64}
 
 
 def numel(shape):
@@ -92,7 +92,7 @@ def switched(value, params, w):
 
 
 def bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+    return t.contiguous().view({4: torch.int32, 2: torch.int16, 8: torch.int64}[t.element_size()])
 
 
 skip = {tuple(x.split(":")) for x in args.skip.split(",") if x}
