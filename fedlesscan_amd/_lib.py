@@ -90,7 +90,11 @@ _PROTOS = {
     "fa_fedavg_f64_layers": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _f64, _vp, _vp]),
     "fa_fedavg_i32": (_int, [_vp, _i64, _i64, _i64, _vp, _f64, _vp, _vp]),
     "fa_fedavg_i64": (_int, [_vp, _i64, _i64, _i64, _vp, _f64, _vp, _vp]),
-    "fa_npz_index": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _int]),
+    "fa_fedavg_i32_ptrs": (_int, [_vp, _i64, _i64, _vp, _vp, _f64, _int, _vp, _vp]),
+    "fa_fedavg_i64_ptrs": (_int, [_vp, _i64, _i64, _vp, _vp, _f64, _int, _vp, _vp]),
+    "fa_fedavg_i32_layers": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _f64, _vp, _vp]),
+    "fa_fedavg_i64_layers": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _f64, _vp, _vp]),
+    "fa_npz_index":(_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _int]),
     "fa_crc32": (_int, [_vp, _i64, ctypes.c_uint32, _int, ctypes.POINTER(ctypes.c_uint32)]),
     "fa_pack": (_int, [_vp, _vp, _vp, _vp, _i64, _int]),
     "fa_bson_elements": (_i64, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64]),
@@ -159,6 +163,7 @@ _BENCH_PROTOS = {
     "fa_fedavg_bf16_ptrs_form": (_int, [_vp, _i64, _i64, _vp, _vp, _f32, _int, _vp, _vp, _vp, _int]),
     "fa_fedavg_f16_ptrs_form": (_int, [_vp, _i64, _i64, _vp, _vp, ctypes.c_uint16, _int, _vp, _vp, _int]),
     "fa_fedavg_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp, _vp]),
+    "fa_fedavg_int_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp]),
     "fa_fedavg_bf16_variant": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _int]),
     "fa_num_bf16_variants": (_int, []),
     "fa_bf16_variant_name": (ctypes.c_char_p, [_int]),

@@ -562,6 +562,29 @@ int fa_fedavg_i64(const int64_t* X, int64_t N, int64_t P, int64_t ldx, const int
     return check_launch("k_fedavg_int<int64>");
 }
 
+// ---- integer rows where the clients' tensors lie (int_rows_fold, int_layers_fold) ----
+int fa_fedavg_i32_ptrs(const int32_t* const* xi, int64_t N, int64_t P, const int64_t* a, const double* s,
+                       double divisor, int rows_aligned, double* out, void* stream) {
+    return int_rows_fold<Int32Rows>("fa_fedavg_i32_ptrs", xi, N, P, a, s, divisor, rows_aligned, out, stream);
+}
+
+int fa_fedavg_i64_ptrs(const int64_t* const* xi, int64_t N, int64_t P, const int64_t* a, const double* s,
+                       double divisor, int rows_aligned, double* out, void* stream) {
+    return int_rows_fold<Int64Rows>("fa_fedavg_i64_ptrs", xi, N, P, a, s, divisor, rows_aligned, out, stream);
+}
+
+int fa_fedavg_i32_layers(const int32_t* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
+                         int units, const int64_t* a, const double* s, double divisor, double* out, void* stream) {
+    return int_layers_fold<Int32Rows>("fa_fedavg_i32_layers", xi, plan, L, N, tiles, units, 0, a, s, divisor, out,
+                                      stream);
+}
+
+int fa_fedavg_i64_layers(const int64_t* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
+                         int units, const int64_t* a, const double* s, double divisor, double* out, void* stream) {
+    return int_layers_fold<Int64Rows>("fa_fedavg_i64_layers", xi, plan, L, N, tiles, units, 0, a, s, divisor, out,
+                                      stream);
+}
+
 // ---- the same folds with the per-client factors in host memory ---------------
 int fa_factors_fill(float* dst, const float* a, const float* s, int64_t N, void* stream) {
     if (N < 0 || (N > 0 && (!dst || !a))) return fail(FA_ERR_ARG, "fa_factors_fill: N %lld, null pointer", (long long)N);

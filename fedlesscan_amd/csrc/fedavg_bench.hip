@@ -671,6 +671,17 @@ int fa_fedavg_layers_form(int dtype, const void* const* xi, const fa_layer_plan*
     return layers_fold(dtype, "fa_fedavg_layers_form", xi, plan, L, N, tiles, units, grid_cap, a, s, divisor, out,
                        out_bf16, stream);
 }
+int fa_fedavg_int_layers_form(int dtype, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
+                              int64_t tiles, int units, int64_t grid_cap, const int64_t* a, const double* s,
+                              double divisor, double* out, void* stream) {
+    if (dtype == 4)
+        return int_layers_fold<Int32Rows>("fa_fedavg_int_layers_form", (const int32_t* const*)xi, plan, L, N, tiles,
+                                          units, grid_cap, a, s, divisor, out, stream);
+    if (dtype == 5)
+        return int_layers_fold<Int64Rows>("fa_fedavg_int_layers_form", (const int64_t* const*)xi, plan, L, N, tiles,
+                                          units, grid_cap, a, s, divisor, out, stream);
+    return fail(FA_ERR_ARG, "fa_fedavg_int_layers_form: unknown dtype %d", dtype);
+}
 const char* fa_variant_name(int variant) {
     return (variant >= 0 && variant < kNumVariants) ? kVariants[variant] : "";
 }

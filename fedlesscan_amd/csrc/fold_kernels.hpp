@@ -2696,6 +2696,191 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_int(
 }
 
 // ---------------------------------------------------------------------------
+// The integer row-table folds (fa_fedavg_i32_ptrs / _i64_ptrs and the
+// _layers entries): numpy's literal fold of integer rows, read where the
+// clients' tensors lie.  T is the rows' dtype, UT its unsigned twin:
+//   p_i = (T)((UT)x * (UT)(T)a_i), wrapping (computed unsigned: no C++ UB)
+//   unscored  acc = p_0, acc = wrap(acc + p_i) in T; out = (double)acc / divisor
+//             -- the arithmetic of k_fedavg_int
+//   scored    t_i = (double)p_i * s_i -- the conversion rounds to nearest even
+//             beyond 2^53, as numpy's cast -- acc = t_0, acc = acc + t_i in
+//             strict client order, multiply and add apart; out = acc / divisor
+// The quotient is the float64 folds' divide (div_d1).  The kernel has the
+// float64 layer-table kernel's shape: grid-stride over the tiles of all
+// layers, the layer_tile search, 16-byte units (4 int32 or 2 int64 columns) C
+// per lane with 8 rows of loads ahead of the ordered adds, the quotients stored
+// non-temporally as 16-byte pairs of doubles (an int32 unit: two stores), an
+// aligned layer's tail columns and an unaligned layer's columns one per lane,
+// 8 rows ahead.  plan == NULL folds the one layer `one`, passed by value: the
+// _ptrs entries, which so allocate and upload nothing.
+// ---------------------------------------------------------------------------
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+typedef int64_t i64x2 __attribute__((ext_vector_type(2)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+struct Int32Rows {
+    typedef int32_t T;
+    typedef uint32_t UT;
+    typedef u32x4 UV;  // a unit as loaded, and the wrapping arithmetic
+    typedef i32x4 SV;
+    typedef f64x4 DV;  // a unit's terms and quotients
+    typedef gu32x4 GUnit;
+    typedef __attribute__((address_space(1))) const int32_t GE;
+    static constexpr int LG = 2;
+};
+struct Int64Rows {
+    typedef int64_t T;
+    typedef uint64_t UT;
+    typedef u64x2 UV;
+    typedef i64x2 SV;
+    typedef f64x2 DV;
+    typedef __attribute__((address_space(1))) const u64x2 GUnit;
+    typedef __attribute__((address_space(1))) const int64_t GE;
+    static constexpr int LG = 1;
+};
+
+// the cardinality as numpy converts it to the rows' dtype (the host has checked that it fits)
+template <class I>
+__device__ __forceinline__ typename I::UT int_factor(const int64_t* __restrict__ a, int64_t i) {
+    return (typename I::UT)(typename I::T)(*(ci64*)(a + i));
+}
+__device__ __forceinline__ double int_score(const double* __restrict__ s, int64_t i) { return *(cf64*)(s + i); }
+
+// one unit's accumulator: the wrapping sum, or the float64 sum of the scored terms
+template <class I, bool SCORED>
+struct IntAcc {
+    typedef typename std::conditional<SCORED, typename I::DV, typename I::UV>::type V;
+    typedef typename std::conditional<SCORED, double, typename I::UT>::type S;
+    static __device__ __forceinline__ typename I::DV dbl(typename I::UV p) {
+        return __builtin_convertvector(__builtin_bit_cast(typename I::SV, p), typename I::DV);
+    }
+    static __device__ __forceinline__ V term(typename I::UV x, typename I::UT a, double s) {
+        const typename I::UV p = x * a;
+        if constexpr (SCORED) return dbl(p) * s;
+        else return p;
+    }
+    static __device__ __forceinline__ S term(typename I::UT x, typename I::UT a, double s) {
+        const typename I::UT p = (typename I::UT)(x * a);
+        if constexpr (SCORED) return (double)(typename I::T)p * s;
+        else return p;
+    }
+    static __device__ __forceinline__ typename I::DV fin(V acc) {
+        if constexpr (SCORED) return acc;
+        else return dbl(acc);
+    }
+    static __device__ __forceinline__ double fin(S acc) {
+        if constexpr (SCORED) return acc;
+        else return (double)(typename I::T)acc;
+    }
+};
+
+__device__ __forceinline__ void st_quotients(double* out, f64x2 acc, double divisor) {
+    __builtin_nontemporal_store(div_d2(acc, divisor), reinterpret_cast<f64x2*>(out));
+}
+__device__ __forceinline__ void st_quotients(double* out, f64x4 acc, double divisor) {
+    __builtin_nontemporal_store(div_d2(f64x2{acc.x, acc.y}, divisor), reinterpret_cast<f64x2*>(out));
+    __builtin_nontemporal_store(div_d2(f64x2{acc.z, acc.w}, divisor), reinterpret_cast<f64x2*>(out) + 1);
+}
+
+// The lane's C units of the rows of src, in row order; out: the lane's first unit's columns
+template <class I, int U, int C, bool SCORED>
+__device__ __forceinline__ void fold_int_units(TableRows<typename I::GUnit, typename I::T> src, int64_t N,
+                                               const int64_t* __restrict__ a, const double* __restrict__ s,
+                                               double divisor, double* out) {
+    typedef IntAcc<I, SCORED> A;
+    typename A::V acc[C];
+    {
+        const auto* r = src.row(0);
+        const typename I::UT a0 = int_factor<I>(a, 0);
+        const double s0 = SCORED ? int_score(s, 0) : 1.0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = A::term(__builtin_nontemporal_load(r + c * kBlock), a0, s0);
+    }
+    int64_t i = 1;
+    for (; i + U <= N; i += U) {
+        typename I::UV v[U][C];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const auto* r = src.row(i + u);
+#pragma unroll
+            for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const typename I::UT ai = int_factor<I>(a, i + u);
+            const double si = SCORED ? int_score(s, i + u) : 1.0;
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] = acc[c] + A::term(v[u][c], ai, si);
+        }
+    }
+    for (; i < N; ++i) {
+        const auto* r = src.row(i);
+        const typename I::UT ai = int_factor<I>(a, i);
+        const double si = SCORED ? int_score(s, i) : 1.0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = acc[c] + A::term(__builtin_nontemporal_load(r + c * kBlock), ai, si);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) st_quotients(out + ((int64_t)c * kBlock << I::LG), A::fin(acc[c]), divisor);
+}
+
+// One column: 8 rows of loads ahead of the ordered adds
+template <class I, bool SCORED>
+__device__ __forceinline__ double fold_int_column(TableRows<typename I::GE, typename I::T> src, int64_t N,
+                                                  const int64_t* __restrict__ a, const double* __restrict__ s,
+                                                  double divisor) {
+    typedef IntAcc<I, SCORED> A;
+    typedef typename I::UT UT;
+    typename A::S acc = A::term((UT)*src.row(0), int_factor<I>(a, 0), SCORED ? int_score(s, 0) : 1.0);
+    int64_t i = 1;
+    for (; i + 8 <= N; i += 8) {
+        UT v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = (UT)__builtin_nontemporal_load(src.row(i + u));
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            acc = acc + A::term(v[u], int_factor<I>(a, i + u), SCORED ? int_score(s, i + u) : 1.0);
+    }
+    for (; i < N; ++i) acc = acc + A::term((UT)*src.row(i), int_factor<I>(a, i), SCORED ? int_score(s, i) : 1.0);
+    return div_d1(A::fin(acc), divisor);
+}
+
+template <class I, int U, int C, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_int_layers(
+    const typename I::T* const* __restrict__ xi, const fa_layer_plan* __restrict__ plan, fa_layer_plan one, int64_t L,
+    int64_t N, const int64_t* __restrict__ a, const double* __restrict__ s, double divisor, double* __restrict__ out,
+    int64_t ntiles) {
+    typedef typename I::T T;
+    int64_t l = 0;
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+        const LayerTile t = plan ? layer_tile(plan, L, bid, l) : LayerTile{0, one.cols, one.offset, bid, one.aligned != 0};
+        l = t.l;
+        const T* const* x = xi + l * N;
+        double* o = out + t.offset;
+        if (!t.aligned) {
+            const int64_t c = t.bid * kBlock + threadIdx.x;
+            if (c < t.cols) o[c] = fold_int_column<I, SCORED>(TableRows<typename I::GE, T>{x, c}, N, a, s, divisor);
+            continue;
+        }
+        octet_tile<C, kBlock, I::LG>(
+            t.bid, t.cols,
+            [&](int64_t q) {
+                fold_int_units<I, U, C, SCORED>(TableRows<typename I::GUnit, T>{x, q}, N, a, s, divisor,
+                                                o + (q << I::LG));
+            },
+            [&](int64_t q) {
+                fold_int_units<I, U, 1, SCORED>(TableRows<typename I::GUnit, T>{x, q}, N, a, s, divisor,
+                                                o + (q << I::LG));
+            },
+            [&](int64_t col) {
+                for (; col < t.cols; ++col)
+                    o[col] = fold_int_column<I, SCORED>(TableRows<typename I::GE, T>{x, col}, N, a, s, divisor);
+            });
+    }
+}
+
+// ---------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------
 inline dim3 grid_for(int64_t lanes) { return dim3((unsigned)((lanes + kBlock - 1) / kBlock)); }
@@ -4352,6 +4537,84 @@ inline int layers_fold(int kind, const char* what, const void* const* xi, const 
         case 2: launch_layers<2>(kind, st, (unsigned)g, xi, plan, L, N, tiles, a, s, divisor, out, outb); break;
         default: launch_layers<1>(kind, st, (unsigned)g, xi, plan, L, N, tiles, a, s, divisor, out, outb); break;
     }
+    return check_launch(what);
+}
+
+// ---- the integer row-table folds (fa_fedavg_i32/i64_ptrs, _layers) ----------
+// The layer-table launch over integer rows: the geometry of layers_fold (8 rows
+// ahead, the plan's units per lane, balanced passes over at most one block per
+// CU).  plan == NULL: the one layer `one` travels by value (the _ptrs entries).
+template <class I, int C>
+void launch_int_layers(hipStream_t st, unsigned g, const typename I::T* const* xi, const fa_layer_plan* plan,
+                       const fa_layer_plan& one, int64_t L, int64_t N, int64_t tiles, const int64_t* a, const double* s,
+                       double divisor, double* out) {
+    if (s)
+        hipLaunchKernelGGL((k_fedavg_int_layers<I, kLayersU, C, true>), dim3(g), dim3(kBlock), 0, st, xi, plan, one, L,
+                           N, a, s, divisor, out, tiles);
+    else
+        hipLaunchKernelGGL((k_fedavg_int_layers<I, kLayersU, C, false>), dim3(g), dim3(kBlock), 0, st, xi, plan, one, L,
+                           N, a, s, divisor, out, tiles);
+}
+
+template <class I>
+void launch_int_layers_units(int units, hipStream_t st, unsigned g, const typename I::T* const* xi,
+                             const fa_layer_plan* plan, const fa_layer_plan& one, int64_t L, int64_t N, int64_t tiles,
+                             const int64_t* a, const double* s, double divisor, double* out) {
+    switch (units) {
+        case 4: launch_int_layers<I, 4>(st, g, xi, plan, one, L, N, tiles, a, s, divisor, out); break;
+        case 2: launch_int_layers<I, 2>(st, g, xi, plan, one, L, N, tiles, a, s, divisor, out); break;
+        default: launch_int_layers<I, 1>(st, g, xi, plan, one, L, N, tiles, a, s, divisor, out); break;
+    }
+}
+
+// The checks of layers_fold, in its order and with its messages
+template <class I>
+int int_layers_fold(const char* what, const typename I::T* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
+                    int64_t tiles, int units, int64_t grid_cap, const int64_t* a, const double* s, double divisor,
+                    double* out, void* stream) {
+    if (L < 0 || N < 0 || tiles < 0)
+        return fail(FA_ERR_ARG, "negative size (L=%lld, N=%lld, tiles=%lld)", (long long)L, (long long)N,
+                    (long long)tiles);
+    if (N == 0) return fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
+    if (units != 1 && units != 2 && units != 4)
+        return fail(FA_ERR_ARG, "%s: %d units per lane (1, 2 or 4)", what, units);
+    if (grid_cap < 0) return fail(FA_ERR_ARG, "%s: negative grid cap", what);
+    if (L == 0 || tiles == 0) { g_err[0] = 0; return FA_OK; }
+    if (!xi || !plan || !a || !out) return fail(FA_ERR_ARG, "null xi/plan/a/out pointer");
+    if (!aligned16(out)) return fail(FA_ERR_ARG, "%s needs 16-B aligned outputs", what);
+    if (tiles > (int64_t)0x7FFFFFFF) return fail(FA_ERR_ARG, "too many tiles for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    StreamDevice on_stream_device(stream);
+    int64_t g = tile_grid(tiles, -1, cu_count());
+    if (grid_cap > 0 && g > grid_cap) g = grid_cap;
+    launch_int_layers_units<I>(units, st, (unsigned)g, xi, plan, fa_layer_plan{0, 0, 0, 0}, L, N, tiles, a, s, divisor,
+                               out);
+    return check_launch(what);
+}
+
+// One layer through the same kernel, its plan entry built here and passed by
+// value: no allocation, no copy, no synchronisation.  The checks of
+// f64_rows_fold.  rows_aligned == 0: one column per lane, rows and out at any
+// offset of the element size (out: 8 B).
+template <class I>
+int int_rows_fold(const char* what, const typename I::T* const* xi, int64_t N, int64_t P, const int64_t* a,
+                  const double* s, double divisor, int rows_aligned, double* out, void* stream) {
+    int rc = check_common(N, P, P, xi, a, out);
+    if (rc) return rc;
+    if (P == 0) { g_err[0] = 0; return FA_OK; }
+    if (rows_aligned && !aligned16(out))
+        return fail(FA_ERR_ARG, "the unit form of the integer row-table fold needs 16-B aligned rows and out");
+    hipStream_t st = (hipStream_t)stream;
+    StreamDevice on_stream_device(stream);
+    const int64_t cus = cu_count();
+    const int32_t al = rows_aligned != 0;
+    const int units = pick_layer_units(&P, &al, 1, I::LG, cus);
+    fa_layer_plan one;
+    int64_t elems = 0;
+    const int64_t tiles = fill_layer_plan(&P, &al, 1, units, I::LG, &one, &elems);
+    if (tiles > (int64_t)0x7FFFFFFF) return fail(FA_ERR_ARG, "too many tiles for one launch");
+    launch_int_layers_units<I>(units, st, (unsigned)tile_grid(tiles, -1, cus), xi, nullptr, one, 1, N, tiles, a, s,
+                               divisor, out);
     return check_launch(what);
 }
 

@@ -3,7 +3,8 @@
 Layering
   engine.fold_stacked(X, weights, scores)   X: CUDA tensor [N, P] (row pitch = X.stride(0))
   engine.fold_rows(rows, weights, scores)   N separately allocated CUDA rows (pointer list: fp32,
-                                            bf16, float16, float64; engine.RowSet prepares a reusable row set)
+                                            bf16, float16, float64, int32, int64; engine.RowSet prepares a
+                                            reusable row set)
   engine.aggregate_layers(params, weights)  host or device per-client layer lists -> per-layer outputs
 
 The scalar factors are formed on the host exactly as numpy forms them in the
@@ -676,6 +677,49 @@ def f64_factors(weights: Sequence, scores: Optional[Sequence] = None, total=None
     return Factors(weights, scores, _F64, total=total)
 
 
+def int_row_factors(dt, weights: Sequence, scores: Optional[Sequence] = None, total=None):
+    """(a int64, s float64 or None, divisor float64) of a fold over rows of
+    the integer dtype dt (int32 or int64) that the integer row-table kernels
+    compute (fa_fedavg_i32/i64_ptrs, _layers), or None for any other fold.
+    fold_plan is asked, so numpy's OverflowError (a Python int the dtype cannot
+    hold) is raised here, before any launch.  Taken: every product `layer * n`
+    stays dt, and either there are no scores and the whole fold is uniform in
+    dt (the quotient float64), or every term, every running sum and the
+    quotient are float64 (`* s` of an integer product is float64 under Python
+    floats, np.float32 and np.float64 alike).  Not taken: float weights (the
+    product is float64), int32 rows under np.int64 weights (the product is
+    int64)."""
+    dt = np.dtype(dt)
+    if dt != np.int32 and dt != np.int64:
+        return None
+    n = min(len(weights), len(scores) if scores is not None else len(weights))
+    if n == 0:
+        return None
+    plan = fold_plan(dt, weights, scores, total)
+    if plan.prod.count(dt) != n:
+        return None
+    if scores is None:
+        if plan.uniform != dt:
+            return None
+    elif plan.term.count(_F64) != n or plan.acc.count(_F64) != n or plan.quot != _F64:
+        return None
+    total = sum(weights) if total is None else total
+    a = np.array([int(w) for w in weights[:n]], dtype=np.int64)
+    s = None if scores is None else round_scalars(list(scores[:n]), _F64)
+    return a, s, np.float64(total)
+
+
+def _int_factors(dt, weights, scores, total) -> Optional[Factors]:
+    """int_row_factors as a Factors (its staging), or None."""
+    t = int_row_factors(dt, weights, scores, total)
+    if t is None:
+        return None
+    f = Factors.__new__(Factors)
+    f.total = sum(weights) if total is None else total
+    f.a, f.s, f.div = t
+    return f
+
+
 def _half_bits(div) -> int:
     """The bit pattern of a binary16 divisor (Factors.div of a float16 fold)."""
     return int(np.asarray(div, dtype=np.float16).view(np.uint16))
@@ -864,12 +908,16 @@ def _equal_stride_view(rows, host_ptrs: np.ndarray, P: int) -> Optional[torch.Te
 
 _dtype_of = operator.attrgetter("dtype")
 # dtypes the library folds through a device table of row pointers
-_ROW_TABLE_DTYPES = (torch.float32, torch.bfloat16, torch.float16, torch.float64)
+_ROW_TABLE_DTYPES = (torch.float32, torch.bfloat16, torch.float16, torch.float64, torch.int32, torch.int64)
+_INT_ROWS = {torch.int32: "fa_fedavg_i32_ptrs", torch.int64: "fa_fedavg_i64_ptrs"}
+# dtypes whose row-table fold does not run under a stream capture: they keep the route they had before it
+_NO_CAPTURE_TABLE = (torch.float64, torch.int32, torch.int64)
 # process-wide route counters (diagnostics, as StreamingFold.stats): 16-bit and
 # float64 folds that ran through a row table (layers: a one-launch model fold
 # counts each of its layers), layer groups copied into a stacked matrix,
-# one-launch model folds (fa_fedavg_*_layers)
-stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0, "layer_table_folds": 0}
+# one-launch model folds (fa_fedavg_*_layers), integer folds that ran through a
+# row table (counted as the float64 ones)
+stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0, "layer_table_folds": 0, "rows_int_folds": 0}
 
 
 class RowSet:
@@ -885,7 +933,10 @@ class RowSet:
         fa_fedavg_f32_ptrs (any alignment);
       - other bfloat16 / float16 / float64 rows get the same table for
         fa_fedavg_bf16_ptrs / fa_fedavg_f16_ptrs / fa_fedavg_f64_ptrs
-        (`aligned` picks the kernels).
+        (`aligned` picks the kernels);
+      - other int32 / int64 rows get the same table for fa_fedavg_i32_ptrs /
+        fa_fedavg_i64_ptrs, which fold_rows takes where int_row_factors
+        accepts the fold.
     fold_rows(rowset, weights) then costs the factor upload and the kernel.
     The RowSet keeps the tensors alive; their CONTENTS may change between
     folds, their storage may not (re-create the RowSet after reallocating)."""
@@ -911,8 +962,9 @@ class RowSet:
         self.ptrs = None
         self.host_ptrs = None
         self.aligned = False
-        # (float64 rows met under a stream capture keep the stacked copy they had before the row table)
-        if dt in _ROW_TABLE_DTYPES and P > 0 and not (dt == torch.float64 and torch.cuda.is_current_stream_capturing()):
+        # (float64 and integer rows met under a stream capture keep the stacked copy they had before the row table)
+        if dt in _ROW_TABLE_DTYPES and P > 0 and not (dt in _NO_CAPTURE_TABLE
+                                                      and torch.cuda.is_current_stream_capturing()):
             host_ptrs = self.host_ptrs = np.fromiter(map(torch.Tensor.data_ptr, rows), dtype=np.int64, count=N)
             self.view = _equal_stride_view(rows, host_ptrs, P)
             if self.view is None:
@@ -1025,11 +1077,33 @@ def _fold_rows_f64(rs: "RowSet", weights, scores, out, total):
     return out
 
 
+def _fold_rows_int(rs: "RowSet", f: Factors, out):
+    """int32 / int64 rows through the row table (fa_fedavg_i32_ptrs /
+    fa_fedavg_i64_ptrs) with the factors of int_row_factors; float64 out."""
+    dev, P = rs.device, rs.P
+    _check_out("out", out, torch.float64, P)
+    dst = out
+    if out is not None and rs.overlaps(out):
+        out = None
+    if out is None:
+        out = torch.empty(P, dtype=torch.float64, device=dev)
+    a, s = f.to(dev)
+    aligned = rs.aligned and out.data_ptr() % 16 == 0
+    _lib.call(_INT_ROWS[rs.dtype], rs.ptrs.data_ptr(), rs.N, P, a.data_ptr(), _ptr(s), float(f.div), int(aligned),
+              out.data_ptr(), stream_ptr(dev))
+    stats["rows_int_folds"] += 1
+    if dst is not None and dst is not out:
+        dst.reshape(-1)[:P].copy_(out)
+        return dst
+    return out
+
+
 def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
               out: Optional[torch.Tensor] = None, total=None, want_bf16: bool = False,
               out_bf16: Optional[torch.Tensor] = None):
     """The fold over separately allocated 1-D CUDA rows (no stacking copy for
-    fp32, bfloat16 and float16 / float64 rows whose result stays in their dtype).  `rows` is a
+    fp32, bfloat16, float16 / float64 rows whose result stays in their dtype, and
+    int32 / int64 rows whose products stay in their dtype: int_row_factors).  `rows` is a
     RowSet (prepared once, reusable) or a sequence of tensors (a RowSet is
     built for this call).  want_bf16 / out_bf16: as fold_stacked (bf16 rows)."""
     rs = rows if isinstance(rows, RowSet) else RowSet(rows)
@@ -1051,6 +1125,12 @@ def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
             and not torch.cuda.is_current_stream_capturing()  # captured float64 rows keep the stacked route
             and result_dtype(_F64, weights, scores, total) == _F64):
         return _fold_rows_f64(rs, weights, scores, out, total)
+    if (rs.dtype in _INT_ROWS and rs.ptrs is not None and rs.P > 0
+            and not torch.cuda.is_current_stream_capturing()):  # captured integer rows keep the stacked route
+        # integer rows whose every product stays in their dtype (numpy's OverflowError comes from here)
+        fi = _int_factors(_TORCH_TO_NP[rs.dtype], weights, scores, total)
+        if fi is not None:
+            return _fold_rows_int(rs, fi, out)
     fw = Factors.weak_f32(weights, scores, total) if rs.dtype == torch.float32 else None
     if fw is None and (rs.dtype != torch.float32
                        or result_dtype(np.dtype(np.float32), weights, scores, total) != np.float32):
@@ -1096,6 +1176,9 @@ _LAYER_TABLE = {
     torch.bfloat16: ("fa_fedavg_bf16_layers", 3),
     torch.float16: ("fa_fedavg_f16_layers", 3),
     torch.float64: ("fa_fedavg_f64_layers", 1),
+    # the plan counts output elements (doubles): four int32 / two int64 columns per 16-byte unit
+    torch.int32: ("fa_fedavg_i32_layers", 2),
+    torch.int64: ("fa_fedavg_i64_layers", 1),
 }
 _shape_of = operator.attrgetter("shape")
 _cu_counts: dict = {}
@@ -1229,6 +1312,8 @@ def _layer_factors(dt: torch.dtype, weights, scores, total) -> Optional[Factors]
         return Factors.weak_f32(weights, scores, total) or Factors(weights, scores, np.dtype(np.float32), total=total)
     if dt == torch.float16:
         return f16_factors(weights, scores, total)
+    if dt in _INT_ROWS:
+        return _int_factors(_TORCH_TO_NP[dt], weights, scores, total)
     return f64_factors(weights, scores, total)
 
 
@@ -1242,7 +1327,8 @@ def fold_model_rows(model, weights: Sequence, scores: Optional[Sequence] = None,
     tensors shaped like the layers: views of one flat result in which layer k
     starts at model.offsets[k], a multiple of 64 elements.  Each holds, bit for
     bit, what fold_rows gives for that layer alone, with fold_rows' factor
-    rules per dtype.  out / out_bf16: flat buffers of model.elems elements to
+    rules per dtype (int32 / int64 layers: float64 results, int_row_factors'
+    rules).  out / out_bf16: flat buffers of model.elems elements to
     fold into; want_bf16 / out_bf16 (bf16 layers): as fold_rows, a pair of
     lists (fp32 layers, RNE bf16 layers), or the bf16 list alone when only
     out_bf16 was given.  Where fold_rows would leave the row table (factors
@@ -1269,7 +1355,7 @@ def fold_model_rows(model, weights: Sequence, scores: Optional[Sequence] = None,
                     [r[1].reshape(s) for r, s in zip(res, ms.shapes)])
         return [r.reshape(s) for r, s in zip(res, ms.shapes)]
     dev, E = ms.device, ms.elems
-    res_dt = torch.float32 if bf16 else ms.dtype
+    res_dt = torch.float32 if bf16 else torch.float64 if ms.dtype in _INT_ROWS else ms.dtype
     _check_out("out", out, res_dt, E)
     _check_out("out_bf16", out_bf16, torch.bfloat16, E)
 
@@ -1295,6 +1381,8 @@ def fold_model_rows(model, weights: Sequence, scores: Optional[Sequence] = None,
     folded = sum(1 for n in ms.sizes if n)  # layers folded through a table, as fold_rows counts them
     if ms.dtype == torch.float64:
         stats["rows64_folds"] += folded
+    elif ms.dtype in _INT_ROWS:
+        stats["rows_int_folds"] += folded
     elif ms.dtype != torch.float32:
         stats["rows16_folds"] += folded
     if dst is not None and dst is not out:
@@ -1337,8 +1425,9 @@ def _rows_route(dt, fp32_result: bool, w, sc, total, where: torch.device, dev) -
     """Does a group of device layers of dtype dt fold per layer through
     fold_rows' row tables (no stacked copy)?  fp32 layers whose result stays
     fp32; bf16 layers (always float32 factors); float16 layers whose result
-    stays float16; float64 layers whose result stays float64.  The 16-bit and
-    float64 groups only where the layers already lie on the device the fold
+    stays float16; float64 layers whose result stays float64; int32 / int64
+    layers whose fold int_row_factors accepts (it raises numpy's OverflowError
+    here, before any launch).  The 16-bit, float64 and integer groups only where the layers already lie on the device the fold
     was asked for (the stacked copy is what moves them)."""
     if dt == torch.float32:
         return fp32_result
@@ -1349,6 +1438,9 @@ def _rows_route(dt, fp32_result: bool, w, sc, total, where: torch.device, dev) -
     if dt == torch.float64:
         return (here and not torch.cuda.is_current_stream_capturing()
                 and result_dtype(_F64, w, sc, total) == _F64)
+    if dt in _INT_ROWS:
+        return (here and not torch.cuda.is_current_stream_capturing()
+                and int_row_factors(_TORCH_TO_NP[dt], w, sc, total) is not None)
     return dt == torch.float16 and here and result_dtype(np.dtype(np.float16), w, sc, total) == np.float16
 
 
@@ -1443,8 +1535,8 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
         elif on_device and _rows_route(dtypes[lis[0]], fp32_result, w, sc, sum(total_weights),
                                        parameters[0][lis[0]].device, dev) and all(
                 parameters[i][li].is_contiguous() for i in range(n_eff) for li in lis):
-            # device fp32 / bf16 layers, and float16 / float64 layers whose result
-            # stays in their dtype: fold each layer straight from the clients' own tensors
+            # device fp32 / bf16 layers, float16 / float64 layers whose result stays in
+            # their dtype, and integer layers whose products stay in theirs: fold each layer straight from the clients' own tensors
             # through a row-pointer list -- no stacking copy.  Two or more layers: one
             # table of every layer's rows and one launch (FEDAVG_LAYER_TABLE=0: a
             # fold per layer); the same bits either way

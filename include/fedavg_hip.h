@@ -507,8 +507,8 @@ int fa_fedavg_f64_ptrs(const double* const* xi, int64_t N, int64_t P,
  * the table live in device memory: the library cannot check them against
  * tiles and units, nor see an alias (no output may overlap a row).  Not
  * covered: a tuner kind (one fixed geometry: 8 rows ahead, units by
- * fa_layers_plan's rule), help for stream capture, integer layers, the
- * sharded step, several GPUs. */
+ * fa_layers_plan's rule), help for stream capture, the sharded step, several
+ * GPUs.  Integer layers: fa_fedavg_i32_layers / fa_fedavg_i64_layers, below. */
 typedef struct fa_layer_plan {
     int64_t cols;    /* columns of the layer                                  */
     int64_t offset;  /* its first element in the flat output (multiple of 64) */
@@ -543,6 +543,52 @@ int fa_fedavg_i32(const int32_t* X, int64_t N, int64_t P, int64_t ldx,
                   const int64_t* a, double divisor, double* out, void* stream);
 int fa_fedavg_i64(const int64_t* X, int64_t N, int64_t P, int64_t ldx,
                   const int64_t* a, double divisor, double* out, void* stream);
+
+/* ---- integer layers where the clients' tensors lie (new symbols, ABI still 7)
+ * A model with BatchNorm carries one int64 counter per BatchNorm layer next to
+ * its float weights; these fold such layers through a row table, with no
+ * stacking copy, in numpy's literal arithmetic (fed_avg_aggregator.py:33,39;
+ * with scores stall_aware_aggregation.py:42-67).  T is the rows' dtype, UT its
+ * unsigned twin, a[i] the cardinalities [device, int64], s[i] [device, double]:
+ *   p_i = (T)((UT)x * (UT)(T)a[i])            wrapping, as `layer * n`
+ *   s == NULL (FedAvg):   acc = p_0, acc = wrap(acc + p_i) in T;
+ *                         out = (double)acc / divisor      -- what fa_fedavg_i32 /
+ *                         fa_fedavg_i64 compute over the same rows stacked
+ *   s != NULL (stall-aware): t_i = (double)p_i * s[i] -- numpy types `* s` in
+ *                         float64; the conversion rounds to nearest even beyond
+ *                         2^53, as numpy's cast -- acc = t_0, acc = acc + t_i in
+ *                         strict client order, multiply and add separate;
+ *                         out = acc / divisor
+ * The divide is the float64 folds' IEEE divide (a subnormal quotient on a tie
+ * rounds to even).  out is float64.
+ *   fa_fedavg_i32_ptrs / _i64_ptrs: one layer, xi a [device] array of N
+ *     [device] row pointers.  rows_aligned != 0 promises 16-B aligned rows and
+ *     out (4 int32 / 2 int64 columns per 16-byte load, 8 rows ahead); with 0,
+ *     rows at any offset of the element size and out at any 8-B offset, one
+ *     column per lane.  The same bits either way.  Argument checks and status
+ *     codes as fa_fedavg_f64_ptrs.  The layer's plan entry travels by value in
+ *     the launch: no allocation, no copy, no synchronisation.
+ *   fa_fedavg_i32_layers / _i64_layers: all L layers in one launch, xi / plan /
+ *     tiles / units as the entries above, from fa_layers_plan with unit_lg 2
+ *     (int32: four columns per 16 bytes) or 1 (int64).  The plan's offset and
+ *     elems count OUTPUT elements, doubles: every layer starts at a multiple of
+ *     64 doubles of the flat out, so a 16-B aligned out keeps every layer's
+ *     stores aligned.  An int32 unit yields four doubles, stored as two 16-byte
+ *     stores; final stores are non-temporal.  Layer l of out holds the bits of
+ *     the _ptrs entry on that layer.  Argument checks and status codes as
+ *     fa_fedavg_f64_layers.
+ * Not covered: integer layers under float weights (the product is float64) and
+ * int32 rows under int64 weights (the product is int64) -- the caller keeps
+ * them off these entries; a tuner kind; help for stream capture; the sharded
+ * step; several GPUs. */
+int fa_fedavg_i32_ptrs(const int32_t* const* xi, int64_t N, int64_t P, const int64_t* a, const double* s,
+                       double divisor, int rows_aligned, double* out, void* stream);
+int fa_fedavg_i64_ptrs(const int64_t* const* xi, int64_t N, int64_t P, const int64_t* a, const double* s,
+                       double divisor, int rows_aligned, double* out, void* stream);
+int fa_fedavg_i32_layers(const int32_t* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
+                         int units, const int64_t* a, const double* s, double divisor, double* out, void* stream);
+int fa_fedavg_i64_layers(const int64_t* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
+                         int units, const int64_t* a, const double* s, double divisor, double* out, void* stream);
 
 /* ---- host staging: page-locked documents and direct DMA ---------------------
  * A result store that keeps documents in page-locked memory lets the ingest

@@ -119,6 +119,15 @@ int fa_fedavg_f16_ptrs_form(const uint16_t* const* xi, int64_t N, int64_t P, con
 int fa_fedavg_layers_form(int dtype, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
                           int64_t tiles, int units, int64_t grid_cap, const void* a, const void* s, double divisor,
                           void* out, void* out_bf16, void* stream);
+/* The same for the integer layer-table folds (fa_fedavg_i32_layers /
+ * fa_fedavg_i64_layers), continuing the dtype codes: 4 int32, 5 int64; a
+ * [device] int64 cardinalities, s [device] doubles or NULL, out doubles.  An
+ * entry of its own: fa_fedavg_layers_form keeps refusing every code above 3.
+ * The _ptrs entries run this kernel over one by-value layer, the same tile
+ * walk, so they have no capped form of their own. */
+int fa_fedavg_int_layers_form(int dtype, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
+                              int64_t tiles, int units, int64_t grid_cap, const int64_t* a, const double* s,
+                              double divisor, double* out, void* stream);
 /* Same for the bf16 fold (variant 0 = fa_fedavg_bf16). */
 int fa_fedavg_bf16_variant(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
                            const float* a, const float* s, float divisor,
