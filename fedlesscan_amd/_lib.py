@@ -30,6 +30,9 @@ BENCH_HEADER = os.path.join(REPO, "include", "fedavg_hip_bench.h")
 ABI_VERSION = 7
 
 FA_OK, FA_ERR_ARG, FA_ERR_NO_CLIENTS, FA_ERR_SHAPE, FA_ERR_HIP = range(5)
+# fa_fedavg_widen's kinds (FA_WIDEN_* of the header): rows dtype, then the fold's
+(FA_WIDEN_F16_F32, FA_WIDEN_F16_F64, FA_WIDEN_F32_F64, FA_WIDEN_I32_F64, FA_WIDEN_I64_F64,
+ FA_WIDEN_I32_I64) = range(6)
 
 _i64 = ctypes.c_int64
 _vp = ctypes.c_void_p
@@ -94,6 +97,8 @@ _PROTOS = {
     "fa_fedavg_i64_ptrs": (_int, [_vp, _i64, _i64, _vp, _vp, _f64, _int, _vp, _vp]),
     "fa_fedavg_i32_layers": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _f64, _vp, _vp]),
     "fa_fedavg_i64_layers": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _f64, _vp, _vp]),
+    "fa_fedavg_widen": (_int, [_int, _vp, _i64, _i64, _i64, _vp, _vp, _f64, _vp, _vp]),
+    "fa_widen_geometry": (_int, [_int, _vp, _vp, _vp]),
     "fa_npz_index":(_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _int]),
     "fa_crc32": (_int, [_vp, _i64, ctypes.c_uint32, _int, ctypes.POINTER(ctypes.c_uint32)]),
     "fa_pack": (_int, [_vp, _vp, _vp, _vp, _i64, _int]),

@@ -585,6 +585,16 @@ int fa_fedavg_i64_layers(const int64_t* const* xi, const fa_layer_plan* plan, in
                                       stream);
 }
 
+// ---- promoted folds from the narrow rows (widen_fold) ------------------------
+int fa_fedavg_widen(int kind, const void* X, int64_t N, int64_t P, int64_t ldx, const void* a, const void* s,
+                    double divisor, void* out, void* stream) {
+    return widen_fold(kind, X, N, P, ldx, a, s, divisor, out, stream);
+}
+
+int fa_widen_geometry(int kind, int* unit_cols, int* units, int* rows_ahead) {
+    return widen_geometry(kind, unit_cols, units, rows_ahead);
+}
+
 // ---- the same folds with the per-client factors in host memory ---------------
 int fa_factors_fill(float* dst, const float* a, const float* s, int64_t N, void* stream) {
     if (N < 0 || (N > 0 && (!dst || !a))) return fail(FA_ERR_ARG, "fa_factors_fill: N %lld, null pointer", (long long)N);

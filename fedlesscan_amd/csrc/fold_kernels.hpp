@@ -2881,6 +2881,284 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_int_layers(
 }
 
 // ---------------------------------------------------------------------------
+// The widening folds (fa_fedavg_widen): a stacked matrix whose rows numpy
+// promotes before it multiplies -- float16 rows under float32 factors, float16,
+// float32, int32 or int64 rows under float64 factors, int32 rows under int64
+// factors -- folded from the narrow rows themselves.  A lane loads 16-byte
+// units of the SOURCE dtype (8 halves, 4 float32, 4 int32, 2 int64), widens
+// each in registers right after the load and from there on runs the wide
+// dtype's own fold: the widened unit is NV 16-byte vectors of the wide dtype
+// (f32x4, f64x2, or u64x2 for the wrapping int64 sum), each of which goes
+// through the arithmetic the wide dtype's kernels already have --
+//   float32  term4 / add4 / div4 (term1 and the plain divide for one column):
+//            fl(fl(x*a)*s), ordered adds, the IEEE float32 divide
+//   float64  term / + / DoubleArith::div (div_d1, div_d2)
+//   int64    IntAcc<Int64Rows, false>: the wrapping product and sum of
+//            k_fedavg_int computed unsigned, (double)acc, then div_d1
+// so the bits are those of widening the matrix first and folding the copy.
+// Every widening is exact but int64 -> float64, which rounds to nearest even as
+// numpy's cast does (IntAcc::dbl).  acc = t_0, strict row order, multiply and
+// add apart, as everywhere.
+//
+// The shape is that of fold_units / fold_int_units: C units per lane spaced
+// kBlock lanes apart, U rows x C units of non-temporal loads issued ahead of the
+// ordered adds, the factors scalar loads from constant address space, the
+// quotients stored non-temporally 16 bytes at a time (a half unit into float64
+// is four stores), octet_tile for the full tile, the one-unit tile and the tail
+// columns.  Where row i starts is a row source (PitchedRows here), so that a
+// row-table form is the same body over TableRows.  Rows off the unit (base or
+// pitch) or an output off 16 bytes take one lane per column, 8 rows ahead.
+// The geometry is fixed per kind (W::C units per lane, W::U rows ahead;
+// DESIGN.md 5): one block per tile.
+// ---------------------------------------------------------------------------
+typedef __attribute__((address_space(4))) const float cf32;
+typedef double f64x8 __attribute__((ext_vector_type(8)));
+typedef int64_t i64x4 __attribute__((ext_vector_type(4)));
+
+// The float64 side of the four kinds that fold in float64
+struct WidenF64 {
+    typedef double FE;  // a factor as stored
+    typedef double F;   // ... and as an operand
+    typedef double O;   // an output element
+    typedef double D;   // the divisor
+    typedef f64x2 V;    // 16 bytes of accumulators
+    typedef f64x2 Q;    // ... and of quotients
+    typedef double S;   // one column's accumulator
+    static __device__ __forceinline__ F factor(const FE* __restrict__ a, int64_t i) { return DoubleArith::factor(a, i); }
+    static __device__ __forceinline__ F one() { return 1.0; }
+    template <bool SCORED, class X>
+    static __device__ __forceinline__ X wterm(X x, F a, F s) { return term<SCORED>(x, a, s); }
+    template <class X>
+    static __device__ __forceinline__ X add(X x, X y) { return x + y; }
+    template <class X>
+    static __device__ __forceinline__ X quot(X acc, D d) { return DoubleArith::div(acc, d); }
+};
+struct WidenF16F64 : WidenF64 {
+    typedef uint16_t E;
+    static constexpr int LG = 3, NV = 4, C = 1, U = 8;  // 8 doubles per unit: one unit per lane
+    static __device__ __forceinline__ void widen(u32x4 u, V (&w)[NV]) {
+        const f64x8 d = __builtin_convertvector(__builtin_bit_cast(f16x8, u), f64x8);
+        w[0] = __builtin_shufflevector(d, d, 0, 1);
+        w[1] = __builtin_shufflevector(d, d, 2, 3);
+        w[2] = __builtin_shufflevector(d, d, 4, 5);
+        w[3] = __builtin_shufflevector(d, d, 6, 7);
+    }
+    static __device__ __forceinline__ S widen(E e) { return (double)__builtin_bit_cast(_Float16, e); }
+};
+struct WidenF32F64 : WidenF64 {
+    typedef float E;
+    static constexpr int LG = 2, NV = 2, C = 2, U = 8;
+    static __device__ __forceinline__ void widen(u32x4 u, V (&w)[NV]) {
+        const f64x4 d = __builtin_convertvector(__builtin_bit_cast(f32x4, u), f64x4);
+        w[0] = __builtin_shufflevector(d, d, 0, 1);
+        w[1] = __builtin_shufflevector(d, d, 2, 3);
+    }
+    static __device__ __forceinline__ S widen(E e) { return (double)e; }
+};
+struct WidenI32F64 : WidenF64 {
+    typedef int32_t E;
+    static constexpr int LG = 2, NV = 2, C = 2, U = 8;
+    static __device__ __forceinline__ void widen(u32x4 u, V (&w)[NV]) {
+        const f64x4 d = __builtin_convertvector(__builtin_bit_cast(i32x4, u), f64x4);
+        w[0] = __builtin_shufflevector(d, d, 0, 1);
+        w[1] = __builtin_shufflevector(d, d, 2, 3);
+    }
+    static __device__ __forceinline__ S widen(E e) { return (double)e; }
+};
+struct WidenI64F64 : WidenF64 {
+    typedef int64_t E;
+    static constexpr int LG = 1, NV = 1, C = 2, U = 8;
+    // beyond 2^53 the conversion rounds to nearest even: the one of the scored integer folds
+    static __device__ __forceinline__ void widen(u32x4 u, V (&w)[NV]) {
+        w[0] = IntAcc<Int64Rows, true>::dbl(__builtin_bit_cast(u64x2, u));
+    }
+    static __device__ __forceinline__ S widen(E e) { return (double)e; }
+};
+struct WidenF16F32 {
+    typedef uint16_t E;
+    typedef float FE;
+    typedef float F;
+    typedef float O;
+    typedef float D;
+    typedef f32x4 V;
+    typedef f32x4 Q;
+    typedef float S;
+    static constexpr int LG = 3, NV = 2, C = 2, U = 8;
+    static __device__ __forceinline__ F factor(const FE* __restrict__ a, int64_t i) { return *(cf32*)(a + i); }
+    static __device__ __forceinline__ F one() { return 1.0f; }
+    static __device__ __forceinline__ void widen(u32x4 u, V (&w)[NV]) {
+        const f32x8 d = __builtin_convertvector(__builtin_bit_cast(f16x8, u), f32x8);
+        w[0] = __builtin_shufflevector(d, d, 0, 1, 2, 3);
+        w[1] = __builtin_shufflevector(d, d, 4, 5, 6, 7);
+    }
+    static __device__ __forceinline__ S widen(E e) { return (float)__builtin_bit_cast(_Float16, e); }
+    template <bool SCORED>
+    static __device__ __forceinline__ V wterm(V x, F a, F s) { return term4<SCORED>(x, a, s); }
+    template <bool SCORED>
+    static __device__ __forceinline__ S wterm(S x, F a, F s) { return term1<SCORED>(x, a, s); }
+    static __device__ __forceinline__ V add(V x, V y) { return add4(x, y); }
+    static __device__ __forceinline__ S add(S x, S y) { return x + y; }
+    static __device__ __forceinline__ Q quot(V acc, D d) { return div4(acc, d); }
+    static __device__ __forceinline__ S quot(S acc, D d) { return acc / d; }
+};
+struct WidenI32I64 {  // unscored only: a score makes the fold float64 (WidenI32F64)
+    typedef IntAcc<Int64Rows, false> A;
+    typedef int32_t E;
+    typedef int64_t FE;
+    typedef uint64_t F;
+    typedef double O;
+    typedef double D;
+    typedef u64x2 V;
+    typedef f64x2 Q;
+    typedef uint64_t S;
+    static constexpr int LG = 2, NV = 2, C = 2, U = 8;
+    static __device__ __forceinline__ F factor(const FE* __restrict__ a, int64_t i) { return int_factor<Int64Rows>(a, i); }
+    static __device__ __forceinline__ F one() { return 1; }
+    static __device__ __forceinline__ void widen(u32x4 u, V (&w)[NV]) {  // sign-extended
+        const i64x4 d = __builtin_convertvector(__builtin_bit_cast(i32x4, u), i64x4);
+        w[0] = __builtin_bit_cast(u64x2, (i64x2)__builtin_shufflevector(d, d, 0, 1));
+        w[1] = __builtin_bit_cast(u64x2, (i64x2)__builtin_shufflevector(d, d, 2, 3));
+    }
+    static __device__ __forceinline__ S widen(E e) { return (uint64_t)(int64_t)e; }
+    template <bool SCORED, class X>
+    static __device__ __forceinline__ X wterm(X x, F a, F) { return A::term(x, a, 1.0); }
+    template <class X>
+    static __device__ __forceinline__ X add(X x, X y) { return x + y; }
+    static __device__ __forceinline__ Q quot(V acc, D d) { return DoubleArith::div(A::fin(acc), d); }
+    static __device__ __forceinline__ double quot(S acc, D d) { return DoubleArith::div(A::fin(acc), d); }
+};
+
+// The lane's C source units of the rows of src, in row order; out: the lane's
+// first unit's columns
+template <class W, int U, int C, bool SCORED, class Rows>
+__device__ __forceinline__ void widen_units(Rows src, int64_t N, const typename W::FE* __restrict__ a,
+                                            const typename W::FE* __restrict__ s, typename W::D divisor,
+                                            typename W::O* out) {
+    typedef typename W::V V;
+    typedef typename W::F F;
+    constexpr int NV = W::NV;
+    V acc[C][NV];
+    {
+        const auto* r = src.row(0);
+        const F a0 = W::factor(a, 0), s0 = SCORED ? W::factor(s, 0) : W::one();
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            V w[NV];
+            W::widen(__builtin_nontemporal_load(r + c * kBlock), w);
+#pragma unroll
+            for (int k = 0; k < NV; ++k) acc[c][k] = W::template wterm<SCORED>(w[k], a0, s0);
+        }
+    }
+    int64_t i = 1;
+    for (; i + U <= N; i += U) {
+        u32x4 v[U][C];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const auto* r = src.row(i + u);
+#pragma unroll
+            for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
+        }
+        // Every load of the group, and the group's factors, issued before the
+        // first conversion: left to itself the scheduler threads the loads
+        // through the conversions and adds to save registers, and two or three
+        // of the sixteen are in flight.  The factors stand ahead of the barrier
+        // so that their scalar loads are one group behind one wait.
+        F af[U], sf[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            af[u] = W::factor(a, i + u);
+            sf[u] = SCORED ? W::factor(s, i + u) : W::one();
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                V w[NV];
+                W::widen(v[u][c], w);
+#pragma unroll
+                for (int k = 0; k < NV; ++k)
+                    acc[c][k] = W::add(acc[c][k], W::template wterm<SCORED>(w[k], af[u], sf[u]));
+            }
+        }
+    }
+    for (; i < N; ++i) {
+        const auto* r = src.row(i);
+        const F ai = W::factor(a, i), si = SCORED ? W::factor(s, i) : W::one();
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            V w[NV];
+            W::widen(__builtin_nontemporal_load(r + c * kBlock), w);
+#pragma unroll
+            for (int k = 0; k < NV; ++k) acc[c][k] = W::add(acc[c][k], W::template wterm<SCORED>(w[k], ai, si));
+        }
+    }
+    typedef typename W::Q Q;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        Q* o = reinterpret_cast<Q*>(out + ((int64_t)c * kBlock << W::LG));
+#pragma unroll
+        for (int k = 0; k < NV; ++k) __builtin_nontemporal_store(W::quot(acc[c][k], divisor), o + k);
+    }
+}
+
+// One column: 8 rows of loads ahead of the ordered adds
+template <class W, bool SCORED, class Rows>
+__device__ __forceinline__ typename W::O widen_column(Rows src, int64_t N, const typename W::FE* __restrict__ a,
+                                                      const typename W::FE* __restrict__ s, typename W::D divisor) {
+    typedef typename W::F F;
+    typename W::S acc = W::template wterm<SCORED>(W::widen(*src.row(0)), W::factor(a, 0),
+                                                  SCORED ? W::factor(s, 0) : W::one());
+    int64_t i = 1;
+    for (; i + 8 <= N; i += 8) {
+        typename W::E v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load(src.row(i + u));
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const F ai = W::factor(a, i + u), si = SCORED ? W::factor(s, i + u) : W::one();
+            acc = W::add(acc, W::template wterm<SCORED>(W::widen(v[u]), ai, si));
+        }
+    }
+    for (; i < N; ++i)
+        acc = W::add(acc, W::template wterm<SCORED>(W::widen(*src.row(i)), W::factor(a, i),
+                                                    SCORED ? W::factor(s, i) : W::one()));
+    return W::quot(acc, divisor);
+}
+
+// one block per tile of W::C units per lane: rows and out 16-B aligned, the pitch a multiple of the unit
+template <class W, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_widen(
+    const typename W::E* __restrict__ X, int64_t N, int64_t P, int64_t ldx, const typename W::FE* __restrict__ a,
+    const typename W::FE* __restrict__ s, typename W::D divisor, typename W::O* __restrict__ out) {
+    typedef typename W::E E;
+    const u32x4* XU = reinterpret_cast<const u32x4*>(X);
+    const int64_t ldu = ldx >> W::LG;
+    octet_tile<W::C, kBlock, W::LG>(
+        blockIdx.x, P,
+        [&](int64_t o) {
+            widen_units<W, W::U, W::C, SCORED>(PitchedRows<u32x4>{XU + o, ldu}, N, a, s, divisor,
+                                                  out + (o << W::LG));
+        },
+        [&](int64_t o) {
+            widen_units<W, W::U, 1, SCORED>(PitchedRows<u32x4>{XU + o, ldu}, N, a, s, divisor, out + (o << W::LG));
+        },
+        [&](int64_t col) {
+            for (; col < P; ++col) out[col] = widen_column<W, SCORED>(PitchedRows<E>{X + col, ldx}, N, a, s, divisor);
+        });
+}
+
+// one column per lane: any element-aligned base, pitch and output
+template <class W, bool SCORED>
+__global__ __launch_bounds__(kBlock) void k_fedavg_widen_scalar(
+    const typename W::E* __restrict__ X, int64_t N, int64_t P, int64_t ldx, const typename W::FE* __restrict__ a,
+    const typename W::FE* __restrict__ s, typename W::D divisor, typename W::O* __restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= P) return;
+    out[c] = widen_column<W, SCORED>(PitchedRows<typename W::E>{X + c, ldx}, N, a, s, divisor);
+}
+
+// ---------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------
 inline dim3 grid_for(int64_t lanes) { return dim3((unsigned)((lanes + kBlock - 1) / kBlock)); }
@@ -4616,6 +4894,67 @@ int int_rows_fold(const char* what, const typename I::T* const* xi, int64_t N, i
     launch_int_layers_units<I>(units, st, (unsigned)tile_grid(tiles, -1, cus), xi, nullptr, one, 1, N, tiles, a, s,
                                divisor, out);
     return check_launch(what);
+}
+
+// ---- the widening folds (fa_fedavg_widen) -----------------------------------
+// One geometry per kind, fixed here, no tuner kind: one block per tile of W::C
+// units per lane, W::U rows ahead; off the unit, one column
+// per lane.
+template <class W>
+void launch_widen(hipStream_t st, const void* X, int64_t N, int64_t P, int64_t ldx, const void* a, const void* s,
+                  double divisor, void* out) {
+    const typename W::E* x = (const typename W::E*)X;
+    const typename W::FE *af = (const typename W::FE*)a, *sf = (const typename W::FE*)s;
+    const typename W::D d = (typename W::D)divisor;
+    typename W::O* o = (typename W::O*)out;
+    const bool vec = aligned16(X) && aligned16(out) && (ldx % (1 << W::LG) == 0);
+    const dim3 g = vec ? dim3((unsigned)octet_grid(P, W::C, 0, 1, W::LG).grid) : grid_for(P);
+    auto k = vec ? k_fedavg_widen<W, false> : k_fedavg_widen_scalar<W, false>;
+    if constexpr (!std::is_same<W, WidenI32I64>::value) {
+        if (s) k = vec ? k_fedavg_widen<W, true> : k_fedavg_widen_scalar<W, true>;
+    }
+    hipLaunchKernelGGL(k, g, dim3(kBlock), 0, st, x, N, P, ldx, af, sf, d, o);
+}
+
+template <class F>
+bool with_widen_kind(int kind, F f) {
+    switch (kind) {
+        case FA_WIDEN_F16_F32: f(WidenF16F32{}); return true;
+        case FA_WIDEN_F16_F64: f(WidenF16F64{}); return true;
+        case FA_WIDEN_F32_F64: f(WidenF32F64{}); return true;
+        case FA_WIDEN_I32_F64: f(WidenI32F64{}); return true;
+        case FA_WIDEN_I64_F64: f(WidenI64F64{}); return true;
+        case FA_WIDEN_I32_I64: f(WidenI32I64{}); return true;
+    }
+    return false;
+}
+
+inline int widen_fold(int kind, const void* X, int64_t N, int64_t P, int64_t ldx, const void* a, const void* s,
+                      double divisor, void* out, void* stream) {
+    if (!with_widen_kind(kind, [](auto) {})) return fail(FA_ERR_ARG, "fa_fedavg_widen: unknown kind %d", kind);
+    int rc = check_common(N, P, ldx, X, a, out);
+    if (rc) return rc;
+    if (kind == FA_WIDEN_I32_I64 && s)
+        return fail(FA_ERR_ARG, "fa_fedavg_widen: int32 rows under int64 factors take no scores (s must be NULL)");
+    if (P == 0) { g_err[0] = 0; return FA_OK; }
+    if (P / kBlock >= (int64_t)0x7FFFFFFF) return fail(FA_ERR_ARG, "P too large for one launch");
+    StreamDevice on_stream_device(stream);
+    with_widen_kind(kind, [&](auto w) {
+        launch_widen<decltype(w)>((hipStream_t)stream, X, N, P, ldx, a, s, divisor, out);
+    });
+    return check_launch("fa_fedavg_widen");
+}
+
+inline int widen_geometry(int kind, int* unit_cols, int* units, int* rows_ahead) {
+    if (!unit_cols || !units || !rows_ahead) return fail(FA_ERR_ARG, "fa_widen_geometry: null pointer");
+    const bool known = with_widen_kind(kind, [&](auto w) {
+        *unit_cols = 1 << decltype(w)::LG;
+        *units = decltype(w)::C;
+        *rows_ahead = decltype(w)::U;
+    });
+    if (!known) return fail(FA_ERR_ARG, "fa_widen_geometry: unknown kind %d", kind);
+    g_err[0] = 0;
+    return FA_OK;
 }
 
 inline int layers_plan(const int64_t* cols, const int32_t* aligned, int64_t L, int unit_lg, int64_t cus, int units,

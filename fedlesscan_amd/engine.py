@@ -335,6 +335,38 @@ def _captured_factors(f: Factors, dev) -> tuple:
     return buf[:n], (None if f.s is None else buf[n:])
 
 
+# fa_fedavg_widen's kinds (include/fedavg_hip.h, FA_WIDEN_*): (row dtype, fold dtype) -> kind
+_WIDEN_KINDS = {(_F16, _F32): _lib.FA_WIDEN_F16_F32, (_F16, _F64): _lib.FA_WIDEN_F16_F64,
+                (_F32, _F64): _lib.FA_WIDEN_F32_F64, (np.dtype(np.int32), _F64): _lib.FA_WIDEN_I32_F64,
+                (np.dtype(np.int64), _F64): _lib.FA_WIDEN_I64_F64,
+                (np.dtype(np.int32), np.dtype(np.int64)): _lib.FA_WIDEN_I32_I64}
+
+
+def widen_kind(in_dt, dt) -> Optional[int]:
+    """The fa_fedavg_widen kind that folds rows of dtype `in_dt` in the promoted
+    dtype `dt` (a fold_plan's `uniform`) from the narrow rows themselves, or
+    None: the fold stays in its dtype, numpy types it term by term (dt None),
+    or no kernel converts that pair on load.  Pure host code."""
+    if in_dt is None or dt is None:
+        return None
+    return _WIDEN_KINDS.get((np.dtype(in_dt), np.dtype(dt)))
+
+
+def widen_enabled() -> bool:
+    """FEDAVG_WIDEN=0 keeps a promoted stacked fold on the widened copy
+    (X.to(wide dtype), then the wide dtype's kernel).  Read per call, so a
+    process can switch it between folds."""
+    return os.environ.get("FEDAVG_WIDEN", "1") != "0"
+
+
+def _widen(kind: Optional[int], P: int) -> bool:
+    """A promoted stacked fold reads the narrow rows (fa_fedavg_widen): a kind
+    exists, there are columns, no capture is in progress (a captured fold keeps
+    the route it had), and the switch is on."""
+    return (kind is not None and P > 0 and widen_enabled()
+            and not torch.cuda.is_current_stream_capturing())
+
+
 def _check_matrix(X: torch.Tensor) -> tuple[int, int, int]:
     if not X.is_cuda:
         raise ValueError("X must be a CUDA (HIP) tensor")
@@ -412,6 +444,12 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
         f = Factors(weights, None, dt, int_weights=True, total=total)
         a, _ = f.to(dev)
         if in_dt != dt:
+            if _widen(widen_kind(in_dt, dt), P):  # int32 rows, int64 products: sign-extended on load
+                out = out if out is not None else torch.empty(P, dtype=torch.float64, device=dev)
+                _lib.call("fa_fedavg_widen", widen_kind(in_dt, dt), X.data_ptr(), N, P, ldx, a.data_ptr(), None,
+                          f.div, out.data_ptr(), st)
+                stats["widened_folds"] += 1
+                return out
             X = X.to(_NP_TO_TORCH[dt])
             ldx = X.stride(0) if N > 1 else max(P, 1)
         out = out if out is not None else torch.empty(P, dtype=torch.float64, device=dev)
@@ -436,7 +474,18 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
     if dt not in (np.float32, np.float64):
         raise InvalidParameterShapeError(f"unsupported result dtype {dt} (input {in_dt})")
     if in_dt != dt:
-        # numpy promotes the operand before multiplying; same on the device.
+        # numpy promotes the operand before multiplying; same on the device: in
+        # registers, right after the load (fa_fedavg_widen), or, where no kernel
+        # does (and for the opt-in split fold), as a widened copy of the rows
+        kind = widen_kind(in_dt, dt)
+        if (exact or dt != np.float32) and _widen(kind, P):
+            f = Factors(weights, scores, dt, total=total)
+            out = out if out is not None else torch.empty(P, dtype=_NP_TO_TORCH[dt], device=dev)
+            a, s = f.to(dev)
+            _lib.call("fa_fedavg_widen", kind, X.data_ptr(), N, P, ldx, a.data_ptr(), _ptr(s), float(f.div),
+                      out.data_ptr(), st)
+            stats["widened_folds"] += 1
+            return out
         X = X.to(_NP_TO_TORCH[dt])
         ldx = X.stride(0) if N > 1 else max(P, 1)
     f = fw or Factors(weights, scores, dt, total=total)
@@ -916,8 +965,10 @@ _NO_CAPTURE_TABLE = (torch.float64, torch.int32, torch.int64)
 # float64 folds that ran through a row table (layers: a one-launch model fold
 # counts each of its layers), layer groups copied into a stacked matrix,
 # one-launch model folds (fa_fedavg_*_layers), integer folds that ran through a
-# row table (counted as the float64 ones)
-stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0, "layer_table_folds": 0, "rows_int_folds": 0}
+# row table (counted as the float64 ones), promoted stacked folds that read
+# the narrow rows (fa_fedavg_widen; nothing else counts there)
+stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0, "layer_table_folds": 0, "rows_int_folds": 0,
+         "widened_folds": 0}
 
 
 class RowSet:

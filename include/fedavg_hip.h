@@ -590,6 +590,50 @@ int fa_fedavg_i32_layers(const int32_t* const* xi, const fa_layer_plan* plan, in
 int fa_fedavg_i64_layers(const int64_t* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles,
                          int units, const int64_t* a, const double* s, double divisor, double* out, void* stream);
 
+/* ---- promoted folds from the narrow rows (new symbols, ABI still 7) ----------
+ * numpy types `layer * num_examples` (fed_avg_aggregator.py:33; with scores
+ * stall_aware_aggregation.py:52-66) by the operands: a numpy-scalar cardinality
+ * (an np.int64 from len() of an array, an np.float32 weight) or a float
+ * default_cardinality promotes the layer before the product, and the running
+ * sum (fed_avg_aggregator.py:38-41) and the quotient stay in the promoted
+ * dtype.  fa_fedavg_widen folds a stacked matrix of such rows without a widened
+ * copy: each 16-byte unit of the rows' own dtype is converted in registers
+ * right after its load, and the fold continues in the wide dtype's arithmetic.
+ *   kind              rows      a, s      out      the bits of
+ *   FA_WIDEN_F16_F32  binary16  float32   float32  fa_fedavg_f32 over the rows as float32
+ *   FA_WIDEN_F16_F64  binary16  double    double   fa_fedavg_f64 over the rows as double
+ *   FA_WIDEN_F32_F64  float32   double    double   fa_fedavg_f64 ...
+ *   FA_WIDEN_I32_F64  int32     double    double   fa_fedavg_f64 over (double)x
+ *   FA_WIDEN_I64_F64  int64     double    double   fa_fedavg_f64 over (double)x, which rounds
+ *                                                  to nearest even beyond 2^53 as numpy's cast
+ *   FA_WIDEN_I32_I64  int32     int64     double   fa_fedavg_i64 over the sign-extended rows:
+ *                                                  wrapping product and sum, (double)acc / divisor
+ * X is [N][ldx] in the rows' dtype, ldx in its elements; a and s are [device]
+ * arrays in the kind's factor type, s NULL for FedAvg and always NULL for
+ * FA_WIDEN_I32_I64 (a score makes that fold float64: FA_WIDEN_I32_F64); the
+ * divisor is exact in a double for every kind (FA_WIDEN_F16_F32 is given a
+ * value that is a float32).  Strict client order, acc = t_0, multiply and add
+ * apart, the wide dtype's IEEE divide, subnormals kept, final stores
+ * non-temporal.  One fixed geometry, no tuner kind: one block per tile of 256
+ * lanes x `units` 16-byte source units, 8 rows of loads ahead of the ordered
+ * adds (fa_widen_geometry reports it); X or out off 16-B alignment, or ldx not
+ * a multiple of the unit's columns: one column per lane, 8 rows ahead, the same
+ * bits.  Argument checks and status codes as fa_fedavg_f64; an unknown kind, or
+ * s != NULL with FA_WIDEN_I32_I64 -> FA_ERR_ARG.  Not covered: row tables and
+ * layer tables of promoted rows, folds numpy types term by term, the ingest
+ * pipe, the sharded step. */
+#define FA_WIDEN_F16_F32 0
+#define FA_WIDEN_F16_F64 1
+#define FA_WIDEN_F32_F64 2
+#define FA_WIDEN_I32_F64 3
+#define FA_WIDEN_I64_F64 4
+#define FA_WIDEN_I32_I64 5
+int fa_fedavg_widen(int kind, const void* X, int64_t N, int64_t P, int64_t ldx,
+                    const void* a, const void* s, double divisor, void* out, void* stream);
+/* [host] The geometry of a kind: the columns of a 16-byte source unit, the
+ * units per lane of a tile, the rows of loads ahead.  Touches no GPU. */
+int fa_widen_geometry(int kind, int* unit_cols, int* units, int* rows_ahead);
+
 /* ---- host staging: page-locked documents and direct DMA ---------------------
  * A result store that keeps documents in page-locked memory lets the ingest
  * DMA each client's layers straight from the document into the device chunk,
