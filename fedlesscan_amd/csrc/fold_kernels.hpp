@@ -91,6 +91,25 @@ void with_flags(bool sc, bool acc, bool fin, F f) {
     }
 }
 
+// Scored or plain as a template argument: f(SC) gets std::true_type or
+// std::false_type.  !BOTH: the plain form alone exists (sc is not looked at).
+template <bool BOTH = true, class F>
+void with_scored(bool sc, F f) {
+    if constexpr (BOTH) {
+        if (sc) { f(std::true_type{}); return; }
+    }
+    f(std::false_type{});
+}
+// 4, 2 or (anything else) 1 units per lane as a template argument: f(std::integral_constant<int, C>)
+template <class F>
+void with_units(int units, F f) {
+    switch (units) {
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        default: f(std::integral_constant<int, 1>{}); break;
+    }
+}
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // f32x4 in the global address space: loads through pointers read from memory
 // (row tables) are global_load, not flat_load
@@ -2089,45 +2108,67 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f64(
 }
 
 // ---------------------------------------------------------------------------
-// The native-arithmetic folds (float16 and float64): every product, every sum
-// and the quotient round to the element's own format, as the reference does
-// (numpy keeps a float16 layer float16 under Python-number weights, and a
-// float64 layer is double throughout); no FMA (-ffp-contract=off keeps multiply
-// and add apart).  One body per job -- a unit fold, a column fold, a stacked
-// tile, a row-table tile -- written over an arithmetic, of which there are two:
-//   HalfArith    8 columns per 16-byte unit (an octet).  The load IS the
-//     operand: 8 halves in 4 registers, no unpack, the accumulator 4 packed
-//     registers per octet, v_pk_mul_f16 / v_pk_add_f16 two columns each.  The
-//     quotient is the IEEE float32 divide of the exactly converted operands,
-//     rounded once to half: float32 carries 24 >= 2 * 11 + 2 bits, so that
-//     double rounding equals the correctly rounded binary16 quotient (numpy
-//     computes it the same way).  The divisor arrives as a float32 kernel
-//     argument (the half's exact value), which also keeps the compiler from
-//     narrowing the divide to its own half expansion.
-//   DoubleArith  2 columns per unit (a pair): the arithmetic of
-//     k_fedavg_f64_v2 -- double multiply, double add, div_d1.
-// A lane owns C units spaced kBlock lanes apart and issues U rows x C units of
-// non-temporal loads ahead of the ordered adds; where row i starts is a row
-// source (PitchedRows, TableRows).  The switches of the fp32 fold_quads (the
-// chunked folds fa_fold_f16 / fa_fold_f64 use them; every other caller is
-// !ACC, FIN):
+// The unit folds: the native-arithmetic folds (float16, float64), the integer
+// row-table folds and the widening folds.  One schedule, written once over an
+// arithmetic description A:
+//   - a lane owns C 16-byte units of the SOURCE dtype spaced kBlock lanes
+//     apart; where row i starts is a row source (PitchedRows, TableRows);
+//   - a loaded unit becomes A::NV accumulator vectors (A::widen), each with a
+//     term, an add and a quotient; acc = t_0, not 0 + t_0 (a column of -0.0
+//     stays -0.0), strict row order, multiply and add apart (no FMA:
+//     -ffp-contract=off);
+//   - U rows x C units of non-temporal loads are issued ahead of the ordered
+//     adds, a one-row loop folds the rest;
+//   - the factors are inputs no launch writes and are read as constant memory,
+//     so they are scalar loads wherever they stand (behind a scheduling barrier
+//     the compiler otherwise falls back to a vector load, which puts a
+//     wave-uniform value on the row loads' counter);
+//   - the quotients are stored non-temporally 16 bytes at a time (an int32 unit
+//     is two stores, a half unit into float64 four);
+//   - fold_column is the one-column twin (AHEAD: 8 rows of loads ahead) for a
+//     tile's tail columns, unaligned layers and the one-column kernels;
+//   - unit_tile is the octet_tile call over a row-source factory, unit_layers
+//     the layer-table loop around it.
+// What the copies of the schedule once differed in is a named constant of the
+// description: barrier(U, C) (a scheduling barrier between the group's loads
+// and its adds), kFactorsAhead (the group's factors read ahead of that barrier,
+// so that their scalar loads are one group behind one wait, or in the add
+// loop), kOctetsLd (the group loaded through octets_ld or in place), kAhead
+// (the column fold of a tile's tail and of an unaligned layer), kTailLoop (the
+// tail lane loops over its columns, or has exactly one), kStoreLoop (a unit's
+// quotient vectors stored in a loop, or its one vector without).
+// The contract of a description: weight() and score() may return different
+// operand types (the integer folds: the rows' unsigned type and double) and
+// read different stored types (WE, SE); one() has score()'s type; score() is
+// never called by an unscored fold (WidenI32I64's is a placeholder); term<SC>
+// gets the fold's own switch (IntAcc, whose accumulator type depends on it,
+// asserts that it is its own).
+// The switches of the fp32 fold_quads (the chunked folds fa_fold_f16 /
+// fa_fold_f64 use them; every other caller is !ACC, FIN, WT = 0, and only the
+// native arithmetics can carry an accumulator in the element's own format):
 //   ACC: the fold continues from acc_in (may alias out: a lane reads its own
-//        units before it writes them); !ACC: acc = t_0, not 0 + t_0, so a
-//        column of -0.0 stays -0.0.
+//        units before it writes them).
 //   FIN: out = fl(acc / divisor); !FIN: out = acc.  Every add already rounds to
 //        the element's format, so the values carried from one chunk to the next
 //        are the accumulator itself: any cut of the rows gives the bits of one
-//        fa_fedavg_f16 / fa_fedavg_f64 over all of them.
+//        fa_fedavg_f16 / fa_fedavg_f64 over all of them.  The partial
+//        accumulator is stored with plain stores (the next chunk reads it back).
 //   WT (the one-launch step, final results only): the quotient units stored
 //        write-through over the tile's wave-uniform base, as fold_octets stores
 //        outb -- no non-temporal store there (no valid producer form for a
 //        round another stream reads).
-// The partial accumulator is stored with plain stores (the next chunk's fold
-// reads it back), the final result non-temporally.  The factors are inputs no
-// launch writes and are read as constant memory, so they are scalar loads
-// wherever they stand (behind a scheduling barrier the compiler otherwise falls
-// back to a vector load, which puts a wave-uniform value on the row loads'
-// counter).
+//
+// HalfArith: 8 columns per unit (an octet); every product, sum and the quotient
+// round to float16, as numpy keeps a float16 layer float16 under Python-number
+// weights.  The load IS the operand: 8 halves in 4 registers, no unpack,
+// v_pk_mul_f16 / v_pk_add_f16 two columns each.  The quotient is the IEEE
+// float32 divide of the exactly converted operands, rounded once to half:
+// float32 carries 24 >= 2 * 11 + 2 bits, so that double rounding equals the
+// correctly rounded binary16 quotient (numpy computes it the same way).  The
+// divisor arrives as a float32 kernel argument (the half's exact value), which
+// also keeps the compiler from narrowing the divide to its own half expansion.
+// DoubleArith: 2 columns per unit (a pair), the arithmetic of k_fedavg_f64_v2
+// -- double multiply, double add, div_d1.
 // ---------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
@@ -2136,16 +2177,25 @@ typedef __attribute__((address_space(1))) const f64x2 gf64x2;
 typedef __attribute__((address_space(1))) const double gf64;
 typedef __attribute__((address_space(4))) const double cf64;
 
+// t_i = fl(fl(x*a) * s) of a vector or a column: two roundings, left to right
+template <bool SCORED, class X, class F>
+__device__ __forceinline__ X term_fl(X x, F a, F s) {
+    X t = x * a;
+    if constexpr (SCORED) t = t * s;
+    return t;
+}
+
 struct HalfArith {
-    typedef uint16_t E;    // an element, a factor: the half's bits
-    typedef _Float16 S;    // one column's arithmetic
-    typedef f16x8 V;       // a unit's arithmetic
-    typedef u32x4 Unit;    // a unit as loaded and stored
-    typedef gu32x4 GUnit;  // ... and as global memory (TableRows)
+    typedef uint16_t E, WE, SE, O;  // an element, a stored weight, score and output: the half's bits
+    typedef _Float16 S;             // one column's arithmetic
+    typedef f16x8 V, X;             // a unit's arithmetic
+    typedef u32x4 Unit, Q;          // a unit as loaded and stored
+    typedef gu32x4 GUnit;           // ... and as global memory (TableRows)
     typedef gu16 GE;
-    typedef float D;       // the divisor
-    static constexpr int LG = 3;          // columns per unit, as a power of two
+    typedef float D;                // the divisor
+    static constexpr int LG = 3, NV = 1;  // columns per unit as a power of two; accumulator vectors per unit
     static constexpr bool kAhead = false;  // a tile's tail columns, an unaligned layer's: one row at a time
+    static constexpr bool kFactorsAhead = false, kOctetsLd = true, kTailLoop = true, kStoreLoop = false;
     // 2 rows x 8 octets (and the deep unrolls, as the bf16 fold): every load of
     // the group issued before the first add, the factors' scalar loads behind
     // them.  Left to itself the scheduler interleaved the short packed-half
@@ -2159,67 +2209,90 @@ struct HalfArith {
     // loads.  So: the aligned dword that holds the half -- the same 4-byte
     // word, hence the same page and allocation granule as the half itself --
     // and the half picked from it.
-    static __device__ __forceinline__ S factor(const E* __restrict__ a, int64_t i) {
+    static __device__ __forceinline__ S weight(const E* __restrict__ a, int64_t i) {
         const E* q = a + i;
         const uint32_t w = *(cu32*)reinterpret_cast<const uint32_t*>(__builtin_align_down(q, 4));
-        return val((E)(__builtin_is_aligned(q, 4) ? w : (w >> 16)));
+        return widen((E)(__builtin_is_aligned(q, 4) ? w : (w >> 16)));
     }
+    static __device__ __forceinline__ S score(const E* __restrict__ s, int64_t i) { return weight(s, i); }
     static __device__ __forceinline__ S one() { return (S)1; }
-    static __device__ __forceinline__ S val(E b) { return __builtin_bit_cast(S, b); }
-    static __device__ __forceinline__ E bits(S h) { return __builtin_bit_cast(E, h); }
-    static __device__ __forceinline__ V vec(Unit u) { return __builtin_bit_cast(V, u); }
-    static __device__ __forceinline__ Unit unit(V v) { return __builtin_bit_cast(Unit, v); }
-    static __device__ __forceinline__ V div(V acc, D d) {
-        return __builtin_convertvector(__builtin_convertvector(acc, f32x8) / d, V);
+    static __device__ __forceinline__ void widen(Unit u, V (&w)[NV]) { w[0] = __builtin_bit_cast(V, u); }
+    static __device__ __forceinline__ S widen(E b) { return __builtin_bit_cast(S, b); }
+    template <bool SCORED, class T>
+    static __device__ __forceinline__ T term(T x, S a, S s) { return term_fl<SCORED>(x, a, s); }
+    static __device__ __forceinline__ Q quot(V acc, D d) {
+        return unit(__builtin_convertvector(__builtin_convertvector(acc, f32x8) / d, V));
     }
-    static __device__ __forceinline__ S div(S acc, D d) { return (S)((float)acc / d); }
+    static __device__ __forceinline__ void store(Q* o, V acc, D d) { __builtin_nontemporal_store(quot(acc, d), o); }
+    static __device__ __forceinline__ O quot(S acc, D d) { return bits((S)((float)acc / d)); }
+    // the accumulator as the chunked fold carries it (!FIN)
+    static __device__ __forceinline__ Unit unit(V v) { return __builtin_bit_cast(Unit, v); }
+    static __device__ __forceinline__ E bits(S h) { return __builtin_bit_cast(E, h); }
 };
 struct DoubleArith {
-    typedef double E;
-    typedef double S;
-    typedef f64x2 V;
-    typedef f64x2 Unit;
+    typedef double E, WE, SE, O, S, D;
+    typedef f64x2 V, X, Unit, Q;
     typedef gf64x2 GUnit;
     typedef gf64 GE;
-    typedef double D;
-    static constexpr int LG = 1;
+    static constexpr int LG = 1, NV = 1;
     static constexpr bool kAhead = true;  // the P % 2 column: 8 rows of loads ahead
+    // pairs are loaded in place, octets through octets_ld: each side as it was
+    // before the two shared a body (the other way round the compiler restructured
+    // the row group of either; profiles/native_refactor/)
+    static constexpr bool kFactorsAhead = false, kOctetsLd = false, kTailLoop = false, kStoreLoop = false;
     static constexpr bool barrier(int, int) { return false; }
-    static __device__ __forceinline__ S factor(const E* __restrict__ a, int64_t i) { return *(cf64*)(a + i); }
+    static __device__ __forceinline__ S weight(const E* __restrict__ a, int64_t i) { return *(cf64*)(a + i); }
+    static __device__ __forceinline__ S score(const E* __restrict__ s, int64_t i) { return weight(s, i); }
     static __device__ __forceinline__ S one() { return 1.0; }
-    static __device__ __forceinline__ S val(E x) { return x; }
-    static __device__ __forceinline__ E bits(S x) { return x; }
-    static __device__ __forceinline__ V vec(Unit u) { return u; }
+    static __device__ __forceinline__ void widen(Unit u, V (&w)[NV]) { w[0] = u; }
+    static __device__ __forceinline__ S widen(E x) { return x; }
+    template <bool SCORED, class T>
+    static __device__ __forceinline__ T term(T x, S a, S s) { return term_fl<SCORED>(x, a, s); }
+    static __device__ __forceinline__ Q quot(V acc, D d) { return div_d2(acc, d); }
+    static __device__ __forceinline__ O quot(S acc, D d) { return div_d1(acc, d); }
+    static __device__ __forceinline__ void store(Q* o, V acc, D d) { __builtin_nontemporal_store(quot(acc, d), o); }
     static __device__ __forceinline__ Unit unit(V v) { return v; }
-    static __device__ __forceinline__ V div(V acc, D d) { return div_d2(acc, d); }
-    static __device__ __forceinline__ S div(S acc, D d) { return div_d1(acc, d); }
+    static __device__ __forceinline__ E bits(S x) { return x; }
 };
 
-// t_i = fl(fl(x*a) * s) of a unit or a column: two roundings, left to right
-template <bool SCORED, class X, class F>
-__device__ __forceinline__ X term(X x, F a, F s) {
-    X t = x * a;
-    if constexpr (SCORED) t = t * s;
-    return t;
-}
-template <class A, bool FIN>
-__device__ __forceinline__ void st_unit(typename A::Unit* out, typename A::V acc, typename A::D divisor) {
-    if constexpr (FIN) __builtin_nontemporal_store(A::unit(A::div(acc, divisor)), out);
-    else *out = A::unit(acc);
+// client i's score as an operand, the multiplicative one for an unscored fold
+template <class A, bool SCORED>
+__device__ __forceinline__ auto score_of(const typename A::SE* __restrict__ s, int64_t i) {
+    return SCORED ? A::score(s, i) : A::one();
 }
 
-// One column (a tile's tail lane, the one-column kernels).  AHEAD: 8 rows of
-// loads ahead of the ordered adds.
+// The terms of one loaded unit: the accumulators themselves (FIRST: acc = t_0)
+// or added to them.  A unit of one vector goes without the loop: around a
+// single-trip loop the compiler exchanged the operands of the add (or of the
+// score's multiply) in the float16 and float64 kernels.
+template <class A, bool SCORED, bool FIRST, class FW, class FS>
+__device__ __forceinline__ void unit_terms(typename A::V (&acc)[A::NV], typename A::Unit u, FW a, FS s) {
+    typename A::X w[A::NV];
+    A::widen(u, w);
+    if constexpr (A::NV == 1) {
+        if constexpr (FIRST) acc[0] = A::template term<SCORED>(w[0], a, s);
+        else acc[0] = acc[0] + A::template term<SCORED>(w[0], a, s);
+    } else {
+#pragma unroll
+        for (int k = 0; k < A::NV; ++k) {
+            if constexpr (FIRST) acc[k] = A::template term<SCORED>(w[k], a, s);
+            else acc[k] = acc[k] + A::template term<SCORED>(w[k], a, s);
+        }
+    }
+}
+
+// One column (a tile's tail lane, an unaligned layer, the one-column kernels).
+// AHEAD: 8 rows of loads ahead of the ordered adds.
 template <class A, bool SCORED, bool ACC, bool FIN, bool AHEAD, class Rows>
-__device__ __forceinline__ typename A::E fold_column(Rows src, int64_t N, const typename A::E* __restrict__ a,
-                                                     const typename A::E* __restrict__ s,
+__device__ __forceinline__ typename A::O fold_column(Rows src, int64_t N, const typename A::WE* __restrict__ a,
+                                                     const typename A::SE* __restrict__ s,
                                                      const typename A::E* acc_in, typename A::D divisor) {
     typename A::S acc;
     int64_t i = 0;
     if constexpr (ACC) {
-        acc = A::val(*acc_in);
+        acc = A::widen(*acc_in);
     } else {
-        acc = term<SCORED>(A::val(*src.row(0)), A::factor(a, 0), SCORED ? A::factor(s, 0) : A::one());
+        acc = A::template term<SCORED>(A::widen(*src.row(0)), A::weight(a, 0), score_of<A, SCORED>(s, 0));
         i = 1;
     }
     if constexpr (AHEAD) {
@@ -2229,42 +2302,42 @@ __device__ __forceinline__ typename A::E fold_column(Rows src, int64_t N, const 
             for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load(src.row(i + u));
 #pragma unroll
             for (int u = 0; u < 8; ++u)
-                acc = acc + term<SCORED>(A::val(v[u]), A::factor(a, i + u), SCORED ? A::factor(s, i + u) : A::one());
+                acc = acc + A::template term<SCORED>(A::widen(v[u]), A::weight(a, i + u), score_of<A, SCORED>(s, i + u));
         }
     }
     for (; i < N; ++i)
-        acc = acc + term<SCORED>(A::val(*src.row(i)), A::factor(a, i), SCORED ? A::factor(s, i) : A::one());
-    return A::bits(FIN ? A::div(acc, divisor) : acc);
+        acc = acc + A::template term<SCORED>(A::widen(*src.row(i)), A::weight(a, i), score_of<A, SCORED>(s, i));
+    if constexpr (FIN) return A::quot(acc, divisor);
+    else return A::bits(acc);
 }
 
 // The unit fold: the lane's C units of the rows of src, in row order; acc_in
-// and out point at the lane's first unit.
+// points at the lane's first unit, out at that unit's first 16 bytes of results.
 template <class A, int U, int C, bool SCORED, bool ACC, bool FIN, int WT = 0, class Rows>
-__device__ __forceinline__ void fold_units(Rows src, int64_t N, const typename A::E* __restrict__ a,
-                                           const typename A::E* __restrict__ s, const typename A::Unit* acc_in,
-                                           typename A::D divisor, typename A::Unit* out) {
+__device__ __forceinline__ void fold_units(Rows src, int64_t N, const typename A::WE* __restrict__ a,
+                                           const typename A::SE* __restrict__ s, const typename A::Unit* acc_in,
+                                           typename A::D divisor, typename A::Q* out) {
     static_assert(!WT || (!ACC && FIN), "write-through stores are for final results");
-    typedef typename A::S S;
-    typename A::V acc[C];
+    static_assert((!ACC && FIN && !WT) || (A::NV == 1 && sizeof(typename A::V) == 16), "a carried accumulator is a unit");
+    constexpr int NV = A::NV;
+    typedef decltype(A::weight(a, 0)) FW;
+    typedef decltype(A::score(s, 0)) FS;
+    typename A::V acc[C][NV];
     int64_t i = 0;
     if constexpr (ACC) {
 #pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = A::vec(acc_in[c * kBlock]);
+        for (int c = 0; c < C; ++c) A::widen(acc_in[c * kBlock], acc[c]);
     } else {
         const auto* r = src.row(0);
-        const S a0 = A::factor(a, 0), s0 = SCORED ? A::factor(s, 0) : A::one();
+        const FW a0 = A::weight(a, 0);
+        const FS s0 = score_of<A, SCORED>(s, 0);
 #pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = term<SCORED>(A::vec(__builtin_nontemporal_load(r + c * kBlock)), a0, s0);
+        for (int c = 0; c < C; ++c) unit_terms<A, SCORED, true>(acc[c], __builtin_nontemporal_load(r + c * kBlock), a0, s0);
         i = 1;
     }
     for (; i + U <= N; i += U) {
         typename A::Unit v[U][C];
-        // octets go through octets_ld, pairs are loaded in place: each side as
-        // it was before the two folds shared this body, so that the compiler
-        // lays the row group out as it did (through octets_ld the float64
-        // kernels came out restructured, and the float16 ones without it;
-        // profiles/native_refactor/)
-        if constexpr (A::LG == 3) {
+        if constexpr (A::kOctetsLd) {
             octets_ld<U, C>(v, src, i);
         } else {
 #pragma unroll
@@ -2274,20 +2347,38 @@ __device__ __forceinline__ void fold_units(Rows src, int64_t N, const typename A
                 for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
             }
         }
+        FW af[A::kFactorsAhead ? U : 1];  // the group's factors, where they are read ahead of the barrier
+        FS sf[A::kFactorsAhead ? U : 1];
+        if constexpr (A::kFactorsAhead) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                af[u] = A::weight(a, i + u);
+                sf[u] = score_of<A, SCORED>(s, i + u);
+            }
+        }
         if constexpr (A::barrier(U, C)) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const S ai = A::factor(a, i + u), si = SCORED ? A::factor(s, i + u) : A::one();
+            FW ai;
+            FS si;
+            if constexpr (A::kFactorsAhead) {
+                ai = af[u];
+                si = sf[u];
+            } else {
+                ai = A::weight(a, i + u);
+                si = score_of<A, SCORED>(s, i + u);
+            }
 #pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = acc[c] + term<SCORED>(A::vec(v[u][c]), ai, si);
+            for (int c = 0; c < C; ++c) unit_terms<A, SCORED, false>(acc[c], v[u][c], ai, si);
         }
     }
     for (; i < N; ++i) {
         const auto* r = src.row(i);
-        const S ai = A::factor(a, i), si = SCORED ? A::factor(s, i) : A::one();
+        const FW ai = A::weight(a, i);
+        const FS si = score_of<A, SCORED>(s, i);
 #pragma unroll
         for (int c = 0; c < C; ++c)
-            acc[c] = acc[c] + term<SCORED>(A::vec(__builtin_nontemporal_load(r + c * kBlock)), ai, si);
+            unit_terms<A, SCORED, false>(acc[c], __builtin_nontemporal_load(r + c * kBlock), ai, si);
     }
     if constexpr (WT) {  // the base: the tile's first unit (out - threadIdx.x, shared by every lane)
         const __amdgpu_buffer_rsrc_t rs = wt_rsrc(reinterpret_cast<const void*>(
@@ -2295,79 +2386,87 @@ __device__ __forceinline__ void fold_units(Rows src, int64_t N, const typename A
 #pragma unroll
         for (int c = 0; c < C; ++c)
             st16_wt<WT>(rs, (int)(16 * ((int)threadIdx.x + c * kBlock)),
-                        __builtin_bit_cast(u32x4, A::div(acc[c], divisor)));
+                        __builtin_bit_cast(u32x4, A::quot(acc[c][0], divisor)));
         return;
     }
+    // A vector's final results are stored by its description (A::store).  The
+    // loop over a unit's vectors is the description's choice (kStoreLoop: the
+    // widening kinds, also those of one vector) and stands here, not in a
+    // helper: around a single-trip innermost loop the compiler emits the
+    // non-temporal store as a plain one, so each family keeps the loop shape,
+    // and with it the stores, that its kernels had.
+    constexpr int NQU = (sizeof(typename A::O) << A::LG) / sizeof(typename A::Q);  // 16-byte results per unit
 #pragma unroll
-    for (int c = 0; c < C; ++c) st_unit<A, FIN>(out + c * kBlock, acc[c], divisor);
+    for (int c = 0; c < C; ++c) {
+        typename A::Q* o = out + c * kBlock * NQU;
+        if constexpr (!FIN) {
+            *o = A::unit(acc[c][0]);
+        } else if constexpr (A::kStoreLoop) {
+#pragma unroll
+            for (int k = 0; k < NV; ++k) A::store(o + k, acc[c][k], divisor);
+        } else {
+            static_assert(NV == 1, "several vectors are stored in a loop");
+            A::store(o, acc[c][0], divisor);
+        }
+    }
 }
 
 // The trailing P % (1 << LG) columns from col on: up to 7 of an octet, the one
 // of a pair
 template <class A, class F>
 __device__ __forceinline__ void tail_columns(int64_t col, int64_t P, F f) {
-    if constexpr (A::LG == 1) {
-        f(col);
-    } else {
+    if constexpr (A::kTailLoop) {
         for (; col < P; ++col) f(col);
+    } else {
+        f(col);
     }
 }
 
-// One tile of a stacked matrix (acc_in may alias out)
-template <class A, int U, int C, bool SCORED, bool ACC, bool FIN, int WT = 0>
-__device__ __forceinline__ void native_tile(int64_t bid, const typename A::E* __restrict__ X, int64_t N, int64_t P,
-                                            int64_t ldx, const typename A::E* __restrict__ a,
-                                            const typename A::E* __restrict__ s, const typename A::E* acc_in,
-                                            typename A::D divisor, typename A::E* out) {
-    typedef typename A::Unit Unit;
-    const int64_t ldu = ldx >> A::LG;
-    const Unit* XU = reinterpret_cast<const Unit*>(X);
-    const Unit* AU = reinterpret_cast<const Unit*>(acc_in);
-    Unit* OU = reinterpret_cast<Unit*>(out);
+// The row sources of a tile over a stacked matrix and over a row table with
+// every row 16-B aligned: the lane's units from unit o on, its column c
+template <class A>
+struct PitchedSource {
+    const typename A::E* X;
+    int64_t ldx, ldu;  // the pitch in elements and in units
+    __device__ __forceinline__ PitchedSource(const typename A::E* X, int64_t ldx) : X(X), ldx(ldx), ldu(ldx >> A::LG) {}
+    __device__ __forceinline__ PitchedRows<typename A::Unit> units(int64_t o) const {
+        return {reinterpret_cast<const typename A::Unit*>(X) + o, ldu};
+    }
+    __device__ __forceinline__ PitchedRows<typename A::E> column(int64_t c) const { return {X + c, ldx}; }
+};
+template <class A>
+struct TableSource {
+    const typename A::E* const* xi;
+    __device__ __forceinline__ TableRows<typename A::GUnit, typename A::E> units(int64_t o) const { return {xi, o}; }
+    __device__ __forceinline__ TableRows<typename A::GE, typename A::E> column(int64_t c) const { return {xi, c}; }
+};
+
+// One tile (acc_in may alias out): the same body over either source, hence the
+// same bits over the same rows
+template <class A, int U, int C, bool SCORED, bool ACC = false, bool FIN = true, int WT = 0, class Src>
+__device__ __forceinline__ void unit_tile(int64_t bid, Src src, int64_t N, int64_t P,
+                                          const typename A::WE* __restrict__ a, const typename A::SE* __restrict__ s,
+                                          const typename A::E* acc_in, typename A::D divisor, typename A::O* out) {
+    constexpr int NQ = (sizeof(typename A::O) << A::LG) / sizeof(typename A::Q);  // 16-byte results per unit
+    const typename A::Unit* AU = reinterpret_cast<const typename A::Unit*>(acc_in);
+    typename A::Q* OQ = reinterpret_cast<typename A::Q*>(out);
     octet_tile<C, kBlock, A::LG>(
         bid, P,
         [&](int64_t o) {
-            fold_units<A, U, C, SCORED, ACC, FIN, WT>(PitchedRows<Unit>{XU + o, ldu}, N, a, s, ACC ? AU + o : nullptr,
-                                                      divisor, OU + o);
+            fold_units<A, U, C, SCORED, ACC, FIN, WT>(src.units(o), N, a, s, ACC ? AU + o : nullptr, divisor,
+                                                      OQ + o * NQ);
         },
         [&](int64_t o) {
-            fold_units<A, U, 1, SCORED, ACC, FIN, WT>(PitchedRows<Unit>{XU + o, ldu}, N, a, s, ACC ? AU + o : nullptr,
-                                                      divisor, OU + o);
+            fold_units<A, U, 1, SCORED, ACC, FIN, WT>(src.units(o), N, a, s, ACC ? AU + o : nullptr, divisor,
+                                                      OQ + o * NQ);
         },
         [&](int64_t col) {
             tail_columns<A>(col, P, [&](int64_t c) {
-                out[c] = fold_column<A, SCORED, ACC, FIN, A::kAhead>(PitchedRows<typename A::E>{X + c, ldx}, N, a, s,
+                out[c] = fold_column<A, SCORED, ACC, FIN, A::kAhead>(src.column(c), N, a, s,
                                                                      ACC ? acc_in + c : nullptr, divisor);
             });
             // WT: these few plain stores are written back before the block publishes
             wt_tail_release<WT>();
-        });
-}
-
-// One tile of a row table with every row 16-B aligned: the stacked tile's body
-// over the table, hence its bits over the same rows
-template <class A, int U, int C, bool SCORED>
-__device__ __forceinline__ void native_rows_tile(int64_t bid, const typename A::E* const* __restrict__ xi, int64_t N,
-                                                 int64_t P, const typename A::E* __restrict__ a,
-                                                 const typename A::E* __restrict__ s, typename A::D divisor,
-                                                 typename A::E* __restrict__ out) {
-    typedef typename A::E E;
-    typename A::Unit* OU = reinterpret_cast<typename A::Unit*>(out);
-    octet_tile<C, kBlock, A::LG>(
-        bid, P,
-        [&](int64_t o) {
-            fold_units<A, U, C, SCORED, false, true>(TableRows<typename A::GUnit, E>{xi, o}, N, a, s, nullptr, divisor,
-                                                     OU + o);
-        },
-        [&](int64_t o) {
-            fold_units<A, U, 1, SCORED, false, true>(TableRows<typename A::GUnit, E>{xi, o}, N, a, s, nullptr, divisor,
-                                                     OU + o);
-        },
-        [&](int64_t col) {
-            tail_columns<A>(col, P, [&](int64_t c) {
-                out[c] = fold_column<A, SCORED, false, true, A::kAhead>(TableRows<typename A::GE, E>{xi, c}, N, a, s,
-                                                                        nullptr, divisor);
-            });
         });
 }
 
@@ -2377,7 +2476,7 @@ template <int U, int C, bool SCORED>
 __global__ __launch_bounds__(kBlock) void k_fedavg_f16_v8(
     const uint16_t* __restrict__ X, int64_t N, int64_t P, int64_t ldx,
     const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out) {
-    native_tile<HalfArith, U, C, SCORED, false, true>(blockIdx.x, X, N, P, ldx, a, s, nullptr, divisor, out);
+    unit_tile<HalfArith, U, C, SCORED>(blockIdx.x, PitchedSource<HalfArith>{X, ldx}, N, P, a, s, nullptr, divisor, out);
 }
 
 // grid-stride over octet tiles, as k_fedavg_bf16_gs
@@ -2387,7 +2486,7 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f16_gs(
     const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out,
     int64_t ntiles) {
     for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
-        native_tile<HalfArith, U, C, SCORED, false, true>(bid, X, N, P, ldx, a, s, nullptr, divisor, out);
+        unit_tile<HalfArith, U, C, SCORED>(bid, PitchedSource<HalfArith>{X, ldx}, N, P, a, s, nullptr, divisor, out);
 }
 
 // float16, one column per lane: any alignment / pitch
@@ -2409,7 +2508,8 @@ __global__ __launch_bounds__(kBlock) void k_fold_f16_gs(
     const uint16_t* __restrict__ a, const uint16_t* __restrict__ s,
     const uint16_t* acc_in, float divisor, uint16_t* out, int64_t ntiles) {  // acc_in may alias out
     for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
-        native_tile<HalfArith, U, C, SCORED, ACC, FIN>(bid, X, N, P, ldx, a, s, acc_in, divisor, out);
+        unit_tile<HalfArith, U, C, SCORED, ACC, FIN>(bid, PitchedSource<HalfArith>{X, ldx}, N, P, a, s, acc_in, divisor,
+                                                     out);
 }
 
 // chunked fold, one column per lane: rows, accumulator or output at any 2-B
@@ -2432,7 +2532,7 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f16_rows_gs(
     const uint16_t* const* __restrict__ xi, int64_t N, int64_t P, const uint16_t* __restrict__ a,
     const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out, int64_t ntiles) {
     for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
-        native_rows_tile<HalfArith, U, C, SCORED>(bid, xi, N, P, a, s, divisor, out);
+        unit_tile<HalfArith, U, C, SCORED>(bid, TableSource<HalfArith>{xi}, N, P, a, s, nullptr, divisor, out);
 }
 
 // float16 list-of-rows form, rows at any 2-B offset: one column per lane, 8
@@ -2456,8 +2556,8 @@ __global__ __launch_bounds__(B) void k_fedavg_f16_step(
     unsigned int epoch) {
     static_assert(B == kBlock, "octet tiles are kBlock lanes wide");
     step_run<UB, CB, US, CS, BAL>(T, sig, epoch, [&](auto U, auto C, int g, int64_t bid) {
-        native_tile<HalfArith, decltype(U)::value, decltype(C)::value, SCORED, false, true, WTM>(
-            bid, X + T.col0[g], N, T.width[g], ldx, a, s, nullptr, divisor, out + T.ocol0[g]);
+        unit_tile<HalfArith, decltype(U)::value, decltype(C)::value, SCORED, false, true, WTM>(
+            bid, PitchedSource<HalfArith>{X + T.col0[g], ldx}, N, T.width[g], a, s, nullptr, divisor, out + T.ocol0[g]);
     });
 }
 
@@ -2469,7 +2569,8 @@ __global__ __launch_bounds__(kBlock) void k_fold_f64_gs(
     const double* __restrict__ a, const double* __restrict__ s,
     const double* acc_in, double divisor, double* out, int64_t ntiles) {  // acc_in may alias out
     for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
-        native_tile<DoubleArith, U, C, SCORED, ACC, FIN>(bid, X, N, P, ldx, a, s, acc_in, divisor, out);
+        unit_tile<DoubleArith, U, C, SCORED, ACC, FIN>(bid, PitchedSource<DoubleArith>{X, ldx}, N, P, a, s, acc_in,
+                                                       divisor, out);
 }
 
 // chunked fold, one column per lane: rows, accumulator or output at any 8-B
@@ -2492,7 +2593,7 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f64_rows_gs(
     const double* const* __restrict__ xi, int64_t N, int64_t P, const double* __restrict__ a,
     const double* __restrict__ s, double divisor, double* __restrict__ out, int64_t ntiles) {
     for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
-        native_rows_tile<DoubleArith, U, C, SCORED>(bid, xi, N, P, a, s, divisor, out);
+        unit_tile<DoubleArith, U, C, SCORED>(bid, TableSource<DoubleArith>{xi}, N, P, a, s, nullptr, divisor, out);
 }
 
 // float64 list-of-rows form, rows at any 8-B offset: one column per lane
@@ -2515,8 +2616,8 @@ __global__ __launch_bounds__(B) void k_fedavg_f64_step(
     unsigned int epoch) {
     static_assert(B == kBlock, "pair tiles are kBlock lanes wide");
     step_run<UB, CB, US, CS, BAL>(T, sig, epoch, [&](auto U, auto C, int g, int64_t bid) {
-        native_tile<DoubleArith, decltype(U)::value, decltype(C)::value, SCORED, false, true, WTM>(
-            bid, X + T.col0[g], N, T.width[g], ldx, a, s, nullptr, divisor, out + T.ocol0[g]);
+        unit_tile<DoubleArith, decltype(U)::value, decltype(C)::value, SCORED, false, true, WTM>(
+            bid, PitchedSource<DoubleArith>{X + T.col0[g], ldx}, N, T.width[g], a, s, nullptr, divisor, out + T.ocol0[g]);
     });
 }
 
@@ -2555,7 +2656,9 @@ __device__ __forceinline__ LayerTile layer_tile(const fa_layer_plan* __restrict_
 }
 
 // One fp32 column of a row table: 8 rows of loads ahead of the ordered adds
-// (the body of k_fold_f32_rows_scalar)
+// (the body of k_fold_f32_rows_scalar, which keeps its own text: calling this
+// function the kernel came out with another register numbering;
+// profiles/unit_fold_refactor/)
 template <bool SCORED>
 __device__ __forceinline__ float fold_column_f32(const float* const* __restrict__ xi, int64_t c, int64_t N,
                                                  const float* __restrict__ a, const float* __restrict__ s,
@@ -2633,32 +2736,34 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_bf16_layers(
     }
 }
 
-// The float16 and float64 layer-table kernels: one loop -- the layer_tile
-// search, the unaligned layer's column path, the tile call -- over the column
-// body and the row-table tile of their own kernels (an unaligned float16 layer:
-// one row at a time, as k_fedavg_f16_scalar).  The fp32 and bf16 kernels above
-// keep the loop written out: through a shared one the compiler laid their
-// preheaders and exits out differently (profiles/native_refactor/).
-template <class A, int U, int C, bool SCORED>
-__device__ __forceinline__ void native_layers(const typename A::E* const* __restrict__ xi,
-                                              const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N,
-                                              const typename A::E* __restrict__ a, const typename A::E* __restrict__ s,
-                                              typename A::D divisor, typename A::E* __restrict__ out, int64_t ntiles) {
-    typedef typename A::E E;
+// The float16, float64 and integer layer-table kernels: one loop -- the
+// layer_tile search, the unaligned layer's column path, the tile call -- over
+// the column body and the row-table tile of their own kernels (an unaligned
+// float16 layer: one row at a time, as k_fedavg_f16_scalar).  ONE: plan == NULL
+// folds the single layer `one`, passed by value (the integer _ptrs entries,
+// which so allocate and upload nothing).  The fp32 and bf16 kernels above keep the loop
+// written out: through a shared one the compiler laid their preheaders and
+// exits out differently (profiles/native_refactor/).
+template <class A, int U, int C, bool SCORED, bool ONE = false>
+__device__ __forceinline__ void unit_layers(const typename A::E* const* __restrict__ xi,
+                                            const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N,
+                                            const typename A::WE* __restrict__ a, const typename A::SE* __restrict__ s,
+                                            typename A::D divisor, typename A::O* __restrict__ out, int64_t ntiles,
+                                            fa_layer_plan one = {}) {
     int64_t l = 0;
     for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-        const LayerTile t = layer_tile(plan, L, bid, l);
+        const LayerTile t = !ONE || plan ? layer_tile(plan, L, bid, l)
+                                         : LayerTile{0, one.cols, one.offset, bid, one.aligned != 0};
         l = t.l;
-        const E* const* x = xi + l * N;
-        E* o = out + t.offset;
+        const TableSource<A> x{xi + l * N};
+        typename A::O* o = out + t.offset;
         if (!t.aligned) {
             const int64_t c = t.bid * kBlock + threadIdx.x;
             if (c < t.cols)
-                o[c] = fold_column<A, SCORED, false, true, A::kAhead>(TableRows<typename A::GE, E>{x, c}, N, a, s,
-                                                                      nullptr, divisor);
+                o[c] = fold_column<A, SCORED, false, true, A::kAhead>(x.column(c), N, a, s, nullptr, divisor);
             continue;
         }
-        native_rows_tile<A, U, C, SCORED>(t.bid, x, N, t.cols, a, s, divisor, o);
+        unit_tile<A, U, C, SCORED>(t.bid, x, N, t.cols, a, s, nullptr, divisor, o);
     }
 }
 
@@ -2667,7 +2772,7 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f16_layers(
     const uint16_t* const* __restrict__ xi, const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N,
     const uint16_t* __restrict__ a, const uint16_t* __restrict__ s, float divisor, uint16_t* __restrict__ out,
     int64_t ntiles) {
-    native_layers<HalfArith, U, C, SCORED>(xi, plan, L, N, a, s, divisor, out, ntiles);
+    unit_layers<HalfArith, U, C, SCORED>(xi, plan, L, N, a, s, divisor, out, ntiles);
 }
 
 template <int U, int C, bool SCORED>
@@ -2675,7 +2780,7 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_f64_layers(
     const double* const* __restrict__ xi, const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N,
     const double* __restrict__ a, const double* __restrict__ s, double divisor, double* __restrict__ out,
     int64_t ntiles) {
-    native_layers<DoubleArith, U, C, SCORED>(xi, plan, L, N, a, s, divisor, out, ntiles);
+    unit_layers<DoubleArith, U, C, SCORED>(xi, plan, L, N, a, s, divisor, out, ntiles);
 }
 
 // numpy integer semantics: product and fold in the input dtype with
@@ -2705,14 +2810,11 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_int(
 //   scored    t_i = (double)p_i * s_i -- the conversion rounds to nearest even
 //             beyond 2^53, as numpy's cast -- acc = t_0, acc = acc + t_i in
 //             strict client order, multiply and add apart; out = acc / divisor
-// The quotient is the float64 folds' divide (div_d1).  The kernel has the
-// float64 layer-table kernel's shape: grid-stride over the tiles of all
-// layers, the layer_tile search, 16-byte units (4 int32 or 2 int64 columns) C
-// per lane with 8 rows of loads ahead of the ordered adds, the quotients stored
-// non-temporally as 16-byte pairs of doubles (an int32 unit: two stores), an
-// aligned layer's tail columns and an unaligned layer's columns one per lane,
-// 8 rows ahead.  plan == NULL folds the one layer `one`, passed by value: the
-// _ptrs entries, which so allocate and upload nothing.
+// The quotient is the float64 folds' divide (div_d1).  The kernel is the
+// float64 layer-table kernel over IntAcc: 16-byte units of 4 int32 or 2 int64
+// columns, the quotients 16-byte pairs of doubles (an int32 unit: two stores),
+// tail columns and unaligned layers one column per lane, 8 rows ahead.
+// plan == NULL folds the one layer `one`, passed by value (the _ptrs entries).
 // ---------------------------------------------------------------------------
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
@@ -2740,29 +2842,45 @@ struct Int64Rows {
     static constexpr int LG = 1;
 };
 
-// the cardinality as numpy converts it to the rows' dtype (the host has checked that it fits)
-template <class I>
-__device__ __forceinline__ typename I::UT int_factor(const int64_t* __restrict__ a, int64_t i) {
-    return (typename I::UT)(typename I::T)(*(ci64*)(a + i));
-}
-__device__ __forceinline__ double int_score(const double* __restrict__ s, int64_t i) { return *(cf64*)(s + i); }
-
-// one unit's accumulator: the wrapping sum, or the float64 sum of the scored terms
+// The arithmetic of the integer folds over the rows I: the accumulator is the
+// wrapping sum, or the float64 sum of the scored terms
 template <class I, bool SCORED>
 struct IntAcc {
+    typedef typename I::T E;
+    typedef typename I::UT UT;
+    typedef typename I::UV Unit, X;  // the wrapping product is formed on the unit as loaded
+    typedef typename I::GUnit GUnit;
+    typedef typename I::GE GE;
+    typedef int64_t WE;
+    typedef double SE, O, D;
+    typedef f64x2 Q;
     typedef typename std::conditional<SCORED, typename I::DV, typename I::UV>::type V;
-    typedef typename std::conditional<SCORED, double, typename I::UT>::type S;
+    typedef typename std::conditional<SCORED, double, UT>::type S;
+    static constexpr int LG = I::LG, NV = 1;
+    static constexpr bool kAhead = true, kFactorsAhead = false, kOctetsLd = false, kTailLoop = true, kStoreLoop = false;
+    static constexpr bool barrier(int, int) { return false; }
+    // the cardinality as numpy converts it to the rows' dtype (the host has checked that it fits)
+    static __device__ __forceinline__ UT weight(const WE* __restrict__ a, int64_t i) { return (UT)(E)(*(ci64*)(a + i)); }
+    static __device__ __forceinline__ double score(const SE* __restrict__ s, int64_t i) { return *(cf64*)(s + i); }
+    static __device__ __forceinline__ double one() { return 1.0; }
+    static __device__ __forceinline__ void widen(Unit u, X (&w)[NV]) { w[0] = u; }
+    static __device__ __forceinline__ UT widen(E e) { return (UT)e; }
+    // the conversion rounds to nearest even beyond 2^53, as numpy's cast
     static __device__ __forceinline__ typename I::DV dbl(typename I::UV p) {
         return __builtin_convertvector(__builtin_bit_cast(typename I::SV, p), typename I::DV);
     }
-    static __device__ __forceinline__ V term(typename I::UV x, typename I::UT a, double s) {
+    template <bool SC>
+    static __device__ __forceinline__ V term(typename I::UV x, UT a, double s) {
+        static_assert(SC == SCORED, "the fold's switch is the accumulator's");
         const typename I::UV p = x * a;
         if constexpr (SCORED) return dbl(p) * s;
         else return p;
     }
-    static __device__ __forceinline__ S term(typename I::UT x, typename I::UT a, double s) {
-        const typename I::UT p = (typename I::UT)(x * a);
-        if constexpr (SCORED) return (double)(typename I::T)p * s;
+    template <bool SC>
+    static __device__ __forceinline__ S term(UT x, UT a, double s) {
+        static_assert(SC == SCORED, "the fold's switch is the accumulator's");
+        const UT p = (UT)(x * a);
+        if constexpr (SCORED) return (double)(E)p * s;
         else return p;
     }
     static __device__ __forceinline__ typename I::DV fin(V acc) {
@@ -2771,113 +2889,26 @@ struct IntAcc {
     }
     static __device__ __forceinline__ double fin(S acc) {
         if constexpr (SCORED) return acc;
-        else return (double)(typename I::T)acc;
+        else return (double)(E)acc;
     }
+    // a unit's quotients: one 16-byte pair of doubles (int64), two (int32)
+    static __device__ __forceinline__ void st_quotients(Q* o, f64x2 acc, D d) {
+        __builtin_nontemporal_store(div_d2(acc, d), o);
+    }
+    static __device__ __forceinline__ void st_quotients(Q* o, f64x4 acc, D d) {
+        __builtin_nontemporal_store(div_d2(f64x2{acc.x, acc.y}, d), o);
+        __builtin_nontemporal_store(div_d2(f64x2{acc.z, acc.w}, d), o + 1);
+    }
+    static __device__ __forceinline__ void store(Q* o, V acc, D d) { st_quotients(o, fin(acc), d); }
+    static __device__ __forceinline__ O quot(S acc, D d) { return div_d1(fin(acc), d); }
 };
-
-__device__ __forceinline__ void st_quotients(double* out, f64x2 acc, double divisor) {
-    __builtin_nontemporal_store(div_d2(acc, divisor), reinterpret_cast<f64x2*>(out));
-}
-__device__ __forceinline__ void st_quotients(double* out, f64x4 acc, double divisor) {
-    __builtin_nontemporal_store(div_d2(f64x2{acc.x, acc.y}, divisor), reinterpret_cast<f64x2*>(out));
-    __builtin_nontemporal_store(div_d2(f64x2{acc.z, acc.w}, divisor), reinterpret_cast<f64x2*>(out) + 1);
-}
-
-// The lane's C units of the rows of src, in row order; out: the lane's first unit's columns
-template <class I, int U, int C, bool SCORED>
-__device__ __forceinline__ void fold_int_units(TableRows<typename I::GUnit, typename I::T> src, int64_t N,
-                                               const int64_t* __restrict__ a, const double* __restrict__ s,
-                                               double divisor, double* out) {
-    typedef IntAcc<I, SCORED> A;
-    typename A::V acc[C];
-    {
-        const auto* r = src.row(0);
-        const typename I::UT a0 = int_factor<I>(a, 0);
-        const double s0 = SCORED ? int_score(s, 0) : 1.0;
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = A::term(__builtin_nontemporal_load(r + c * kBlock), a0, s0);
-    }
-    int64_t i = 1;
-    for (; i + U <= N; i += U) {
-        typename I::UV v[U][C];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const auto* r = src.row(i + u);
-#pragma unroll
-            for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const typename I::UT ai = int_factor<I>(a, i + u);
-            const double si = SCORED ? int_score(s, i + u) : 1.0;
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = acc[c] + A::term(v[u][c], ai, si);
-        }
-    }
-    for (; i < N; ++i) {
-        const auto* r = src.row(i);
-        const typename I::UT ai = int_factor<I>(a, i);
-        const double si = SCORED ? int_score(s, i) : 1.0;
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = acc[c] + A::term(__builtin_nontemporal_load(r + c * kBlock), ai, si);
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) st_quotients(out + ((int64_t)c * kBlock << I::LG), A::fin(acc[c]), divisor);
-}
-
-// One column: 8 rows of loads ahead of the ordered adds
-template <class I, bool SCORED>
-__device__ __forceinline__ double fold_int_column(TableRows<typename I::GE, typename I::T> src, int64_t N,
-                                                  const int64_t* __restrict__ a, const double* __restrict__ s,
-                                                  double divisor) {
-    typedef IntAcc<I, SCORED> A;
-    typedef typename I::UT UT;
-    typename A::S acc = A::term((UT)*src.row(0), int_factor<I>(a, 0), SCORED ? int_score(s, 0) : 1.0);
-    int64_t i = 1;
-    for (; i + 8 <= N; i += 8) {
-        UT v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = (UT)__builtin_nontemporal_load(src.row(i + u));
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            acc = acc + A::term(v[u], int_factor<I>(a, i + u), SCORED ? int_score(s, i + u) : 1.0);
-    }
-    for (; i < N; ++i) acc = acc + A::term((UT)*src.row(i), int_factor<I>(a, i), SCORED ? int_score(s, i) : 1.0);
-    return div_d1(A::fin(acc), divisor);
-}
 
 template <class I, int U, int C, bool SCORED>
 __global__ __launch_bounds__(kBlock) void k_fedavg_int_layers(
     const typename I::T* const* __restrict__ xi, const fa_layer_plan* __restrict__ plan, fa_layer_plan one, int64_t L,
     int64_t N, const int64_t* __restrict__ a, const double* __restrict__ s, double divisor, double* __restrict__ out,
     int64_t ntiles) {
-    typedef typename I::T T;
-    int64_t l = 0;
-    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-        const LayerTile t = plan ? layer_tile(plan, L, bid, l) : LayerTile{0, one.cols, one.offset, bid, one.aligned != 0};
-        l = t.l;
-        const T* const* x = xi + l * N;
-        double* o = out + t.offset;
-        if (!t.aligned) {
-            const int64_t c = t.bid * kBlock + threadIdx.x;
-            if (c < t.cols) o[c] = fold_int_column<I, SCORED>(TableRows<typename I::GE, T>{x, c}, N, a, s, divisor);
-            continue;
-        }
-        octet_tile<C, kBlock, I::LG>(
-            t.bid, t.cols,
-            [&](int64_t q) {
-                fold_int_units<I, U, C, SCORED>(TableRows<typename I::GUnit, T>{x, q}, N, a, s, divisor,
-                                                o + (q << I::LG));
-            },
-            [&](int64_t q) {
-                fold_int_units<I, U, 1, SCORED>(TableRows<typename I::GUnit, T>{x, q}, N, a, s, divisor,
-                                                o + (q << I::LG));
-            },
-            [&](int64_t col) {
-                for (; col < t.cols; ++col)
-                    o[col] = fold_int_column<I, SCORED>(TableRows<typename I::GE, T>{x, col}, N, a, s, divisor);
-            });
-    }
+    unit_layers<IntAcc<I, SCORED>, U, C, SCORED, true>(xi, plan, L, N, a, s, divisor, out, ntiles, one);
 }
 
 // ---------------------------------------------------------------------------
@@ -2897,41 +2928,41 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_int_layers(
 //            k_fedavg_int computed unsigned, (double)acc, then div_d1
 // so the bits are those of widening the matrix first and folding the copy.
 // Every widening is exact but int64 -> float64, which rounds to nearest even as
-// numpy's cast does (IntAcc::dbl).  acc = t_0, strict row order, multiply and
-// add apart, as everywhere.
+// numpy's cast does (IntAcc::dbl).
 //
-// The shape is that of fold_units / fold_int_units: C units per lane spaced
-// kBlock lanes apart, U rows x C units of non-temporal loads issued ahead of the
-// ordered adds, the factors scalar loads from constant address space, the
-// quotients stored non-temporally 16 bytes at a time (a half unit into float64
-// is four stores), octet_tile for the full tile, the one-unit tile and the tail
-// columns.  Where row i starts is a row source (PitchedRows here), so that a
-// row-table form is the same body over TableRows.  Rows off the unit (base or
-// pitch) or an output off 16 bytes take one lane per column, 8 rows ahead.
-// The geometry is fixed per kind (W::C units per lane, W::U rows ahead;
-// DESIGN.md 5): one block per tile.
+// Every group's loads and factors are issued before the first conversion
+// (barrier, kFactorsAhead): left to itself the scheduler threads the loads
+// through the conversions and adds to save registers, and two or three of the
+// sixteen are in flight.  Rows off the unit (base or pitch) or an output off 16
+// bytes take one lane per column, 8 rows ahead.  The geometry is fixed per kind
+// (W::C units per lane, W::U rows ahead): one block per tile.
 // ---------------------------------------------------------------------------
 typedef __attribute__((address_space(4))) const float cf32;
 typedef double f64x8 __attribute__((ext_vector_type(8)));
 typedef int64_t i64x4 __attribute__((ext_vector_type(4)));
 
+// What the six kinds share: 16 bytes of any source dtype as loaded, the schedule
+struct WidenUnit {
+    typedef u32x4 Unit;
+    static constexpr bool kAhead = true, kFactorsAhead = true, kOctetsLd = false, kTailLoop = true, kStoreLoop = true;
+    static constexpr bool barrier(int, int) { return true; }
+};
 // The float64 side of the four kinds that fold in float64
-struct WidenF64 {
-    typedef double FE;  // a factor as stored
-    typedef double F;   // ... and as an operand
-    typedef double O;   // an output element
-    typedef double D;   // the divisor
-    typedef f64x2 V;    // 16 bytes of accumulators
-    typedef f64x2 Q;    // ... and of quotients
-    typedef double S;   // one column's accumulator
-    static __device__ __forceinline__ F factor(const FE* __restrict__ a, int64_t i) { return DoubleArith::factor(a, i); }
-    static __device__ __forceinline__ F one() { return 1.0; }
-    template <bool SCORED, class X>
-    static __device__ __forceinline__ X wterm(X x, F a, F s) { return term<SCORED>(x, a, s); }
-    template <class X>
-    static __device__ __forceinline__ X add(X x, X y) { return x + y; }
-    template <class X>
-    static __device__ __forceinline__ X quot(X acc, D d) { return DoubleArith::div(acc, d); }
+struct WidenF64 : WidenUnit {
+    typedef double FE, WE, SE;  // a factor as stored: a weight, a score
+    typedef double O;       // an output element
+    typedef double D;       // the divisor
+    typedef f64x2 V, X;     // 16 bytes of accumulators, of widened elements
+    typedef f64x2 Q;        // ... and of quotients
+    typedef double S;       // one column's accumulator
+    static __device__ __forceinline__ S weight(const WE* __restrict__ a, int64_t i) { return DoubleArith::weight(a, i); }
+    static __device__ __forceinline__ S score(const SE* __restrict__ s, int64_t i) { return DoubleArith::weight(s, i); }
+    static __device__ __forceinline__ S one() { return 1.0; }
+    template <bool SCORED, class T>
+    static __device__ __forceinline__ T term(T x, S a, S s) { return term_fl<SCORED>(x, a, s); }
+    static __device__ __forceinline__ Q quot(V acc, D d) { return div_d2(acc, d); }
+    static __device__ __forceinline__ O quot(S acc, D d) { return div_d1(acc, d); }
+    static __device__ __forceinline__ void store(Q* o, V acc, D d) { __builtin_nontemporal_store(quot(acc, d), o); }
 };
 struct WidenF16F64 : WidenF64 {
     typedef uint16_t E;
@@ -2974,18 +3005,14 @@ struct WidenI64F64 : WidenF64 {
     }
     static __device__ __forceinline__ S widen(E e) { return (double)e; }
 };
-struct WidenF16F32 {
+struct WidenF16F32 : WidenUnit {
     typedef uint16_t E;
-    typedef float FE;
-    typedef float F;
-    typedef float O;
-    typedef float D;
-    typedef f32x4 V;
-    typedef f32x4 Q;
-    typedef float S;
+    typedef float FE, WE, SE, O, D, S;
+    typedef f32x4 V, X, Q;
     static constexpr int LG = 3, NV = 2, C = 2, U = 8;
-    static __device__ __forceinline__ F factor(const FE* __restrict__ a, int64_t i) { return *(cf32*)(a + i); }
-    static __device__ __forceinline__ F one() { return 1.0f; }
+    static __device__ __forceinline__ S weight(const WE* __restrict__ a, int64_t i) { return *(cf32*)(a + i); }
+    static __device__ __forceinline__ S score(const SE* __restrict__ s, int64_t i) { return weight(s, i); }
+    static __device__ __forceinline__ S one() { return 1.0f; }
     static __device__ __forceinline__ void widen(u32x4 u, V (&w)[NV]) {
         const f32x8 d = __builtin_convertvector(__builtin_bit_cast(f16x8, u), f32x8);
         w[0] = __builtin_shufflevector(d, d, 0, 1, 2, 3);
@@ -2993,159 +3020,44 @@ struct WidenF16F32 {
     }
     static __device__ __forceinline__ S widen(E e) { return (float)__builtin_bit_cast(_Float16, e); }
     template <bool SCORED>
-    static __device__ __forceinline__ V wterm(V x, F a, F s) { return term4<SCORED>(x, a, s); }
+    static __device__ __forceinline__ V term(V x, S a, S s) { return term4<SCORED>(x, a, s); }
     template <bool SCORED>
-    static __device__ __forceinline__ S wterm(S x, F a, F s) { return term1<SCORED>(x, a, s); }
-    static __device__ __forceinline__ V add(V x, V y) { return add4(x, y); }
-    static __device__ __forceinline__ S add(S x, S y) { return x + y; }
+    static __device__ __forceinline__ S term(S x, S a, S s) { return term1<SCORED>(x, a, s); }
     static __device__ __forceinline__ Q quot(V acc, D d) { return div4(acc, d); }
-    static __device__ __forceinline__ S quot(S acc, D d) { return acc / d; }
+    static __device__ __forceinline__ void store(Q* o, V acc, D d) { __builtin_nontemporal_store(quot(acc, d), o); }
+    static __device__ __forceinline__ O quot(S acc, D d) { return acc / d; }
 };
-struct WidenI32I64 {  // unscored only: a score makes the fold float64 (WidenI32F64)
+struct WidenI32I64 : WidenUnit {  // unscored only: a score makes the fold float64 (WidenI32F64)
     typedef IntAcc<Int64Rows, false> A;
     typedef int32_t E;
-    typedef int64_t FE;
-    typedef uint64_t F;
-    typedef double O;
-    typedef double D;
-    typedef u64x2 V;
+    typedef int64_t FE, WE, SE;
+    typedef double O, D;
+    typedef u64x2 V, X;
     typedef f64x2 Q;
     typedef uint64_t S;
     static constexpr int LG = 2, NV = 2, C = 2, U = 8;
-    static __device__ __forceinline__ F factor(const FE* __restrict__ a, int64_t i) { return int_factor<Int64Rows>(a, i); }
-    static __device__ __forceinline__ F one() { return 1; }
+    static __device__ __forceinline__ S weight(const WE* __restrict__ a, int64_t i) { return A::weight(a, i); }
+    static __device__ __forceinline__ S score(const SE* __restrict__ s, int64_t i) { return A::weight(s, i); }
+    static __device__ __forceinline__ S one() { return 1; }
     static __device__ __forceinline__ void widen(u32x4 u, V (&w)[NV]) {  // sign-extended
         const i64x4 d = __builtin_convertvector(__builtin_bit_cast(i32x4, u), i64x4);
         w[0] = __builtin_bit_cast(u64x2, (i64x2)__builtin_shufflevector(d, d, 0, 1));
         w[1] = __builtin_bit_cast(u64x2, (i64x2)__builtin_shufflevector(d, d, 2, 3));
     }
     static __device__ __forceinline__ S widen(E e) { return (uint64_t)(int64_t)e; }
-    template <bool SCORED, class X>
-    static __device__ __forceinline__ X wterm(X x, F a, F) { return A::term(x, a, 1.0); }
-    template <class X>
-    static __device__ __forceinline__ X add(X x, X y) { return x + y; }
-    static __device__ __forceinline__ Q quot(V acc, D d) { return DoubleArith::div(A::fin(acc), d); }
-    static __device__ __forceinline__ double quot(S acc, D d) { return DoubleArith::div(A::fin(acc), d); }
+    template <bool SCORED, class T>
+    static __device__ __forceinline__ T term(T x, S a, S) { return A::template term<false>(x, a, 1.0); }
+    static __device__ __forceinline__ Q quot(V acc, D d) { return div_d2(A::fin(acc), d); }
+    static __device__ __forceinline__ void store(Q* o, V acc, D d) { __builtin_nontemporal_store(quot(acc, d), o); }
+    static __device__ __forceinline__ O quot(S acc, D d) { return A::quot(acc, d); }
 };
-
-// The lane's C source units of the rows of src, in row order; out: the lane's
-// first unit's columns
-template <class W, int U, int C, bool SCORED, class Rows>
-__device__ __forceinline__ void widen_units(Rows src, int64_t N, const typename W::FE* __restrict__ a,
-                                            const typename W::FE* __restrict__ s, typename W::D divisor,
-                                            typename W::O* out) {
-    typedef typename W::V V;
-    typedef typename W::F F;
-    constexpr int NV = W::NV;
-    V acc[C][NV];
-    {
-        const auto* r = src.row(0);
-        const F a0 = W::factor(a, 0), s0 = SCORED ? W::factor(s, 0) : W::one();
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            V w[NV];
-            W::widen(__builtin_nontemporal_load(r + c * kBlock), w);
-#pragma unroll
-            for (int k = 0; k < NV; ++k) acc[c][k] = W::template wterm<SCORED>(w[k], a0, s0);
-        }
-    }
-    int64_t i = 1;
-    for (; i + U <= N; i += U) {
-        u32x4 v[U][C];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const auto* r = src.row(i + u);
-#pragma unroll
-            for (int c = 0; c < C; ++c) v[u][c] = __builtin_nontemporal_load(r + c * kBlock);
-        }
-        // Every load of the group, and the group's factors, issued before the
-        // first conversion: left to itself the scheduler threads the loads
-        // through the conversions and adds to save registers, and two or three
-        // of the sixteen are in flight.  The factors stand ahead of the barrier
-        // so that their scalar loads are one group behind one wait.
-        F af[U], sf[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            af[u] = W::factor(a, i + u);
-            sf[u] = SCORED ? W::factor(s, i + u) : W::one();
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                V w[NV];
-                W::widen(v[u][c], w);
-#pragma unroll
-                for (int k = 0; k < NV; ++k)
-                    acc[c][k] = W::add(acc[c][k], W::template wterm<SCORED>(w[k], af[u], sf[u]));
-            }
-        }
-    }
-    for (; i < N; ++i) {
-        const auto* r = src.row(i);
-        const F ai = W::factor(a, i), si = SCORED ? W::factor(s, i) : W::one();
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            V w[NV];
-            W::widen(__builtin_nontemporal_load(r + c * kBlock), w);
-#pragma unroll
-            for (int k = 0; k < NV; ++k) acc[c][k] = W::add(acc[c][k], W::template wterm<SCORED>(w[k], ai, si));
-        }
-    }
-    typedef typename W::Q Q;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        Q* o = reinterpret_cast<Q*>(out + ((int64_t)c * kBlock << W::LG));
-#pragma unroll
-        for (int k = 0; k < NV; ++k) __builtin_nontemporal_store(W::quot(acc[c][k], divisor), o + k);
-    }
-}
-
-// One column: 8 rows of loads ahead of the ordered adds
-template <class W, bool SCORED, class Rows>
-__device__ __forceinline__ typename W::O widen_column(Rows src, int64_t N, const typename W::FE* __restrict__ a,
-                                                      const typename W::FE* __restrict__ s, typename W::D divisor) {
-    typedef typename W::F F;
-    typename W::S acc = W::template wterm<SCORED>(W::widen(*src.row(0)), W::factor(a, 0),
-                                                  SCORED ? W::factor(s, 0) : W::one());
-    int64_t i = 1;
-    for (; i + 8 <= N; i += 8) {
-        typename W::E v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load(src.row(i + u));
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const F ai = W::factor(a, i + u), si = SCORED ? W::factor(s, i + u) : W::one();
-            acc = W::add(acc, W::template wterm<SCORED>(W::widen(v[u]), ai, si));
-        }
-    }
-    for (; i < N; ++i)
-        acc = W::add(acc, W::template wterm<SCORED>(W::widen(*src.row(i)), W::factor(a, i),
-                                                    SCORED ? W::factor(s, i) : W::one()));
-    return W::quot(acc, divisor);
-}
 
 // one block per tile of W::C units per lane: rows and out 16-B aligned, the pitch a multiple of the unit
 template <class W, bool SCORED>
 __global__ __launch_bounds__(kBlock) void k_fedavg_widen(
     const typename W::E* __restrict__ X, int64_t N, int64_t P, int64_t ldx, const typename W::FE* __restrict__ a,
     const typename W::FE* __restrict__ s, typename W::D divisor, typename W::O* __restrict__ out) {
-    typedef typename W::E E;
-    const u32x4* XU = reinterpret_cast<const u32x4*>(X);
-    const int64_t ldu = ldx >> W::LG;
-    octet_tile<W::C, kBlock, W::LG>(
-        blockIdx.x, P,
-        [&](int64_t o) {
-            widen_units<W, W::U, W::C, SCORED>(PitchedRows<u32x4>{XU + o, ldu}, N, a, s, divisor,
-                                                  out + (o << W::LG));
-        },
-        [&](int64_t o) {
-            widen_units<W, W::U, 1, SCORED>(PitchedRows<u32x4>{XU + o, ldu}, N, a, s, divisor, out + (o << W::LG));
-        },
-        [&](int64_t col) {
-            for (; col < P; ++col) out[col] = widen_column<W, SCORED>(PitchedRows<E>{X + col, ldx}, N, a, s, divisor);
-        });
+    unit_tile<W, W::U, W::C, SCORED>(blockIdx.x, PitchedSource<W>{X, ldx}, N, P, a, s, nullptr, divisor, out);
 }
 
 // one column per lane: any element-aligned base, pitch and output
@@ -3155,7 +3067,7 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_widen_scalar(
     const typename W::FE* __restrict__ s, typename W::D divisor, typename W::O* __restrict__ out) {
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= P) return;
-    out[c] = widen_column<W, SCORED>(PitchedRows<typename W::E>{X + c, ldx}, N, a, s, divisor);
+    out[c] = fold_column<W, SCORED, false, true, true>(PitchedRows<typename W::E>{X + c, ldx}, N, a, s, nullptr, divisor);
 }
 
 // ---------------------------------------------------------------------------
@@ -4604,6 +4516,21 @@ void launch_f16_rows_gs(hipStream_t st, const uint16_t* const* xi, int64_t N, in
                    N, P, a, s, d, out);
 }
 
+// What the row-table folds share: the common checks, nothing to fold, the
+// vector forms' alignment refusal (refusal: its text, or NULL), the stream's
+// device, launch(st) (non-zero: its failure), the launch check.
+template <class Launch>
+int rows_fold(const char* what, const void* xi, int64_t N, int64_t P, const void* a, const void* out, void* stream,
+              const char* refusal, Launch launch) {
+    int rc = check_common(N, P, P, xi, a, out);
+    if (rc) return rc;
+    if (P == 0) { g_err[0] = 0; return FA_OK; }
+    if (refusal) return fail(FA_ERR_ARG, "%s", refusal);
+    StreamDevice on_stream_device(stream);
+    rc = launch((hipStream_t)stream);
+    return rc ? rc : check_launch(what);
+}
+
 // form < 0: the policy (rows_aligned picks the octet tiling or the column
 // kernel); form >= 0: that form (the bench library; the octet forms need
 // rows_aligned != 0)
@@ -4611,58 +4538,52 @@ inline int bf16_rows_fold(const uint16_t* const* xi, int64_t N, int64_t P, const
                           float divisor, int rows_aligned, float* out_f32, uint16_t* out_bf16, void* stream,
                           int form = -1) {
     if (form >= kNumRows16Forms) return fail(FA_ERR_ARG, "unknown 16-bit row-table form %d", form);
-    int rc = check_common(N, P, P, xi, a, bf16_any_out(out_f32, out_bf16));
-    if (rc) return rc;
-    if (P == 0) { g_err[0] = 0; return FA_OK; }
-    if (form < 0) form = (int)(rows_aligned ? pick_rows16(N, P) : Rows16Form::kColumn);
-    if (form != (int)Rows16Form::kColumn && !(rows_aligned && aligned16(out_f32) && aligned16(out_bf16)))
-        return fail(FA_ERR_ARG, "the octet forms of the bf16 row-table fold need 16-B aligned rows and outputs");
-    hipStream_t st = (hipStream_t)stream;
-    StreamDevice on_stream_device(stream);
-    switch ((Rows16Form)form) {
-        case Rows16Form::kGsU2C8: launch_bf16_rows_gs<2, 8>(st, xi, N, P, a, s, divisor, out_f32, out_bf16); break;
-        case Rows16Form::kGsU8C4: launch_bf16_rows_gs<8, 4>(st, xi, N, P, a, s, divisor, out_f32, out_bf16); break;
-        case Rows16Form::kGsU8C2: launch_bf16_rows_gs<8, 2>(st, xi, N, P, a, s, divisor, out_f32, out_bf16); break;
-        case Rows16Form::kGsU8C1: launch_bf16_rows_gs<8, 1>(st, xi, N, P, a, s, divisor, out_f32, out_bf16); break;
-        case Rows16Form::kColumn:
-            if (s)
-                hipLaunchKernelGGL(k_fedavg_bf16_rows_scalar<true>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a, s,
-                                   divisor, out_f32, out_bf16);
-            else
-                hipLaunchKernelGGL(k_fedavg_bf16_rows_scalar<false>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a, s,
-                                   divisor, out_f32, out_bf16);
-            break;
-    }
-    return check_launch("fa_fedavg_bf16_ptrs");
+    if (form < 0) form = (int)(rows_aligned && N > 0 && P > 0 ? pick_rows16(N, P) : Rows16Form::kColumn);
+    const bool fits = form == (int)Rows16Form::kColumn || (rows_aligned && aligned16(out_f32) && aligned16(out_bf16));
+    return rows_fold(
+        "fa_fedavg_bf16_ptrs", xi, N, P, a, bf16_any_out(out_f32, out_bf16), stream,
+        fits ? nullptr : "the octet forms of the bf16 row-table fold need 16-B aligned rows and outputs",
+        [&](hipStream_t st) {
+            switch ((Rows16Form)form) {
+                case Rows16Form::kGsU2C8: launch_bf16_rows_gs<2, 8>(st, xi, N, P, a, s, divisor, out_f32, out_bf16); break;
+                case Rows16Form::kGsU8C4: launch_bf16_rows_gs<8, 4>(st, xi, N, P, a, s, divisor, out_f32, out_bf16); break;
+                case Rows16Form::kGsU8C2: launch_bf16_rows_gs<8, 2>(st, xi, N, P, a, s, divisor, out_f32, out_bf16); break;
+                case Rows16Form::kGsU8C1: launch_bf16_rows_gs<8, 1>(st, xi, N, P, a, s, divisor, out_f32, out_bf16); break;
+                case Rows16Form::kColumn:
+                    with_scored(s != nullptr, [&](auto SC) {
+                        hipLaunchKernelGGL(k_fedavg_bf16_rows_scalar<SC.value>, grid_for(P), dim3(kBlock), 0, st, xi, N,
+                                           P, a, s, divisor, out_f32, out_bf16);
+                    });
+                    break;
+            }
+            return 0;
+        });
 }
 
 inline int f16_rows_fold(const uint16_t* const* xi, int64_t N, int64_t P, const uint16_t* a, const uint16_t* s,
                          uint16_t divisor, int rows_aligned, uint16_t* out, void* stream, int form = -1) {
     if (form >= kNumRows16Forms) return fail(FA_ERR_ARG, "unknown 16-bit row-table form %d", form);
-    int rc = check_common(N, P, P, xi, a, out);
-    if (rc) return rc;
-    if (P == 0) { g_err[0] = 0; return FA_OK; }
-    if (form < 0) form = (int)(rows_aligned ? pick_rows16(N, P) : Rows16Form::kColumn);
-    if (form != (int)Rows16Form::kColumn && !(rows_aligned && aligned16(out)))
-        return fail(FA_ERR_ARG, "the octet forms of the float16 row-table fold need 16-B aligned rows and out");
-    hipStream_t st = (hipStream_t)stream;
-    StreamDevice on_stream_device(stream);
     const float d = half_bits_to_float(divisor);
-    switch ((Rows16Form)form) {
-        case Rows16Form::kGsU2C8: launch_f16_rows_gs<2, 8>(st, xi, N, P, a, s, d, out); break;
-        case Rows16Form::kGsU8C4: launch_f16_rows_gs<8, 4>(st, xi, N, P, a, s, d, out); break;
-        case Rows16Form::kGsU8C2: launch_f16_rows_gs<8, 2>(st, xi, N, P, a, s, d, out); break;
-        case Rows16Form::kGsU8C1: launch_f16_rows_gs<8, 1>(st, xi, N, P, a, s, d, out); break;
-        case Rows16Form::kColumn:
-            if (s)
-                hipLaunchKernelGGL(k_fedavg_f16_rows_scalar<true>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a, s, d,
-                                   out);
-            else
-                hipLaunchKernelGGL(k_fedavg_f16_rows_scalar<false>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a, s, d,
-                                   out);
-            break;
-    }
-    return check_launch("fa_fedavg_f16_ptrs");
+    if (form < 0) form = (int)(rows_aligned && N > 0 && P > 0 ? pick_rows16(N, P) : Rows16Form::kColumn);
+    const bool fits = form == (int)Rows16Form::kColumn || (rows_aligned && aligned16(out));
+    return rows_fold(
+        "fa_fedavg_f16_ptrs", xi, N, P, a, out, stream,
+        fits ? nullptr : "the octet forms of the float16 row-table fold need 16-B aligned rows and out",
+        [&](hipStream_t st) {
+            switch ((Rows16Form)form) {
+                case Rows16Form::kGsU2C8: launch_f16_rows_gs<2, 8>(st, xi, N, P, a, s, d, out); break;
+                case Rows16Form::kGsU8C4: launch_f16_rows_gs<8, 4>(st, xi, N, P, a, s, d, out); break;
+                case Rows16Form::kGsU8C2: launch_f16_rows_gs<8, 2>(st, xi, N, P, a, s, d, out); break;
+                case Rows16Form::kGsU8C1: launch_f16_rows_gs<8, 1>(st, xi, N, P, a, s, d, out); break;
+                case Rows16Form::kColumn:
+                    with_scored(s != nullptr, [&](auto SC) {
+                        hipLaunchKernelGGL(k_fedavg_f16_rows_scalar<SC.value>, grid_for(P), dim3(kBlock), 0, st, xi, N,
+                                           P, a, s, d, out);
+                    });
+                    break;
+            }
+            return 0;
+        });
 }
 
 // ---- the float64 pair folds (fa_fold_f64, fa_fedavg_f64_ptrs) -----------------
@@ -4697,11 +4618,7 @@ inline int f64_fold(const double* X, int64_t N, int64_t P, int64_t ldx, const do
                                    dim3((unsigned)g.grid), dim3(kBlock), 0, st, X, N, P, ldx, a, s, acc_in, divisor, out,
                                    g.tiles);
             };
-            switch (pick_pairs(P, cu_count())) {
-                case 4: gs(int_c<4>{}); break;
-                case 2: gs(int_c<2>{}); break;
-                default: gs(int_c<1>{}); break;
-            }
+            with_units(pick_pairs(P, cu_count()), gs);
         });
 }
 
@@ -4714,28 +4631,22 @@ void launch_f64_rows_gs(hipStream_t st, const double* const* xi, int64_t N, int6
 
 inline int f64_rows_fold(const double* const* xi, int64_t N, int64_t P, const double* a, const double* s,
                          double divisor, int rows_aligned, double* out, void* stream) {
-    int rc = check_common(N, P, P, xi, a, out);
-    if (rc) return rc;
-    if (P == 0) { g_err[0] = 0; return FA_OK; }
-    if (rows_aligned && !aligned16(out))
-        return fail(FA_ERR_ARG, "the pair form of the float64 row-table fold needs 16-B aligned rows and out");
-    hipStream_t st = (hipStream_t)stream;
-    StreamDevice on_stream_device(stream);
-    if (!rows_aligned) {
-        if (s)
-            hipLaunchKernelGGL(k_fedavg_f64_rows_scalar<true>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a, s, divisor,
-                               out);
-        else
-            hipLaunchKernelGGL(k_fedavg_f64_rows_scalar<false>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a, s,
-                               divisor, out);
-        return check_launch("fa_fedavg_f64_ptrs");
-    }
-    switch (pick_pairs(P, cu_count())) {
-        case 4: launch_f64_rows_gs<4>(st, xi, N, P, a, s, divisor, out); break;
-        case 2: launch_f64_rows_gs<2>(st, xi, N, P, a, s, divisor, out); break;
-        default: launch_f64_rows_gs<1>(st, xi, N, P, a, s, divisor, out); break;
-    }
-    return check_launch("fa_fedavg_f64_ptrs");
+    return rows_fold(
+        "fa_fedavg_f64_ptrs", xi, N, P, a, out, stream,
+        rows_aligned && !aligned16(out) ? "the pair form of the float64 row-table fold needs 16-B aligned rows and out"
+                                        : nullptr,
+        [&](hipStream_t st) {
+            if (!rows_aligned)
+                with_scored(s != nullptr, [&](auto SC) {
+                    hipLaunchKernelGGL(k_fedavg_f64_rows_scalar<SC.value>, grid_for(P), dim3(kBlock), 0, st, xi, N, P, a,
+                                       s, divisor, out);
+                });
+            else
+                with_units(pick_pairs(P, cu_count()), [&](auto C) {
+                    launch_f64_rows_gs<C.value>(st, xi, N, P, a, s, divisor, out);
+                });
+            return 0;
+        });
 }
 
 // ---- the layer-table folds (fa_fedavg_*_layers) ---------------------------
@@ -4748,42 +4659,29 @@ inline int f64_rows_fold(const double* const* xi, int64_t N, int64_t P, const do
 constexpr int kLayersU = 8;
 enum LayersKind { kLayersF32 = 0, kLayersBf16 = 1, kLayersF16 = 2, kLayersF64 = 3 };
 
-template <int C>
-void launch_layers(int kind, hipStream_t st, unsigned g, const void* const* xi, const fa_layer_plan* plan, int64_t L,
-                   int64_t N, int64_t tiles, const void* a, const void* s, double divisor, void* out, void* outb) {
-#define FA_LAY(K, SC, ...) \
-    hipLaunchKernelGGL((K<kLayersU, C, SC>), dim3(g), dim3(kBlock), 0, st, __VA_ARGS__, tiles)
-    switch (kind) {
-        case kLayersF32: {
-            const float* const* x = (const float* const*)xi;
-            const float *af = (const float*)a, *sf = (const float*)s;
-            if (s) FA_LAY(k_fold_f32_layers, true, x, plan, L, N, af, sf, (float)divisor, (float*)out);
-            else FA_LAY(k_fold_f32_layers, false, x, plan, L, N, af, sf, (float)divisor, (float*)out);
-            break;
-        }
-        case kLayersBf16: {
-            const uint16_t* const* x = (const uint16_t* const*)xi;
-            const float *af = (const float*)a, *sf = (const float*)s;
-            if (s) FA_LAY(k_fedavg_bf16_layers, true, x, plan, L, N, af, sf, (float)divisor, (float*)out, (uint16_t*)outb);
-            else FA_LAY(k_fedavg_bf16_layers, false, x, plan, L, N, af, sf, (float)divisor, (float*)out, (uint16_t*)outb);
-            break;
-        }
-        case kLayersF16: {
-            const uint16_t* const* x = (const uint16_t* const*)xi;
-            const uint16_t *ah = (const uint16_t*)a, *sh = (const uint16_t*)s;
-            if (s) FA_LAY(k_fedavg_f16_layers, true, x, plan, L, N, ah, sh, (float)divisor, (uint16_t*)out);
-            else FA_LAY(k_fedavg_f16_layers, false, x, plan, L, N, ah, sh, (float)divisor, (uint16_t*)out);
-            break;
-        }
-        default: {
-            const double* const* x = (const double* const*)xi;
-            const double *ad = (const double*)a, *sd = (const double*)s;
-            if (s) FA_LAY(k_fedavg_f64_layers, true, x, plan, L, N, ad, sd, divisor, (double*)out);
-            else FA_LAY(k_fedavg_f64_layers, false, x, plan, L, N, ad, sd, divisor, (double*)out);
-            break;
-        }
-    }
-#undef FA_LAY
+// The argument checks of the layer-table entries, in this order and with these
+// messages (tests pin the texts).  *empty: nothing to fold, FA_OK.  ptrs: xi,
+// plan, a and an output are given; aligned: the outputs are 16-B aligned.
+inline int check_layers(const char* what, int64_t L, int64_t N, int64_t tiles, int units, int64_t grid_cap, bool ptrs,
+                        bool aligned, bool* empty) {
+    *empty = false;
+    if (L < 0 || N < 0 || tiles < 0)
+        return fail(FA_ERR_ARG, "negative size (L=%lld, N=%lld, tiles=%lld)", (long long)L, (long long)N,
+                    (long long)tiles);
+    if (N == 0) return fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
+    if (units != 1 && units != 2 && units != 4)
+        return fail(FA_ERR_ARG, "%s: %d units per lane (1, 2 or 4)", what, units);
+    if (grid_cap < 0) return fail(FA_ERR_ARG, "%s: negative grid cap", what);
+    if (L == 0 || tiles == 0) { *empty = true; g_err[0] = 0; return FA_OK; }
+    if (!ptrs) return fail(FA_ERR_ARG, "null xi/plan/a/out pointer");
+    if (!aligned) return fail(FA_ERR_ARG, "%s needs 16-B aligned outputs", what);
+    if (tiles > (int64_t)0x7FFFFFFF) return fail(FA_ERR_ARG, "too many tiles for one launch");
+    return FA_OK;
+}
+inline dim3 layers_grid(int64_t tiles, int64_t grid_cap) {
+    int64_t g = tile_grid(tiles, -1, cu_count());
+    if (grid_cap > 0 && g > grid_cap) g = grid_cap;
+    return dim3((unsigned)g);
 }
 
 // divisor: the entry's divisor as a double (exact for a float32 and for the
@@ -4792,29 +4690,39 @@ inline int layers_fold(int kind, const char* what, const void* const* xi, const 
                        int64_t N, int64_t tiles, int units, int64_t grid_cap, const void* a, const void* s,
                        double divisor, void* out, void* outb, void* stream) {
     if (kind < kLayersF32 || kind > kLayersF64) return fail(FA_ERR_ARG, "%s: unknown dtype %d", what, kind);
-    if (L < 0 || N < 0 || tiles < 0)
-        return fail(FA_ERR_ARG, "negative size (L=%lld, N=%lld, tiles=%lld)", (long long)L, (long long)N,
-                    (long long)tiles);
-    if (N == 0) return fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
-    if (units != 1 && units != 2 && units != 4)
-        return fail(FA_ERR_ARG, "%s: %d units per lane (1, 2 or 4)", what, units);
-    if (grid_cap < 0) return fail(FA_ERR_ARG, "%s: negative grid cap", what);
-    if (L == 0 || tiles == 0) { g_err[0] = 0; return FA_OK; }
     const bool any_out = kind == kLayersBf16 ? (out || outb) : out != nullptr;
-    if (!xi || !plan || !a || !any_out) return fail(FA_ERR_ARG, "null xi/plan/a/out pointer");
-    if (!aligned16(out) || (kind == kLayersBf16 && !aligned16(outb)))
-        return fail(FA_ERR_ARG, "%s needs 16-B aligned outputs", what);
-    if (tiles > (int64_t)0x7FFFFFFF) return fail(FA_ERR_ARG, "too many tiles for one launch");
+    bool empty;
+    int rc = check_layers(what, L, N, tiles, units, grid_cap, xi && plan && a && any_out,
+                          aligned16(out) && (kind != kLayersBf16 || aligned16(outb)), &empty);
+    if (rc || empty) return rc;
     hipStream_t st = (hipStream_t)stream;
     StreamDevice on_stream_device(stream);
-    int64_t g = tile_grid(tiles, -1, cu_count());
-    if (grid_cap > 0 && g > grid_cap) g = grid_cap;
-    if (kind != kLayersBf16) outb = nullptr;
-    switch (units) {
-        case 4: launch_layers<4>(kind, st, (unsigned)g, xi, plan, L, N, tiles, a, s, divisor, out, outb); break;
-        case 2: launch_layers<2>(kind, st, (unsigned)g, xi, plan, L, N, tiles, a, s, divisor, out, outb); break;
-        default: launch_layers<1>(kind, st, (unsigned)g, xi, plan, L, N, tiles, a, s, divisor, out, outb); break;
-    }
+    const dim3 g = layers_grid(tiles, grid_cap);
+    with_units(units, [&](auto C) {
+        with_scored(s != nullptr, [&](auto SC) {
+#define FA_LAY(K, ...) \
+    hipLaunchKernelGGL((K<kLayersU, C.value, SC.value>), g, dim3(kBlock), 0, st, __VA_ARGS__, tiles)
+            switch (kind) {
+                case kLayersF32:
+                    FA_LAY(k_fold_f32_layers, (const float* const*)xi, plan, L, N, (const float*)a, (const float*)s,
+                           (float)divisor, (float*)out);
+                    break;
+                case kLayersBf16:
+                    FA_LAY(k_fedavg_bf16_layers, (const uint16_t* const*)xi, plan, L, N, (const float*)a,
+                           (const float*)s, (float)divisor, (float*)out, (uint16_t*)outb);
+                    break;
+                case kLayersF16:
+                    FA_LAY(k_fedavg_f16_layers, (const uint16_t* const*)xi, plan, L, N, (const uint16_t*)a,
+                           (const uint16_t*)s, (float)divisor, (uint16_t*)out);
+                    break;
+                default:
+                    FA_LAY(k_fedavg_f64_layers, (const double* const*)xi, plan, L, N, (const double*)a,
+                           (const double*)s, divisor, (double*)out);
+                    break;
+            }
+#undef FA_LAY
+        });
+    });
     return check_launch(what);
 }
 
@@ -4822,78 +4730,54 @@ inline int layers_fold(int kind, const char* what, const void* const* xi, const 
 // The layer-table launch over integer rows: the geometry of layers_fold (8 rows
 // ahead, the plan's units per lane, balanced passes over at most one block per
 // CU).  plan == NULL: the one layer `one` travels by value (the _ptrs entries).
-template <class I, int C>
-void launch_int_layers(hipStream_t st, unsigned g, const typename I::T* const* xi, const fa_layer_plan* plan,
+template <class I>
+void launch_int_layers(int units, hipStream_t st, dim3 g, const typename I::T* const* xi, const fa_layer_plan* plan,
                        const fa_layer_plan& one, int64_t L, int64_t N, int64_t tiles, const int64_t* a, const double* s,
                        double divisor, double* out) {
-    if (s)
-        hipLaunchKernelGGL((k_fedavg_int_layers<I, kLayersU, C, true>), dim3(g), dim3(kBlock), 0, st, xi, plan, one, L,
-                           N, a, s, divisor, out, tiles);
-    else
-        hipLaunchKernelGGL((k_fedavg_int_layers<I, kLayersU, C, false>), dim3(g), dim3(kBlock), 0, st, xi, plan, one, L,
-                           N, a, s, divisor, out, tiles);
+    with_units(units, [&](auto C) {
+        with_scored(s != nullptr, [&](auto SC) {
+            hipLaunchKernelGGL((k_fedavg_int_layers<I, kLayersU, C.value, SC.value>), g, dim3(kBlock), 0, st, xi, plan,
+                               one, L, N, a, s, divisor, out, tiles);
+        });
+    });
 }
 
-template <class I>
-void launch_int_layers_units(int units, hipStream_t st, unsigned g, const typename I::T* const* xi,
-                             const fa_layer_plan* plan, const fa_layer_plan& one, int64_t L, int64_t N, int64_t tiles,
-                             const int64_t* a, const double* s, double divisor, double* out) {
-    switch (units) {
-        case 4: launch_int_layers<I, 4>(st, g, xi, plan, one, L, N, tiles, a, s, divisor, out); break;
-        case 2: launch_int_layers<I, 2>(st, g, xi, plan, one, L, N, tiles, a, s, divisor, out); break;
-        default: launch_int_layers<I, 1>(st, g, xi, plan, one, L, N, tiles, a, s, divisor, out); break;
-    }
-}
-
-// The checks of layers_fold, in its order and with its messages
 template <class I>
 int int_layers_fold(const char* what, const typename I::T* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
                     int64_t tiles, int units, int64_t grid_cap, const int64_t* a, const double* s, double divisor,
                     double* out, void* stream) {
-    if (L < 0 || N < 0 || tiles < 0)
-        return fail(FA_ERR_ARG, "negative size (L=%lld, N=%lld, tiles=%lld)", (long long)L, (long long)N,
-                    (long long)tiles);
-    if (N == 0) return fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
-    if (units != 1 && units != 2 && units != 4)
-        return fail(FA_ERR_ARG, "%s: %d units per lane (1, 2 or 4)", what, units);
-    if (grid_cap < 0) return fail(FA_ERR_ARG, "%s: negative grid cap", what);
-    if (L == 0 || tiles == 0) { g_err[0] = 0; return FA_OK; }
-    if (!xi || !plan || !a || !out) return fail(FA_ERR_ARG, "null xi/plan/a/out pointer");
-    if (!aligned16(out)) return fail(FA_ERR_ARG, "%s needs 16-B aligned outputs", what);
-    if (tiles > (int64_t)0x7FFFFFFF) return fail(FA_ERR_ARG, "too many tiles for one launch");
+    bool empty;
+    int rc = check_layers(what, L, N, tiles, units, grid_cap, xi && plan && a && out, aligned16(out), &empty);
+    if (rc || empty) return rc;
     hipStream_t st = (hipStream_t)stream;
     StreamDevice on_stream_device(stream);
-    int64_t g = tile_grid(tiles, -1, cu_count());
-    if (grid_cap > 0 && g > grid_cap) g = grid_cap;
-    launch_int_layers_units<I>(units, st, (unsigned)g, xi, plan, fa_layer_plan{0, 0, 0, 0}, L, N, tiles, a, s, divisor,
-                               out);
+    launch_int_layers<I>(units, st, layers_grid(tiles, grid_cap), xi, plan, fa_layer_plan{0, 0, 0, 0}, L, N, tiles, a, s,
+                         divisor, out);
     return check_launch(what);
 }
 
 // One layer through the same kernel, its plan entry built here and passed by
-// value: no allocation, no copy, no synchronisation.  The checks of
-// f64_rows_fold.  rows_aligned == 0: one column per lane, rows and out at any
-// offset of the element size (out: 8 B).
+// value: no allocation, no copy, no synchronisation.  rows_aligned == 0: one
+// column per lane, rows and out at any offset of the element size (out: 8 B).
 template <class I>
 int int_rows_fold(const char* what, const typename I::T* const* xi, int64_t N, int64_t P, const int64_t* a,
                   const double* s, double divisor, int rows_aligned, double* out, void* stream) {
-    int rc = check_common(N, P, P, xi, a, out);
-    if (rc) return rc;
-    if (P == 0) { g_err[0] = 0; return FA_OK; }
-    if (rows_aligned && !aligned16(out))
-        return fail(FA_ERR_ARG, "the unit form of the integer row-table fold needs 16-B aligned rows and out");
-    hipStream_t st = (hipStream_t)stream;
-    StreamDevice on_stream_device(stream);
-    const int64_t cus = cu_count();
-    const int32_t al = rows_aligned != 0;
-    const int units = pick_layer_units(&P, &al, 1, I::LG, cus);
-    fa_layer_plan one;
-    int64_t elems = 0;
-    const int64_t tiles = fill_layer_plan(&P, &al, 1, units, I::LG, &one, &elems);
-    if (tiles > (int64_t)0x7FFFFFFF) return fail(FA_ERR_ARG, "too many tiles for one launch");
-    launch_int_layers_units<I>(units, st, (unsigned)tile_grid(tiles, -1, cus), xi, nullptr, one, 1, N, tiles, a, s,
-                               divisor, out);
-    return check_launch(what);
+    return rows_fold(
+        what, xi, N, P, a, out, stream,
+        rows_aligned && !aligned16(out) ? "the unit form of the integer row-table fold needs 16-B aligned rows and out"
+                                        : nullptr,
+        [&](hipStream_t st) {
+            const int64_t cus = cu_count();
+            const int32_t al = rows_aligned != 0;
+            const int units = pick_layer_units(&P, &al, 1, I::LG, cus);
+            fa_layer_plan one;
+            int64_t elems = 0;
+            const int64_t tiles = fill_layer_plan(&P, &al, 1, units, I::LG, &one, &elems);
+            if (tiles > (int64_t)0x7FFFFFFF) return fail(FA_ERR_ARG, "too many tiles for one launch");
+            launch_int_layers<I>(units, st, dim3((unsigned)tile_grid(tiles, -1, cus)), xi, nullptr, one, 1, N, tiles, a,
+                                 s, divisor, out);
+            return 0;
+        });
 }
 
 // ---- the widening folds (fa_fedavg_widen) -----------------------------------
@@ -4904,16 +4788,16 @@ template <class W>
 void launch_widen(hipStream_t st, const void* X, int64_t N, int64_t P, int64_t ldx, const void* a, const void* s,
                   double divisor, void* out) {
     const typename W::E* x = (const typename W::E*)X;
-    const typename W::FE *af = (const typename W::FE*)a, *sf = (const typename W::FE*)s;
+    const typename W::WE* af = (const typename W::WE*)a;
+    const typename W::SE* sf = (const typename W::SE*)s;
     const typename W::D d = (typename W::D)divisor;
     typename W::O* o = (typename W::O*)out;
     const bool vec = aligned16(X) && aligned16(out) && (ldx % (1 << W::LG) == 0);
     const dim3 g = vec ? dim3((unsigned)octet_grid(P, W::C, 0, 1, W::LG).grid) : grid_for(P);
-    auto k = vec ? k_fedavg_widen<W, false> : k_fedavg_widen_scalar<W, false>;
-    if constexpr (!std::is_same<W, WidenI32I64>::value) {
-        if (s) k = vec ? k_fedavg_widen<W, true> : k_fedavg_widen_scalar<W, true>;
-    }
-    hipLaunchKernelGGL(k, g, dim3(kBlock), 0, st, x, N, P, ldx, af, sf, d, o);
+    with_scored<!std::is_same<W, WidenI32I64>::value>(s != nullptr, [&](auto SC) {
+        hipLaunchKernelGGL((vec ? k_fedavg_widen<W, SC.value> : k_fedavg_widen_scalar<W, SC.value>), g, dim3(kBlock),
+                           0, st, x, N, P, ldx, af, sf, d, o);
+    });
 }
 
 template <class F>
