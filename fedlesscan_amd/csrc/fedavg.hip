@@ -595,6 +595,19 @@ int fa_widen_geometry(int kind, int* unit_cols, int* units, int* rows_ahead) {
     return widen_geometry(kind, unit_cols, units, rows_ahead);
 }
 
+// ---- promoted rows where the clients' tensors lie (widen_rows_fold, widen_layers_fold) ----
+int fa_fedavg_widen_ptrs(int kind, const void* const* xi, int64_t N, int64_t P, const void* a, const void* s,
+                         double divisor, int rows_aligned, void* out, void* stream) {
+    return widen_rows_fold(kind, xi, N, P, a, s, divisor, rows_aligned, out, stream);
+}
+
+int fa_fedavg_widen_layers(int kind, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
+                           int64_t tiles, int units, const void* a, const void* s, double divisor, void* out,
+                           void* stream) {
+    return widen_layers_fold("fa_fedavg_widen_layers", kind, xi, plan, L, N, tiles, units, 0, a, s, divisor, out,
+                             stream);
+}
+
 // ---- the same folds with the per-client factors in host memory ---------------
 int fa_factors_fill(float* dst, const float* a, const float* s, int64_t N, void* stream) {
     if (N < 0 || (N > 0 && (!dst || !a))) return fail(FA_ERR_ARG, "fa_factors_fill: N %lld, null pointer", (long long)N);

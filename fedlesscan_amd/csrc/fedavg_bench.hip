@@ -682,6 +682,12 @@ int fa_fedavg_int_layers_form(int dtype, const void* const* xi, const fa_layer_p
                                           units, grid_cap, a, s, divisor, out, stream);
     return fail(FA_ERR_ARG, "fa_fedavg_int_layers_form: unknown dtype %d", dtype);
 }
+int fa_fedavg_widen_layers_form(int kind, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
+                                int64_t tiles, int units, int64_t grid_cap, const void* a, const void* s,
+                                double divisor, void* out, void* stream) {
+    return widen_layers_fold("fa_fedavg_widen_layers_form", kind, xi, plan, L, N, tiles, units, grid_cap, a, s, divisor,
+                             out, stream);
+}
 const char* fa_variant_name(int variant) {
     return (variant >= 0 && variant < kNumVariants) ? kVariants[variant] : "";
 }

@@ -2944,6 +2944,7 @@ typedef int64_t i64x4 __attribute__((ext_vector_type(4)));
 // What the six kinds share: 16 bytes of any source dtype as loaded, the schedule
 struct WidenUnit {
     typedef u32x4 Unit;
+    typedef gu32x4 GUnit;  // ... and as global memory (TableRows); GE, per kind: one source element there
     static constexpr bool kAhead = true, kFactorsAhead = true, kOctetsLd = false, kTailLoop = true, kStoreLoop = true;
     static constexpr bool barrier(int, int) { return true; }
 };
@@ -2966,6 +2967,7 @@ struct WidenF64 : WidenUnit {
 };
 struct WidenF16F64 : WidenF64 {
     typedef uint16_t E;
+    typedef gu16 GE;
     static constexpr int LG = 3, NV = 4, C = 1, U = 8;  // 8 doubles per unit: one unit per lane
     static __device__ __forceinline__ void widen(u32x4 u, V (&w)[NV]) {
         const f64x8 d = __builtin_convertvector(__builtin_bit_cast(f16x8, u), f64x8);
@@ -2978,6 +2980,7 @@ struct WidenF16F64 : WidenF64 {
 };
 struct WidenF32F64 : WidenF64 {
     typedef float E;
+    typedef gf32 GE;
     static constexpr int LG = 2, NV = 2, C = 2, U = 8;
     static __device__ __forceinline__ void widen(u32x4 u, V (&w)[NV]) {
         const f64x4 d = __builtin_convertvector(__builtin_bit_cast(f32x4, u), f64x4);
@@ -2988,6 +2991,7 @@ struct WidenF32F64 : WidenF64 {
 };
 struct WidenI32F64 : WidenF64 {
     typedef int32_t E;
+    typedef Int32Rows::GE GE;
     static constexpr int LG = 2, NV = 2, C = 2, U = 8;
     static __device__ __forceinline__ void widen(u32x4 u, V (&w)[NV]) {
         const f64x4 d = __builtin_convertvector(__builtin_bit_cast(i32x4, u), f64x4);
@@ -2998,6 +3002,7 @@ struct WidenI32F64 : WidenF64 {
 };
 struct WidenI64F64 : WidenF64 {
     typedef int64_t E;
+    typedef Int64Rows::GE GE;
     static constexpr int LG = 1, NV = 1, C = 2, U = 8;
     // beyond 2^53 the conversion rounds to nearest even: the one of the scored integer folds
     static __device__ __forceinline__ void widen(u32x4 u, V (&w)[NV]) {
@@ -3007,6 +3012,7 @@ struct WidenI64F64 : WidenF64 {
 };
 struct WidenF16F32 : WidenUnit {
     typedef uint16_t E;
+    typedef gu16 GE;
     typedef float FE, WE, SE, O, D, S;
     typedef f32x4 V, X, Q;
     static constexpr int LG = 3, NV = 2, C = 2, U = 8;
@@ -3030,6 +3036,7 @@ struct WidenF16F32 : WidenUnit {
 struct WidenI32I64 : WidenUnit {  // unscored only: a score makes the fold float64 (WidenI32F64)
     typedef IntAcc<Int64Rows, false> A;
     typedef int32_t E;
+    typedef Int32Rows::GE GE;
     typedef int64_t FE, WE, SE;
     typedef double O, D;
     typedef u64x2 V, X;
@@ -3068,6 +3075,36 @@ __global__ __launch_bounds__(kBlock) void k_fedavg_widen_scalar(
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= P) return;
     out[c] = fold_column<W, SCORED, false, true, true>(PitchedRows<typename W::E>{X + c, ldx}, N, a, s, nullptr, divisor);
+}
+
+// The widening folds over row tables (fa_fedavg_widen_ptrs, fa_fedavg_widen_layers):
+// the promoted rows read where the clients' tensors lie, L*N row bases
+// layer-major and a plan as the layer-table folds above.  Grid-stride over the
+// tiles of all layers: unit_layers' walk -- layer_tile's search, then the tile
+// of k_fedavg_widen over TableSource<W>{xi + l*N} (the bases wave-uniform scalar
+// loads, the rows global loads of the narrow dtype, widened right after the
+// load), a layer with a row off 16 bytes one column per lane, 8 rows ahead, as
+// k_fedavg_widen_scalar -- so layer l of out holds the bits of fa_fedavg_widen
+// over that layer's rows stacked.  The plan's offsets count OUTPUT elements.
+// ONE: the single layer `one` travels by value (fa_fedavg_widen_ptrs: nothing
+// to allocate or upload).  The launch is the native layer tables' (layers_grid:
+// balanced passes over at most one block per CU): a grid of as many blocks as
+// the registers let reside on a CU (4-5, by the occupancy query) measured the
+// same at 100 x 1M and 2-3 % slower at 256 x 12.5M.
+// Compiled without packed fp32 instructions: the float32 kind's products and
+// sums are one v_mul_f32 / v_add_f32 per column, the same IEEE operations per
+// element as the packed pair forms, in a fold that waits on its loads.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FA_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define FA_NO_PACKED_F32  // a device feature: the host pass does not know it
+#endif
+template <class W, bool SCORED, bool ONE>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_widen_layers(
+    const typename W::E* const* __restrict__ xi, const fa_layer_plan* __restrict__ plan, fa_layer_plan one, int64_t L,
+    int64_t N, const typename W::FE* __restrict__ a, const typename W::FE* __restrict__ s, typename W::D divisor,
+    typename W::O* __restrict__ out, int64_t ntiles) {
+    unit_layers<W, W::U, W::C, SCORED, ONE>(xi, ONE ? nullptr : plan, L, N, a, s, divisor, out, ntiles, one);
 }
 
 // ---------------------------------------------------------------------------
@@ -4839,6 +4876,84 @@ inline int widen_geometry(int kind, int* unit_cols, int* units, int* rows_ahead)
     if (!known) return fail(FA_ERR_ARG, "fa_widen_geometry: unknown kind %d", kind);
     g_err[0] = 0;
     return FA_OK;
+}
+
+// ---- the widening folds over row tables (fa_fedavg_widen_ptrs, _layers) -------
+// The launch of k_fedavg_widen_layers: the kind's own geometry (W::C units per
+// lane, W::U rows ahead), the grid of the native layer tables (layers_grid).
+// plan == NULL: the one layer `one`, by value.  grid_cap > 0 (the bench
+// library): at most that many blocks.
+template <class W>
+void launch_widen_layers(hipStream_t st, int64_t grid_cap, const void* const* xi, const fa_layer_plan* plan,
+                         const fa_layer_plan& one, int64_t L, int64_t N, int64_t tiles, const void* a, const void* s,
+                         double divisor, void* out) {
+    with_scored<!std::is_same<W, WidenI32I64>::value>(s != nullptr, [&](auto SC) {
+        auto go = [&](auto ONE) {
+            hipLaunchKernelGGL((k_fedavg_widen_layers<W, SC.value, ONE.value>), layers_grid(tiles, grid_cap),
+                               dim3(kBlock), 0, st, (const typename W::E* const*)xi, plan, one, L, N,
+                               (const typename W::FE*)a, (const typename W::FE*)s, (typename W::D)divisor,
+                               (typename W::O*)out, tiles);
+        };
+        if (plan) go(std::false_type{});
+        else go(std::true_type{});
+    });
+}
+
+inline int check_widen_kind(const char* what, int kind, const void* s) {
+    if (!with_widen_kind(kind, [](auto) {})) return fail(FA_ERR_ARG, "%s: unknown kind %d", what, kind);
+    if (kind == FA_WIDEN_I32_I64 && s)
+        return fail(FA_ERR_ARG, "%s: int32 rows under int64 factors take no scores (s must be NULL)", what);
+    return FA_OK;
+}
+
+inline int widen_layers_fold(const char* what, int kind, const void* const* xi, const fa_layer_plan* plan, int64_t L,
+                             int64_t N, int64_t tiles, int units, int64_t grid_cap, const void* a, const void* s,
+                             double divisor, void* out, void* stream) {
+    int rc = check_widen_kind(what, kind, s);
+    if (rc) return rc;
+    bool empty;
+    rc = check_layers(what, L, N, tiles, units, grid_cap, xi && plan && a && out, aligned16(out), &empty);
+    if (rc) return rc;
+    int kind_units = 0;
+    with_widen_kind(kind, [&](auto w) { kind_units = decltype(w)::C; });
+    if (units != kind_units)
+        return fail(FA_ERR_ARG, "%s: %d units per lane, the kind folds %d (fa_widen_geometry)", what, units, kind_units);
+    if (empty) return FA_OK;
+    StreamDevice on_stream_device(stream);
+    with_widen_kind(kind, [&](auto w) {
+        launch_widen_layers<decltype(w)>((hipStream_t)stream, grid_cap, xi, plan, fa_layer_plan{0, 0, 0, 0}, L, N, tiles, a,
+                                         s, divisor, out);
+    });
+    return check_launch(what);
+}
+
+// One layer through the same kernel, its plan entry built here and passed by
+// value (as int_rows_fold).  rows_aligned == 0: one column per lane, rows at
+// any offset of the element size and out at any offset of its own.
+inline int widen_rows_fold(int kind, const void* const* xi, int64_t N, int64_t P, const void* a, const void* s,
+                           double divisor, int rows_aligned, void* out, void* stream) {
+    int rc = check_widen_kind("fa_fedavg_widen_ptrs", kind, s);
+    if (rc) return rc;
+    return rows_fold(
+        "fa_fedavg_widen_ptrs", xi, N, P, a, out, stream,
+        rows_aligned && !aligned16(out) ? "the unit form of the widening row-table fold needs 16-B aligned rows and out"
+                                        : nullptr,
+        [&](hipStream_t st) {
+            int lrc = 0;
+            with_widen_kind(kind, [&](auto w) {
+                typedef decltype(w) W;
+                const int32_t al = rows_aligned != 0;
+                fa_layer_plan one;
+                int64_t elems = 0;
+                const int64_t tiles = fill_layer_plan(&P, &al, 1, W::C, W::LG, &one, &elems);
+                if (tiles > (int64_t)0x7FFFFFFF) {
+                    lrc = fail(FA_ERR_ARG, "too many tiles for one launch");
+                    return;
+                }
+                launch_widen_layers<W>(st, 0, xi, nullptr, one, 1, N, tiles, a, s, divisor, out);
+            });
+            return lrc;
+        });
 }
 
 inline int layers_plan(const int64_t* cols, const int32_t* aligned, int64_t L, int unit_lg, int64_t cus, int units,

@@ -367,6 +367,50 @@ def _widen(kind: Optional[int], P: int) -> bool:
             and not torch.cuda.is_current_stream_capturing())
 
 
+def widen_rows_enabled() -> bool:
+    """FEDAVG_WIDEN_ROWS=1 (read per call) lets aggregate_layers and the
+    strategy classes fold a promoted device group through the widening row
+    tables (fold_rows / fold_model_rows) instead of stacking it; the default
+    keeps the stacked copy there.  fold_rows and fold_model_rows themselves
+    take the tables whatever it says."""
+    return os.environ.get("FEDAVG_WIDEN_ROWS", "0") == "1"
+
+
+def widen_factors(in_dt, weights: Sequence, scores: Optional[Sequence] = None, total=None):
+    """(kind, Factors) of a promoted fold over rows of dtype `in_dt` that a
+    widening kernel computes from the narrow rows, with the factors fold_stacked
+    builds for that kind (the kind's factor dtype; int64 cardinalities for
+    int32 rows under int64 weights) -- or None: the fold is not promoted, numpy
+    types it term by term, no kernel converts that pair, or FEDAVG_WIDEN=0.
+    Pure host code; raises what fold_plan raises."""
+    if not widen_enabled() or not len(weights):
+        return None
+    dt = fold_plan(in_dt, weights, scores, total).uniform
+    kind = widen_kind(in_dt, dt)
+    if kind is None:
+        return None
+    if dt.kind == "i":
+        return kind, Factors(weights, None, dt, int_weights=True, total=total)
+    return kind, Factors(weights, scores, dt, total=total)
+
+
+_widen_geometries: dict = {}
+
+
+def widen_geometry(kind: int) -> tuple:
+    """fa_widen_geometry: (columns of a 16-byte source unit, units per lane, rows ahead).  No GPU."""
+    g = _widen_geometries.get(kind)
+    if g is None:
+        u, c, r = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _lib.call("fa_widen_geometry", kind, ctypes.addressof(u), ctypes.addressof(c), ctypes.addressof(r))
+        g = _widen_geometries[kind] = (u.value, c.value, r.value)
+    return g
+
+
+def _widen_out_dtype(kind: int) -> torch.dtype:
+    return torch.float32 if kind == _lib.FA_WIDEN_F16_F32 else torch.float64
+
+
 def _check_matrix(X: torch.Tensor) -> tuple[int, int, int]:
     if not X.is_cuda:
         raise ValueError("X must be a CUDA (HIP) tensor")
@@ -966,9 +1010,11 @@ _NO_CAPTURE_TABLE = (torch.float64, torch.int32, torch.int64)
 # counts each of its layers), layer groups copied into a stacked matrix,
 # one-launch model folds (fa_fedavg_*_layers), integer folds that ran through a
 # row table (counted as the float64 ones), promoted stacked folds that read
-# the narrow rows (fa_fedavg_widen; nothing else counts there)
+# the narrow rows (fa_fedavg_widen; nothing else counts there), layers folded
+# through a widening row table (fa_fedavg_widen_ptrs, or each layer of a
+# fa_fedavg_widen_layers launch) and those launches (they move no other counter)
 stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0, "layer_table_folds": 0, "rows_int_folds": 0,
-         "widened_folds": 0}
+         "widened_folds": 0, "widened_row_folds": 0, "widened_table_folds": 0}
 
 
 class RowSet:
@@ -1149,12 +1195,37 @@ def _fold_rows_int(rs: "RowSet", f: Factors, out):
     return out
 
 
+def _fold_rows_widen(rs: "RowSet", kind: int, f: Factors, out):
+    """Promoted rows through the row table (fa_fedavg_widen_ptrs) with the
+    factors of widen_factors: neither a stacked nor a widened copy; out in the
+    promoted dtype."""
+    dev, P = rs.device, rs.P
+    res_dt = _widen_out_dtype(kind)
+    _check_out("out", out, res_dt, P)
+    dst = out
+    if out is not None and rs.overlaps(out):
+        out = None
+    if out is None:
+        out = torch.empty(P, dtype=res_dt, device=dev)
+    a, s = f.to(dev)
+    aligned = rs.aligned and out.data_ptr() % 16 == 0
+    _lib.call("fa_fedavg_widen_ptrs", kind, rs.ptrs.data_ptr(), rs.N, P, a.data_ptr(), _ptr(s), float(f.div),
+              int(aligned), out.data_ptr(), stream_ptr(dev))
+    stats["widened_row_folds"] += 1
+    if dst is not None and dst is not out:
+        dst.reshape(-1)[:P].copy_(out)
+        return dst
+    return out
+
+
 def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
               out: Optional[torch.Tensor] = None, total=None, want_bf16: bool = False,
               out_bf16: Optional[torch.Tensor] = None):
     """The fold over separately allocated 1-D CUDA rows (no stacking copy for
-    fp32, bfloat16, float16 / float64 rows whose result stays in their dtype, and
-    int32 / int64 rows whose products stay in their dtype: int_row_factors).  `rows` is a
+    fp32, bfloat16, float16 / float64 rows whose result stays in their dtype,
+    int32 / int64 rows whose products stay in their dtype: int_row_factors, and
+    rows numpy promotes as a whole where a widening kernel converts them on
+    load: widen_factors).  `rows` is a
     RowSet (prepared once, reusable) or a sequence of tensors (a RowSet is
     built for this call).  want_bf16 / out_bf16: as fold_stacked (bf16 rows)."""
     rs = rows if isinstance(rows, RowSet) else RowSet(rows)
@@ -1185,9 +1256,16 @@ def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
     fw = Factors.weak_f32(weights, scores, total) if rs.dtype == torch.float32 else None
     if fw is None and (rs.dtype != torch.float32
                        or result_dtype(np.dtype(np.float32), weights, scores, total) != np.float32):
-        # no row-table fold for this dtype / these factors (float16 rows under
-        # numpy-scalar weights promote): the stacked fold, over the rows' own
-        # storage when they sit at a fixed pitch, else over a stacked copy
+        # numpy promotes the fold (float16 rows under np.float32 weights, float32
+        # rows under an np.int64 from len(), integer rows under float weights):
+        # rows apart go through the widening row table, converted on load
+        if (rs.view is None and rs.ptrs is not None and rs.P > 0 and rs.dtype in _TORCH_TO_NP
+                and not torch.cuda.is_current_stream_capturing()):
+            wf = widen_factors(_TORCH_TO_NP[rs.dtype], weights, scores, total)
+            if wf is not None:
+                return _fold_rows_widen(rs, *wf, out)
+        # no row-table fold for this dtype / these factors: the stacked fold, over
+        # the rows' own storage when they sit at a fixed pitch, else over a stacked copy
         X = rs.view if rs.view is not None else rs.stacked()
         return fold_stacked(X, weights, scores, out=out, total=total)
     if rs.view is not None or rs.P == 0:
@@ -1259,6 +1337,16 @@ def layer_plan(cols: Sequence[int], aligned: Sequence[bool], unit_lg: int, cus: 
     return plan, tiles.value, elems.value, u.value
 
 
+def plan_at_units(host_plan: np.ndarray, elems: int, unit_lg: int, cus: int, units: int):
+    """The layers of `host_plan` (a layer_plan result) planned again at `units`
+    units per lane: (plan, tiles).  Only tile0 may differ: a layer's offset is
+    its predecessors' columns rounded up to 64 elements, whatever the tiling,
+    so results split by the first plan's offsets stay valid.  No GPU."""
+    plan, tiles, e, u = layer_plan(host_plan[:, 0], host_plan[:, 3], unit_lg, cus, units)
+    assert u == units and e == elems and np.array_equal(plan[:, [0, 1, 3]], host_plan[:, [0, 1, 3]])
+    return plan, tiles
+
+
 class ModelRowSet:
     """N clients x L layers already on the GPU, prepared once for repeated
     one-launch folds (fold_model_rows): what RowSet is for one layer.
@@ -1303,6 +1391,7 @@ class ModelRowSet:
         self.esize = t0.element_size() if t0 is not None else 0
         self.entry = None
         self._rowsets: dict = {}
+        self._plans: dict = {}
         self.ptrs = self.plan = self.host_plan = None
         self.tiles = self.elems = self.units = 0
         if self.dtype in _LAYER_TABLE and self.L:
@@ -1313,6 +1402,18 @@ class ModelRowSet:
             both = torch.from_numpy(np.concatenate([host_ptrs.reshape(-1), self.host_plan.reshape(-1)])).to(self.device)
             self.ptrs, self.plan = both[:self.L * N], both[self.L * N:]
         self.offsets = [int(o) for o in self.host_plan[:, 1]] if self.host_plan is not None else []
+
+    def plan_for(self, units: int):
+        """(device plan, tiles) of the set's layers at `units` units per lane:
+        the set's own where its rule chose that many, else planned on first
+        use, uploaded once and kept (the widening kinds fix their units)."""
+        if units == self.units:
+            return self.plan, self.tiles
+        hit = self._plans.get(units)
+        if hit is None:
+            host, tiles = plan_at_units(self.host_plan, self.elems, _LAYER_TABLE[self.dtype][1], _cus(self.device), units)
+            hit = self._plans[units] = (torch.from_numpy(host.reshape(-1)).to(self.device), tiles)
+        return hit
 
     def overlaps(self, t: torch.Tensor) -> bool:
         """Does tensor t share a byte with any client tensor of the set?"""
@@ -1382,9 +1483,13 @@ def fold_model_rows(model, weights: Sequence, scores: Optional[Sequence] = None,
     rules).  out / out_bf16: flat buffers of model.elems elements to
     fold into; want_bf16 / out_bf16 (bf16 layers): as fold_rows, a pair of
     lists (fp32 layers, RNE bf16 layers), or the bf16 list alone when only
-    out_bf16 was given.  Where fold_rows would leave the row table (factors
-    that promote the result, a dtype without a table, a stream capture in
-    progress) every layer goes through fold_rows on its own, over the set's
+    out_bf16 was given.  Factors that promote the whole fold (widen_factors)
+    take the widening layer table, fa_fedavg_widen_layers: still one launch,
+    over a plan at the kind's units per lane that the set keeps, the layers in
+    the promoted dtype, out= a flat buffer of that dtype.  Where fold_rows
+    would leave the row table (a fold numpy types term by term, a dtype
+    without a table, FEDAVG_WIDEN=0 under promoting factors, a stream capture
+    in progress) every layer goes through fold_rows on its own, over the set's
     own table and into fresh tensors (out / out_bf16 are refused there)."""
     ms = model if isinstance(model, ModelRowSet) else ModelRowSet(model)
     N = ms.N
@@ -1394,9 +1499,14 @@ def fold_model_rows(model, weights: Sequence, scores: Optional[Sequence] = None,
     bf16 = ms.dtype == torch.bfloat16
     if (out_bf16 is not None or want_bf16) and not bf16:
         raise InvalidParameterShapeError("want_bf16 / out_bf16 are for bfloat16 layers")
-    f = None
+    f = kind = None
     if ms.entry is not None and not torch.cuda.is_current_stream_capturing():
         f = _layer_factors(ms.dtype, weights, scores, total)
+        if f is None and ms.dtype in _TORCH_TO_NP:
+            # numpy promotes the whole fold: the widening layer table, where a kernel converts these rows on load
+            wf = widen_factors(_TORCH_TO_NP[ms.dtype], weights, scores, total)
+            if wf is not None:
+                kind, f = wf
     if f is None:
         if out is not None or out_bf16 is not None:
             raise InvalidParameterShapeError("out / out_bf16 need the layer-table route (no promotion, no capture)")
@@ -1407,6 +1517,8 @@ def fold_model_rows(model, weights: Sequence, scores: Optional[Sequence] = None,
         return [r.reshape(s) for r, s in zip(res, ms.shapes)]
     dev, E = ms.device, ms.elems
     res_dt = torch.float32 if bf16 else torch.float64 if ms.dtype in _INT_ROWS else ms.dtype
+    if kind is not None:
+        res_dt = _widen_out_dtype(kind)
     _check_out("out", out, res_dt, E)
     _check_out("out_bf16", out_bf16, torch.bfloat16, E)
 
@@ -1421,6 +1533,19 @@ def fold_model_rows(model, weights: Sequence, scores: Optional[Sequence] = None,
     if out is None and (dst is not None or outb is None or want_bf16):
         out = torch.empty(E, dtype=res_dt, device=dev)
     a, s = f.to(dev)
+    folded = sum(1 for n in ms.sizes if n)  # layers folded through a table, as fold_rows counts them
+    if kind is not None:
+        # the kind fixes the units per lane; the offsets are the set's own (plan_at_units), so split() holds
+        units = widen_geometry(kind)[1]
+        plan, tiles = ms.plan_for(units)
+        _lib.call("fa_fedavg_widen_layers", kind, ms.ptrs.data_ptr(), plan.data_ptr(), ms.L, N, tiles, units,
+                  a.data_ptr(), _ptr(s), float(f.div), out.data_ptr(), stream_ptr(dev))
+        stats["widened_table_folds"] += 1
+        stats["widened_row_folds"] += folded
+        if dst is not None and dst is not out:
+            dst.reshape(-1)[:E].copy_(out)
+            out = dst
+        return ms.split(out.reshape(-1))
     args = [ms.ptrs.data_ptr(), ms.plan.data_ptr(), ms.L, N, ms.tiles, ms.units, a.data_ptr(), _ptr(s)]
     if bf16:
         _lib.call(ms.entry, *args, float(f.div), _ptr(out), _ptr(outb), stream_ptr(dev))
@@ -1429,7 +1554,6 @@ def fold_model_rows(model, weights: Sequence, scores: Optional[Sequence] = None,
     else:
         _lib.call(ms.entry, *args, float(f.div), out.data_ptr(), stream_ptr(dev))
     stats["layer_table_folds"] += 1
-    folded = sum(1 for n in ms.sizes if n)  # layers folded through a table, as fold_rows counts them
     if ms.dtype == torch.float64:
         stats["rows64_folds"] += folded
     elif ms.dtype in _INT_ROWS:
@@ -1479,20 +1603,25 @@ def _rows_route(dt, fp32_result: bool, w, sc, total, where: torch.device, dev) -
     stays float16; float64 layers whose result stays float64; int32 / int64
     layers whose fold int_row_factors accepts (it raises numpy's OverflowError
     here, before any launch).  The 16-bit, float64 and integer groups only where the layers already lie on the device the fold
-    was asked for (the stacked copy is what moves them)."""
-    if dt == torch.float32:
-        return fp32_result
+    was asked for (the stacked copy is what moves them).  With
+    FEDAVG_WIDEN_ROWS=1 also a group numpy promotes as a whole, where a
+    widening kernel converts its rows on load (widen_factors), under the
+    conditions of the integer groups."""
+    if dt == torch.float32 and fp32_result:
+        return True
     d = torch.device(dev)
     here = where.type == d.type and where.index == (d.index if d.index is not None else torch.cuda.current_device())
     if dt == torch.bfloat16:
         return here
+    capturing = torch.cuda.is_current_stream_capturing()
     if dt == torch.float64:
-        return (here and not torch.cuda.is_current_stream_capturing()
-                and result_dtype(_F64, w, sc, total) == _F64)
-    if dt in _INT_ROWS:
-        return (here and not torch.cuda.is_current_stream_capturing()
-                and int_row_factors(_TORCH_TO_NP[dt], w, sc, total) is not None)
-    return dt == torch.float16 and here and result_dtype(np.dtype(np.float16), w, sc, total) == np.float16
+        return here and not capturing and result_dtype(_F64, w, sc, total) == _F64
+    if dt in _INT_ROWS and here and not capturing and int_row_factors(_TORCH_TO_NP[dt], w, sc, total) is not None:
+        return True
+    if dt == torch.float16 and here and result_dtype(np.dtype(np.float16), w, sc, total) == np.float16:
+        return True
+    return (widen_rows_enabled() and here and not capturing and dt in _TORCH_TO_NP
+            and widen_factors(_TORCH_TO_NP[dt], w, sc, total) is not None)
 
 
 def _multi(devices) -> Optional[list]:
@@ -1587,7 +1716,8 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
                                        parameters[0][lis[0]].device, dev) and all(
                 parameters[i][li].is_contiguous() for i in range(n_eff) for li in lis):
             # device fp32 / bf16 layers, float16 / float64 layers whose result stays in
-            # their dtype, and integer layers whose products stay in theirs: fold each layer straight from the clients' own tensors
+            # their dtype, integer layers whose products stay in theirs, and (FEDAVG_WIDEN_ROWS=1) groups
+            # promoted as a whole: fold each layer straight from the clients' own tensors
             # through a row-pointer list -- no stacking copy.  Two or more layers: one
             # table of every layer's rows and one launch (FEDAVG_LAYER_TABLE=0: a
             # fold per layer); the same bits either way

@@ -619,9 +619,8 @@ int fa_fedavg_i64_layers(const int64_t* const* xi, const fa_layer_plan* plan, in
  * adds (fa_widen_geometry reports it); X or out off 16-B alignment, or ldx not
  * a multiple of the unit's columns: one column per lane, 8 rows ahead, the same
  * bits.  Argument checks and status codes as fa_fedavg_f64; an unknown kind, or
- * s != NULL with FA_WIDEN_I32_I64 -> FA_ERR_ARG.  Not covered: row tables and
- * layer tables of promoted rows, folds numpy types term by term, the ingest
- * pipe, the sharded step. */
+ * s != NULL with FA_WIDEN_I32_I64 -> FA_ERR_ARG.  Not covered: folds numpy
+ * types term by term, the ingest pipe, the sharded step. */
 #define FA_WIDEN_F16_F32 0
 #define FA_WIDEN_F16_F64 1
 #define FA_WIDEN_F32_F64 2
@@ -633,6 +632,41 @@ int fa_fedavg_widen(int kind, const void* X, int64_t N, int64_t P, int64_t ldx,
 /* [host] The geometry of a kind: the columns of a 16-byte source unit, the
  * units per lane of a tile, the rows of loads ahead.  Touches no GPU. */
 int fa_widen_geometry(int kind, int* unit_cols, int* units, int* rows_ahead);
+
+/* ---- promoted rows where the clients' tensors lie (new symbols, ABI still 7) --
+ * A device-resident simulation keeps every client's layers in tensors of their
+ * own; under a promoting cardinality (fed_avg_aggregator.py:33: `layer *
+ * num_examples`, the fold and quotient of :38-41; with scores
+ * stall_aware_aggregation.py:52-66) these fold them through a row table, with
+ * neither a stacked nor a widened copy.  kind, a, s, divisor and the output
+ * dtype as fa_fedavg_widen's table; every 16-byte unit of the rows' own dtype
+ * is widened right after its load and folded in the wide dtype's arithmetic:
+ * the bits of fa_fedavg_widen over the same rows stacked.
+ *   fa_fedavg_widen_ptrs: one layer, xi a [device] array of N [device] row
+ *     pointers.  rows_aligned != 0 promises 16-B aligned rows and out (the
+ *     kind's tile: 256 lanes x `units` source units, 8 rows ahead); with 0,
+ *     rows at any offset of their element size and out at any offset of its
+ *     own, one column per lane.  The same bits either way.  Argument checks and
+ *     status codes as fa_fedavg_f64_ptrs.  The layer's plan entry travels by
+ *     value in the launch: no allocation, no copy, no synchronisation.
+ *   fa_fedavg_widen_layers: all L layers in one launch; xi holds L*N row bases,
+ *     layer-major; plan / tiles from fa_layers_plan with unit_lg = log2 of the
+ *     kind's unit_cols and units = the kind's units (fa_widen_geometry); any
+ *     other `units` -> FA_ERR_ARG.  The plan's offset and elems count OUTPUT
+ *     elements: every layer starts at a multiple of 64 elements of the flat
+ *     out, so a 16-B aligned out keeps every layer's stores aligned.  Layer l
+ *     of out holds the bits of the _ptrs entry on that layer.  Argument checks
+ *     and status codes as fa_fedavg_f64_layers.  Neither allocates nor
+ *     synchronises.
+ * Both walk the tiles grid-stride, balanced passes over at most one block per
+ * CU, as the other layer tables.  An unknown kind, or s != NULL with FA_WIDEN_I32_I64 -> FA_ERR_ARG.  Not covered:
+ * folds numpy types term by term, the ingest pipe, the sharded step, several
+ * GPUs, a tuner kind, help for stream capture. */
+int fa_fedavg_widen_ptrs(int kind, const void* const* xi, int64_t N, int64_t P, const void* a, const void* s,
+                         double divisor, int rows_aligned, void* out, void* stream);
+int fa_fedavg_widen_layers(int kind, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
+                           int64_t tiles, int units, const void* a, const void* s, double divisor, void* out,
+                           void* stream);
 
 /* ---- host staging: page-locked documents and direct DMA ---------------------
  * A result store that keeps documents in page-locked memory lets the ingest

@@ -128,6 +128,13 @@ int fa_fedavg_layers_form(int dtype, const void* const* xi, const fa_layer_plan*
 int fa_fedavg_int_layers_form(int dtype, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
                               int64_t tiles, int units, int64_t grid_cap, const int64_t* a, const double* s,
                               double divisor, double* out, void* stream);
+/* The same for the widening layer-table fold (fa_fedavg_widen_layers): kind,
+ * a, s, divisor, units and out as that entry's; grid_cap > 0 caps its grid,
+ * so a block walks several tiles across layer boundaries.  fa_fedavg_widen_ptrs runs this kernel over one by-value layer
+ * and has no capped form of its own. */
+int fa_fedavg_widen_layers_form(int kind, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
+                                int64_t tiles, int units, int64_t grid_cap, const void* a, const void* s,
+                                double divisor, void* out, void* stream);
 /* Same for the bf16 fold (variant 0 = fa_fedavg_bf16). */
 int fa_fedavg_bf16_variant(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
                            const float* a, const float* s, float divisor,
