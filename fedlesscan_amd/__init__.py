@@ -18,3 +18,4 @@ from .aggregator import (  # noqa: F401,E402
     StreamStallAwareAggregator,
     UnknownCardinalityError,
 )
+from .engine import ScaledLayer  # noqa: F401,E402

@@ -272,6 +272,17 @@ int fa_fedavg_f16_ptrs(const uint16_t* const* xi, int64_t N, int64_t P, const ui
     return f16_rows_fold(xi, N, P, a, s, divisor, rows_aligned, out, stream);
 }
 
+int fa_fedavg_fp8(int fmt, const uint8_t* X, int64_t N, int64_t P, int64_t ldx, const float* a, const float* s,
+                  const float* c, float divisor, float* out_f32, uint16_t* out_bf16, void* stream) {
+    return fp8_fold(fmt, X, N, P, ldx, a, s, c, divisor, out_f32, out_bf16, stream);
+}
+
+int fa_fedavg_fp8_ptrs(int fmt, const uint8_t* const* xi, int64_t N, int64_t P, const float* a, const float* s,
+                       const float* c, float divisor, int rows_aligned, float* out_f32, uint16_t* out_bf16,
+                       void* stream) {
+    return fp8_rows_fold(fmt, xi, N, P, a, s, c, divisor, rows_aligned, out_f32, out_bf16, stream);
+}
+
 // ---- one launch per exchange step (struct fa_rounds: peer_exchange.hpp) ------
 
 int fa_rounds_create(fa_rounds** r, int device) {

@@ -665,6 +665,26 @@ int fa_fedavg_f16_ptrs_form(const uint16_t* const* xi, int64_t N, int64_t P, con
                             uint16_t divisor, int rows_aligned, uint16_t* out, void* stream, int form) {
     return f16_rows_fold(xi, N, P, a, s, divisor, rows_aligned, out, stream, form < 0 ? -1 : form);
 }
+int fa_fedavg_fp8_form(const uint8_t* X, int64_t N, int64_t P, int64_t ldx, const float* a, const float* s,
+                       const float* c, float divisor, float* out_f32, uint16_t* out_bf16, void* stream, int form,
+                       int blocks_per_cu) {
+    bool go;
+    const int rc = fp8_fold_checks(FA_FP8_E4M3FN, X, N, P, ldx, a, out_f32, out_bf16, &go);
+    if (!go) return rc;
+    if (form < 0 || form > 3 || blocks_per_cu < 1 || !fp8_vec(X, ldx, out_f32, out_bf16))
+        return fail(FA_ERR_ARG, "fp8 form %d over %d blocks per CU: forms 0..3, aligned rows and outputs", form,
+                    blocks_per_cu);
+    StreamDevice on_stream_device(stream);
+    const Fp8Pitched src{X, ldx};
+    hipStream_t st = (hipStream_t)stream;
+    switch (form) {
+        case 0: launch_fp8<Fp8E4M3, 0>(st, true, src, N, P, a, s, c, divisor, out_f32, out_bf16, blocks_per_cu); break;
+        case 1: launch_fp8<Fp8E4M3, 1>(st, true, src, N, P, a, s, c, divisor, out_f32, out_bf16, blocks_per_cu); break;
+        case 2: launch_fp8<Fp8E4M3, 2>(st, true, src, N, P, a, s, c, divisor, out_f32, out_bf16, blocks_per_cu); break;
+        default: launch_fp8<Fp8E4M3, 3>(st, true, src, N, P, a, s, c, divisor, out_f32, out_bf16, blocks_per_cu); break;
+    }
+    return check_launch("fa_fedavg_fp8_form");
+}
 int fa_fedavg_layers_form(int dtype, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
                           int64_t tiles, int units, int64_t grid_cap, const void* a, const void* s, double divisor,
                           void* out, void* out_bf16, void* stream) {

@@ -3108,6 +3108,290 @@ FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_widen_layers
 }
 
 // ---------------------------------------------------------------------------
+// fp8 rows (OCP e4m3fn / e5m2) with an optional dequantisation scale per client
+// (fa_fedavg_fp8, fa_fedavg_fp8_ptrs).  The 8-bit family
+// beside the 16-bit octets: a 16-byte load is 16 columns of one row, widened
+// exactly to float32 and folded in float32 as the bf16 fold does,
+//   x = f32(q);  x = fl(x * c_i) [scaled];  t = fl(x * a_i);  t = fl(t * s_i) [scored]
+//   acc = t_0;  acc = fl(acc + t_i) in row order;  out = fl(acc / divisor)
+// Geometry, one per entry and fixed: a lane owns kFp8C = 2 units spaced kBlock
+// apart and loads kFp8U = 8 rows at a time, the next 8 while it folds these
+// (16 to 32 loads of 16 B in flight, 32 float32 accumulators); a tile is
+//   kFp8TileCols = kBlock * kFp8C * 16 = 8192 columns.
+// Tiles are walked grid-stride over balanced passes of at most two blocks per
+// CU (Src::kBlocksPerCu); the measurements behind that, and behind kFp8Form,
+// are in DESIGN.md 5 fp8.
+// Conversion: v_cvt_pk_f32_fp8 / v_cvt_pk_f32_bf8, two columns per instruction
+// (gfx950 decodes the OCP formats: all 256 bytes of each, NaNs and subnormals
+// included, compared with the CPU upcast by tests/test_gpu_fp8.py); a single
+// column (tail lanes, the one-column kernel) v_cvt_f32_fp8 / _bf8 of byte 0.
+// Products and sums are one v_mul_f32 / v_add_f32 per column (compiled without
+// packed fp32 instructions, as the widening layer folds above).
+// ---------------------------------------------------------------------------
+constexpr int kFp8U = 8, kFp8C = 2, kFp8LG = 4;
+constexpr int kFp8TileCols = kBlock * kFp8C * (1 << kFp8LG);
+typedef __attribute__((address_space(1))) const uint8_t gu8;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// The row sources, passed to the kernels by value: the lane's units from unit
+// o on, its column c, of a stacked byte matrix and of a table of row bases
+struct Fp8Pitched {
+    static constexpr int kBlocksPerCu = 2;
+    const uint8_t* X;
+    int64_t ldx;
+    __device__ __forceinline__ PitchedRows<u32x4> units(int64_t o) const {
+        return {reinterpret_cast<const u32x4*>(X) + o, ldx >> kFp8LG};
+    }
+    __device__ __forceinline__ PitchedRows<uint8_t> column(int64_t c) const { return {X + c, ldx}; }
+};
+struct Fp8Table {
+    static constexpr int kBlocksPerCu = 2;
+    const uint8_t* const* xi;
+    __device__ __forceinline__ TableRows<gu32x4, uint8_t> units(int64_t o) const { return {xi, o}; }
+    __device__ __forceinline__ TableRows<gu8, uint8_t> column(int64_t c) const { return {xi, c}; }
+};
+
+// The two formats: columns 2h, 2h+1 of a word's four (pair<h>), one byte (one)
+struct Fp8E4M3 {
+    template <bool HI>
+    static __device__ __forceinline__ f32x2 pair(uint32_t w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_amdgcn_cvt_pk_f32_fp8((int)w, HI);
+#else
+        return f32x2{0.0f, 0.0f};
+#endif
+    }
+    static __device__ __forceinline__ float one(uint32_t byte) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_amdgcn_cvt_f32_fp8((int)byte, 0);
+#else
+        return 0.0f;
+#endif
+    }
+};
+struct Fp8E5M2 {
+    template <bool HI>
+    static __device__ __forceinline__ f32x2 pair(uint32_t w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_amdgcn_cvt_pk_f32_bf8((int)w, HI);
+#else
+        return f32x2{0.0f, 0.0f};
+#endif
+    }
+    static __device__ __forceinline__ float one(uint32_t byte) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_amdgcn_cvt_f32_bf8((int)byte, 0);
+#else
+        return 0.0f;
+#endif
+    }
+};
+
+// The column body both paths share: one client's term of one column
+template <bool SCORED, bool SCALED>
+__device__ __forceinline__ float fp8_term(float x, float a, float s, float c) {
+    if constexpr (SCALED) x = x * c;
+    float t = x * a;
+    if constexpr (SCORED) t = t * s;
+    return t;
+}
+
+// One row's unit into the lane's 16 accumulators (FIRST: acc = t_0, not 0 + t_0)
+template <class F, bool SCORED, bool SCALED, bool FIRST>
+__device__ __forceinline__ void fp8_unit_add(float (&acc)[16], u32x4 v, float a, float s, float c) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const f32x2 lo = F::template pair<false>(w[k]), hi = F::template pair<true>(w[k]);
+        const float x[4] = {lo.x, lo.y, hi.x, hi.y};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float t = fp8_term<SCORED, SCALED>(x[j], a, s, c);
+            acc[4 * k + j] = FIRST ? t : acc[4 * k + j] + t;
+        }
+    }
+}
+
+// One group of U rows x C units, already loaded, into the accumulators in row order
+template <class F, int U, int C, bool SCORED, bool SCALED>
+__device__ __forceinline__ void fp8_group_add(float (&acc)[C][16], const u32x4 (&v)[U][C], const float* __restrict__ a,
+                                              const float* __restrict__ s, const float* __restrict__ sc, int64_t i) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const float ai = a[i + u], si = SCORED ? s[i + u] : 1.0f, ci = SCALED ? sc[i + u] : 1.0f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) fp8_unit_add<F, SCORED, SCALED, false>(acc[c], v[u][c], ai, si, ci);
+    }
+}
+
+// The forms of the unit fold (bits of FORM).  kFp8Ahead: two groups of loads
+// alternate, the next group's loads issued before this group's converts and
+// adds, so a wave's arithmetic runs while its own loads are in flight (the
+// loads return in order: waiting for the older group leaves the younger one
+// outstanding).  kFp8Exchange: a wave whose 64 lanes all hold a unit passes its
+// float32 results through 4 KiB of LDS of its own, so that each 16-byte store
+// instruction writes 1 KiB contiguous where the lanes' own 64 B are 64 B apart.
+constexpr int kFp8Ahead = 1, kFp8Exchange = 2;
+constexpr int kFp8Form = kFp8Ahead | kFp8Exchange;  // the product's form
+
+// The lane's C units of rows 0..N-1 of src, in row order; o0 = its first unit in out / outb
+template <class F, int U, int C, bool SCORED, bool SCALED, int FORM, class Rows>
+__device__ __forceinline__ void fold_fp8_units(Rows src, int64_t N, const float* __restrict__ a,
+                                               const float* __restrict__ s, const float* __restrict__ sc,
+                                               float divisor, float* __restrict__ out, uint16_t* __restrict__ outb,
+                                               int64_t o0, u32x4* wave_lds) {
+    float acc[C][16];
+    {
+        const auto* r = src.row(0);
+        const float a0 = a[0], s0 = SCORED ? s[0] : 1.0f, c0 = SCALED ? sc[0] : 1.0f;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            fp8_unit_add<F, SCORED, SCALED, true>(acc[c], __builtin_nontemporal_load(r + c * kBlock), a0, s0, c0);
+    }
+    int64_t i = 1;
+    if constexpr (FORM & kFp8Ahead) {
+        if (i + U <= N) {
+            u32x4 va[U][C], vb[U][C];
+            octets_ld<U, C>(va, src, i);
+            for (;;) {
+                const bool more_b = i + 2 * U <= N;
+                if (more_b) octets_ld<U, C>(vb, src, i + U);
+                __builtin_amdgcn_sched_barrier(0);  // the younger group's loads are issued ahead of these adds
+                fp8_group_add<F, U, C, SCORED, SCALED>(acc, va, a, s, sc, i);
+                i += U;
+                if (!more_b) break;
+                const bool more_a = i + 2 * U <= N;
+                if (more_a) octets_ld<U, C>(va, src, i + U);
+                __builtin_amdgcn_sched_barrier(0);
+                fp8_group_add<F, U, C, SCORED, SCALED>(acc, vb, a, s, sc, i);
+                i += U;
+                if (!more_a) break;
+            }
+        }
+    } else {
+        for (; i + U <= N; i += U) {
+            u32x4 v[U][C];
+            octets_ld<U, C>(v, src, i);
+            fp8_group_add<F, U, C, SCORED, SCALED>(acc, v, a, s, sc, i);
+        }
+    }
+    for (; i < N; ++i) {
+        const auto* r = src.row(i);
+        const float ai = a[i], si = SCORED ? s[i] : 1.0f, ci = SCALED ? sc[i] : 1.0f;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            fp8_unit_add<F, SCORED, SCALED, false>(acc[c], __builtin_nontemporal_load(r + c * kBlock), ai, si, ci);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        float q[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) q[j] = acc[c][j] / divisor;
+        const int64_t oc = o0 + (int64_t)c * kBlock;
+        // out (fp32) and outb (RNE bf16) are each optional, one of them given
+        if (out) {
+            f32x4* o4 = reinterpret_cast<f32x4*>(out) + 4 * oc;
+            bool exchanged = false;
+            if constexpr ((FORM & kFp8Exchange) != 0) {
+                // wave-uniform: all 64 lanes are here, so the wave's 64 units are 4 KiB contiguous in out
+                if (__builtin_amdgcn_ballot_w64(true) == ~0ull) {
+                    const int lane = threadIdx.x & 63;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        wave_lds[4 * lane + k] =
+                            __builtin_bit_cast(u32x4, f32x4{q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]});
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    f32x4* wave_out = o4 - 4 * lane;  // the unit of lane 0
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) st16(wave_out + 64 * k + lane, wave_lds[64 * k + lane]);
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    exchanged = true;
+                }
+            }
+            if (!exchanged) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    st16(o4 + k, __builtin_bit_cast(u32x4, f32x4{q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]}));
+            }
+        }
+        if (outb) {
+            u32x4* o8 = reinterpret_cast<u32x4*>(outb) + 2 * oc;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                u32x4 b;
+                b.x = (uint32_t)f2bf_rne(q[8 * k]) | ((uint32_t)f2bf_rne(q[8 * k + 1]) << 16);
+                b.y = (uint32_t)f2bf_rne(q[8 * k + 2]) | ((uint32_t)f2bf_rne(q[8 * k + 3]) << 16);
+                b.z = (uint32_t)f2bf_rne(q[8 * k + 4]) | ((uint32_t)f2bf_rne(q[8 * k + 5]) << 16);
+                b.w = (uint32_t)f2bf_rne(q[8 * k + 6]) | ((uint32_t)f2bf_rne(q[8 * k + 7]) << 16);
+                st16(o8 + k, b);
+            }
+        }
+    }
+}
+
+// One column, 8 rows of loads ahead of the ordered adds (a tail lane of the
+// vector path, every lane of the one-column kernel): the f32 quotient
+template <class F, bool SCORED, bool SCALED, class Rows>
+__device__ __forceinline__ float fold_column_fp8(Rows src, int64_t N, const float* __restrict__ a,
+                                                 const float* __restrict__ s, const float* __restrict__ sc,
+                                                 float divisor) {
+    float acc = fp8_term<SCORED, SCALED>(F::one(*src.row(0)), a[0], SCORED ? s[0] : 1.0f, SCALED ? sc[0] : 1.0f);
+    int64_t i = 1;
+    for (; i + 8 <= N; i += 8) {
+        uint8_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load(src.row(i + u));
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            acc = acc + fp8_term<SCORED, SCALED>(F::one(v[u]), a[i + u], SCORED ? s[i + u] : 1.0f,
+                                                 SCALED ? sc[i + u] : 1.0f);
+    }
+    for (; i < N; ++i)
+        acc = acc + fp8_term<SCORED, SCALED>(F::one(*src.row(i)), a[i], SCORED ? s[i] : 1.0f, SCALED ? sc[i] : 1.0f);
+    return acc / divisor;
+}
+
+// The vector path: rows and outputs 16-B aligned (a stacked matrix: ldx % 16 ==
+// 0 too), grid-stride over the tiles.  Src: Fp8Pitched or Fp8Table.
+template <class F, int U, int C, bool SCORED, bool SCALED, int FORM, class Src>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_fp8_gs(
+    Src src, int64_t N, int64_t P, const float* __restrict__ a, const float* __restrict__ s,
+    const float* __restrict__ sc, float divisor, float* __restrict__ out, uint16_t* __restrict__ outb,
+    int64_t ntiles) {
+    u32x4* wave_lds = nullptr;
+    if constexpr ((FORM & kFp8Exchange) != 0) {
+        __shared__ u32x4 lds[kBlock * 4];  // 64 lanes x 64 B per wave
+        wave_lds = lds + (threadIdx.x >> 6) * 256;
+    }
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        octet_tile<C, kBlock, kFp8LG>(
+            bid, P,
+            [&](int64_t o) {
+                fold_fp8_units<F, U, C, SCORED, SCALED, FORM>(src.units(o), N, a, s, sc, divisor, out, outb, o, wave_lds);
+            },
+            [&](int64_t o) {
+                fold_fp8_units<F, U, 1, SCORED, SCALED, FORM>(src.units(o), N, a, s, sc, divisor, out, outb, o, wave_lds);
+            },
+            [&](int64_t col) {
+                for (; col < P; ++col)
+                    st_column_bf16(fold_column_fp8<F, SCORED, SCALED>(src.column(col), N, a, s, sc, divisor), out, outb,
+                                   col);
+            });
+}
+
+// One lane per column: rows at any byte offset, any pitch, any output alignment
+template <class F, bool SCORED, bool SCALED, class Src>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_fp8_scalar(
+    Src src, int64_t N, int64_t P, const float* __restrict__ a, const float* __restrict__ s,
+    const float* __restrict__ sc, float divisor, float* __restrict__ out, uint16_t* __restrict__ outb) {
+    const int64_t col = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (col >= P) return;
+    st_column_bf16(fold_column_fp8<F, SCORED, SCALED>(src.column(col), N, a, s, sc, divisor), out, outb, col);
+}
+
+// ---------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------
 inline dim3 grid_for(int64_t lanes) { return dim3((unsigned)((lanes + kBlock - 1) / kBlock)); }
@@ -4621,6 +4905,82 @@ inline int f16_rows_fold(const uint16_t* const* xi, int64_t N, int64_t P, const 
             }
             return 0;
         });
+}
+
+// ---- the fp8 folds (fa_fedavg_fp8, fa_fedavg_fp8_ptrs) -------------------------
+// One geometry per entry, fixed on the host, no tuner kind.  vec: the vector
+// path (tiles of kFp8TileCols columns, balanced passes over at most
+// Src::kBlocksPerCu blocks per CU), else one column per lane.
+static_assert(kFp8TileCols == FA_FP8_TILE_COLS && kFp8U == FA_FP8_ROWS_AHEAD, "the header states the fp8 geometry");
+
+// FORM: the unit fold's form (the product's is kFp8Form; the bench library times
+// the others); blocks_per_cu: the product's is Src::kBlocksPerCu
+template <class F, int FORM, class Src>
+void launch_fp8(hipStream_t st, bool vec, Src src, int64_t N, int64_t P, const float* a, const float* s,
+                const float* c, float d, float* out, uint16_t* outb, int blocks_per_cu = Src::kBlocksPerCu) {
+    const OctetGrid g = octet_grid(P, kFp8C, -blocks_per_cu, cu_count(), kFp8LG);
+    with_scored(s != nullptr, [&](auto SC) {
+        with_scored(c != nullptr, [&](auto CS) {
+            constexpr bool kScored = decltype(SC)::value, kScaled = decltype(CS)::value;
+            if (vec)
+                hipLaunchKernelGGL((k_fedavg_fp8_gs<F, kFp8U, kFp8C, kScored, kScaled, FORM, Src>), dim3((unsigned)g.grid),
+                                   dim3(kBlock), 0, st, src, N, P, a, s, c, d, out, outb, g.tiles);
+            else
+                hipLaunchKernelGGL((k_fedavg_fp8_scalar<F, kScored, kScaled, Src>), grid_for(P), dim3(kBlock), 0, st,
+                                   src, N, P, a, s, c, d, out, outb);
+        });
+    });
+}
+template <class Src>
+int launch_fp8_fmt(int fmt, hipStream_t st, bool vec, Src src, int64_t N, int64_t P, const float* a, const float* s,
+                   const float* c, float d, float* out, uint16_t* outb) {
+    if (fmt == FA_FP8_E4M3FN) launch_fp8<Fp8E4M3, kFp8Form>(st, vec, src, N, P, a, s, c, d, out, outb);
+    else if (fmt == FA_FP8_E5M2) launch_fp8<Fp8E5M2, kFp8Form>(st, vec, src, N, P, a, s, c, d, out, outb);
+    else return fail(FA_ERR_ARG, "unknown fp8 format %d", fmt);
+    return 0;
+}
+
+// The checks of the stacked fold: *go = true to launch (false with FA_OK: nothing to fold)
+inline int fp8_fold_checks(int fmt, const uint8_t* X, int64_t N, int64_t P, int64_t ldx, const float* a,
+                           float* out_f32, uint16_t* out_bf16, bool* go) {
+    *go = false;
+    int rc = check_common(N, P, ldx, X, a, bf16_any_out(out_f32, out_bf16));
+    if (rc) return rc;
+    if (fmt != FA_FP8_E4M3FN && fmt != FA_FP8_E5M2) return fail(FA_ERR_ARG, "unknown fp8 format %d", fmt);
+    if (P == 0) { g_err[0] = 0; return FA_OK; }
+    const size_t xbytes = (size_t)(N - 1) * ldx + P;
+    if ((out_f32 && overlaps(out_f32, (size_t)P * 4, X, xbytes)) ||
+        (out_bf16 && overlaps(out_bf16, (size_t)P * 2, X, xbytes)))
+        return fail(FA_ERR_ARG, "fa_fedavg_fp8: an output overlaps the rows (the outputs are wider than the rows)");
+    *go = true;
+    return FA_OK;
+}
+inline bool fp8_vec(const uint8_t* X, int64_t ldx, const float* out_f32, const uint16_t* out_bf16) {
+    return aligned16(X) && (ldx % 16 == 0) && aligned16(out_f32) && aligned16(out_bf16);
+}
+
+inline int fp8_fold(int fmt, const uint8_t* X, int64_t N, int64_t P, int64_t ldx, const float* a, const float* s,
+                    const float* c, float divisor, float* out_f32, uint16_t* out_bf16, void* stream) {
+    bool go;
+    int rc = fp8_fold_checks(fmt, X, N, P, ldx, a, out_f32, out_bf16, &go);
+    if (!go) return rc;
+    StreamDevice on_stream_device(stream);
+    const bool vec = fp8_vec(X, ldx, out_f32, out_bf16);
+    rc = launch_fp8_fmt(fmt, (hipStream_t)stream, vec, Fp8Pitched{X, ldx}, N, P, a, s, c, divisor, out_f32, out_bf16);
+    return rc ? rc : check_launch("fa_fedavg_fp8");
+}
+
+inline int fp8_rows_fold(int fmt, const uint8_t* const* xi, int64_t N, int64_t P, const float* a, const float* s,
+                         const float* c, float divisor, int rows_aligned, float* out_f32, uint16_t* out_bf16,
+                         void* stream) {
+    if (fmt != FA_FP8_E4M3FN && fmt != FA_FP8_E5M2) return fail(FA_ERR_ARG, "unknown fp8 format %d", fmt);
+    const bool fits = !rows_aligned || (aligned16(out_f32) && aligned16(out_bf16));
+    return rows_fold("fa_fedavg_fp8_ptrs", xi, N, P, a, bf16_any_out(out_f32, out_bf16), stream,
+                     fits ? nullptr : "the vector path of the fp8 row-table fold needs 16-B aligned rows and outputs",
+                     [&](hipStream_t st) {
+                         return launch_fp8_fmt(fmt, st, rows_aligned != 0, Fp8Table{xi}, N, P, a, s, c, divisor, out_f32,
+                                               out_bf16);
+                     });
 }
 
 // ---- the float64 pair folds (fa_fold_f64, fa_fedavg_f64_ptrs) -----------------

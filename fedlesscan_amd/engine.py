@@ -40,6 +40,16 @@ _NP_TO_TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch
                 np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64,
                 np.dtype(np.float16): torch.float16}
 ROW_ALIGN = 64  # elements; row pitch multiple of 256 B for fp32
+# the OCP fp8 dtypes the library folds from the bytes themselves -> fa_fedavg_fp8's fmt
+_FP8_FORMATS = {torch.float8_e4m3fn: _lib.FA_FP8_E4M3FN, torch.float8_e5m2: _lib.FA_FP8_E5M2}
+
+
+class ScaledLayer(NamedTuple):
+    """A client's fp8 layer with its dequantisation scale, as aggregate_layers
+    (and the strategy classes' _aggregate) take it: the layer counts as
+    q.to(float32) * np.float32(scale).  Every client wraps a layer or none does."""
+    q: torch.Tensor
+    scale: float
 
 
 def default_device() -> torch.device:
@@ -423,7 +433,7 @@ def _check_matrix(X: torch.Tensor) -> tuple[int, int, int]:
 
 def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] = None, *,
                  out: Optional[torch.Tensor] = None, want_bf16: bool = False, total=None,
-                 exact: bool = True, out_bf16: Optional[torch.Tensor] = None):
+                 exact: bool = True, out_bf16: Optional[torch.Tensor] = None, scales: Optional[Sequence] = None):
     """FedAvg (scores None) / stall-aware fold over the rows of X, in row order.
 
     `total` overrides the divisor sum (used when zip() truncated the rows but
@@ -436,12 +446,20 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
     exact=False (fp32 only) opts into the split-client fold,
     fa_fedavg_f32_splitn: faster on very narrow models, deterministic, but NOT
     bit-identical to the reference (a different association of the same sum).
+    fp8 rows (float8_e4m3fn, float8_e5m2; no reference path) are upcast exactly
+    and folded in float32 with the bf16 fold's outputs; scales= (N floats,
+    rounded to float32 as the weights are) multiplies row i by scale_i before
+    its weight, with a rounding of its own.
     """
     N, P, ldx = _check_matrix(X)
     if len(weights) != N or (scores is not None and len(scores) != N):
         raise InvalidParameterShapeError(f"{N} rows but {len(weights)} weights"
                                          + ("" if scores is None else f" / {len(scores)} scores"))
     dev = X.device
+    if X.dtype in _FP8_FORMATS:
+        return _fold_fp8(X, None, weights, scores, scales, out, total, want_bf16, out_bf16)
+    if scales is not None:
+        raise InvalidParameterShapeError(f"scales are for fp8 rows, got {X.dtype}")
     st = stream_ptr(dev)
     if out_bf16 is not None and X.dtype != torch.bfloat16:
         raise InvalidParameterShapeError("out_bf16 is for bfloat16 rows")
@@ -1001,7 +1019,8 @@ def _equal_stride_view(rows, host_ptrs: np.ndarray, P: int) -> Optional[torch.Te
 
 _dtype_of = operator.attrgetter("dtype")
 # dtypes the library folds through a device table of row pointers
-_ROW_TABLE_DTYPES = (torch.float32, torch.bfloat16, torch.float16, torch.float64, torch.int32, torch.int64)
+_ROW_TABLE_DTYPES = (torch.float32, torch.bfloat16, torch.float16, torch.float64, torch.int32, torch.int64,
+                     *_FP8_FORMATS)
 _INT_ROWS = {torch.int32: "fa_fedavg_i32_ptrs", torch.int64: "fa_fedavg_i64_ptrs"}
 # dtypes whose row-table fold does not run under a stream capture: they keep the route they had before it
 _NO_CAPTURE_TABLE = (torch.float64, torch.int32, torch.int64)
@@ -1012,9 +1031,10 @@ _NO_CAPTURE_TABLE = (torch.float64, torch.int32, torch.int64)
 # row table (counted as the float64 ones), promoted stacked folds that read
 # the narrow rows (fa_fedavg_widen; nothing else counts there), layers folded
 # through a widening row table (fa_fedavg_widen_ptrs, or each layer of a
-# fa_fedavg_widen_layers launch) and those launches (they move no other counter)
+# fa_fedavg_widen_layers launch) and those launches (they move no other counter),
+# fp8 folds (fa_fedavg_fp8 and fa_fedavg_fp8_ptrs: one per layer of a model)
 stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0, "layer_table_folds": 0, "rows_int_folds": 0,
-         "widened_folds": 0, "widened_row_folds": 0, "widened_table_folds": 0}
+         "widened_folds": 0, "widened_row_folds": 0, "widened_table_folds": 0, "fp8_folds": 0}
 
 
 class RowSet:
@@ -1028,9 +1048,9 @@ class RowSet:
       - other fp32 rows get a device table of row pointers for
         fa_fedavg_f32_ptrs_aligned (every row 16-B aligned) or
         fa_fedavg_f32_ptrs (any alignment);
-      - other bfloat16 / float16 / float64 rows get the same table for
-        fa_fedavg_bf16_ptrs / fa_fedavg_f16_ptrs / fa_fedavg_f64_ptrs
-        (`aligned` picks the kernels);
+      - other bfloat16 / float16 / float64 / fp8 rows get the same table for
+        fa_fedavg_bf16_ptrs / fa_fedavg_f16_ptrs / fa_fedavg_f64_ptrs /
+        fa_fedavg_fp8_ptrs (`aligned` picks the kernels);
       - other int32 / int64 rows get the same table for fa_fedavg_i32_ptrs /
         fa_fedavg_i64_ptrs, which fold_rows takes where int_row_factors
         accepts the fold.
@@ -1113,6 +1133,71 @@ def _fold_rows_bf16(rs: "RowSet", weights, scores, out, total, want_bf16, out_bf
         _lib.call("fa_fedavg_bf16_ptrs_hostf", rs.ptrs.data_ptr(), rs.N, P, *f.host(), float(f.div),
                   int(aligned), _ptr(out), _ptr(outb), st)
     stats["rows16_folds"] += 1
+    if dst is not None and dst is not out:
+        dst.reshape(-1)[:P].copy_(out)
+        out = dst
+    if dstb is not None and dstb is not outb:
+        dstb.reshape(-1)[:P].copy_(outb)
+        outb = dstb
+    if want_bf16:
+        return out, outb
+    if out_bf16 is not None:
+        return outb if out is None else (out, outb)
+    return out
+
+
+def _fold_fp8(X: Optional[torch.Tensor], rs: Optional["RowSet"], weights, scores, scales, out, total, want_bf16,
+              out_bf16):
+    """fp8 rows, a stacked [N, P] matrix X (fa_fedavg_fp8) or the row table of
+    rs (fa_fedavg_fp8_ptrs): float32 factors and scales in ONE staged upload,
+    the bf16 fold's outputs.  The outputs are wider than the rows, so one that
+    shares bytes with a row is folded into a fresh buffer and copied."""
+    if torch.cuda.is_current_stream_capturing():
+        raise InvalidParameterShapeError("the fp8 fold does not run under stream capture "
+                                         "(its factors and scales are staged by a copy the graph would not own)")
+    if X is not None:
+        N, P, ldx = _check_matrix(X)
+        dev, fmt = X.device, _FP8_FORMATS[X.dtype]
+    else:
+        N, P, dev, fmt = rs.N, rs.P, rs.device, _FP8_FORMATS[rs.dtype]
+    if scales is not None and len(scales) != N:
+        raise InvalidParameterShapeError(f"{N} rows but {len(scales)} scales")
+    _check_out("out", out, torch.float32, P)
+    _check_out("out_bf16", out_bf16, torch.bfloat16, P)
+
+    def clash(t) -> bool:
+        if t is None or P == 0:
+            return False
+        if X is None:
+            return rs.overlaps(t)
+        lo, hi = t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+        return lo < X.data_ptr() + (N - 1) * ldx + P and X.data_ptr() < hi
+
+    dst, dstb = out, out_bf16
+    if clash(out):
+        out = None
+    outb = None if clash(out_bf16) else out_bf16
+    if outb is None and (want_bf16 or out_bf16 is not None):
+        outb = torch.empty(P, dtype=torch.bfloat16, device=dev)
+    if out is None and (dst is not None or outb is None or want_bf16):
+        out = torch.empty(P, dtype=torch.float32, device=dev)
+    f = Factors.weak_f32(weights, scores, total) or Factors(weights, scores, _F32, total=total)
+    parts = [f.a] if f.s is None else [f.a, f.s]
+    if scales is not None:
+        c = weak_f32(scales)
+        parts.append(c if c is not None else round_scalars(scales, _F32))
+    staged = stage_factors(parts, dev)
+    a, s = staged[0], (staged[1] if f.s is not None else None)
+    c = staged[-1] if scales is not None else None
+    if X is not None:
+        _lib.call("fa_fedavg_fp8", fmt, X.data_ptr(), N, P, ldx, a.data_ptr(), _ptr(s), _ptr(c), float(f.div),
+                  _ptr(out), _ptr(outb), stream_ptr(dev))
+    else:
+        aligned = (rs.aligned and (out is None or out.data_ptr() % 16 == 0)
+                   and (outb is None or outb.data_ptr() % 16 == 0))
+        _lib.call("fa_fedavg_fp8_ptrs", fmt, rs.ptrs.data_ptr(), N, P, a.data_ptr(), _ptr(s), _ptr(c), float(f.div),
+                  int(aligned), _ptr(out), _ptr(outb), stream_ptr(dev))
+    stats["fp8_folds"] += 1
     if dst is not None and dst is not out:
         dst.reshape(-1)[:P].copy_(out)
         out = dst
@@ -1220,18 +1305,28 @@ def _fold_rows_widen(rs: "RowSet", kind: int, f: Factors, out):
 
 def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
               out: Optional[torch.Tensor] = None, total=None, want_bf16: bool = False,
-              out_bf16: Optional[torch.Tensor] = None):
+              out_bf16: Optional[torch.Tensor] = None, scales: Optional[Sequence] = None):
     """The fold over separately allocated 1-D CUDA rows (no stacking copy for
     fp32, bfloat16, float16 / float64 rows whose result stays in their dtype,
     int32 / int64 rows whose products stay in their dtype: int_row_factors, and
     rows numpy promotes as a whole where a widening kernel converts them on
     load: widen_factors).  `rows` is a
     RowSet (prepared once, reusable) or a sequence of tensors (a RowSet is
-    built for this call).  want_bf16 / out_bf16: as fold_stacked (bf16 rows)."""
+    built for this call).  want_bf16 / out_bf16: as fold_stacked (bf16 and
+    fp8 rows); scales: as fold_stacked (fp8 rows, folded through their own row
+    table)."""
     rs = rows if isinstance(rows, RowSet) else RowSet(rows)
     if len(weights) != rs.N or (scores is not None and len(scores) != rs.N):
         raise InvalidParameterShapeError(f"{rs.N} rows but {len(weights)} weights"
                                          + ("" if scores is None else f" / {len(scores)} scores"))
+    if rs.dtype in _FP8_FORMATS:
+        if rs.view is not None or rs.P == 0:
+            # rows of one allocation at a fixed pitch (or no columns): the stacked fold, no pointer table
+            X = rs.view if rs.view is not None else torch.empty((rs.N, 0), dtype=rs.dtype, device=rs.device)
+            return _fold_fp8(X, None, weights, scores, scales, out, total, want_bf16, out_bf16)
+        return _fold_fp8(None, rs, weights, scores, scales, out, total, want_bf16, out_bf16)
+    if scales is not None:
+        raise InvalidParameterShapeError(f"scales are for fp8 rows, got {rs.dtype}")
     if out_bf16 is not None and rs.dtype != torch.bfloat16:
         raise InvalidParameterShapeError("out_bf16 is for bfloat16 rows")
     if rs.dtype == torch.bfloat16:
@@ -1624,6 +1719,27 @@ def _rows_route(dt, fp32_result: bool, w, sc, total, where: torch.device, dev) -
             and widen_factors(_TORCH_TO_NP[dt], w, sc, total) is not None)
 
 
+def _unwrap_scaled(parameters, n_eff):
+    """aggregate_layers' parameters with every ScaledLayer replaced by its
+    tensor, and {layer index: the clients' scales of that layer}; the
+    parameters themselves and {} when no layer is wrapped."""
+    if not any(isinstance(x, ScaledLayer) for p in parameters[:n_eff] for x in p):
+        return parameters, {}
+    L = min(len(p) for p in parameters[:n_eff])
+    plain = [list(p[:L]) for p in parameters[:n_eff]]
+    scales = {}
+    for li in range(L):
+        wrapped = [isinstance(p[li], ScaledLayer) for p in plain]
+        if not any(wrapped):
+            continue
+        if not all(wrapped):
+            raise InvalidParameterShapeError(f"layer {li}: every client gives a ScaledLayer or none does")
+        scales[li] = [p[li].scale for p in plain]
+        for p in plain:
+            p[li] = p[li].q
+    return plain, scales
+
+
 def _multi(devices) -> Optional[list]:
     """The device list of a multi-GPU call, or None for a one-GPU call."""
     if devices is None:
@@ -1648,6 +1764,11 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
     devices: several GPUs of this process (multigpu.py): host float32 layers
     are folded one column bucket per GPU, bit-identical to one GPU.  Other
     layer groups (device tensors, other dtypes) run on the first of them.
+
+    Device fp8 layers (float8_e4m3fn, float8_e5m2) fold one layer at a time
+    through their row table, where they lie; such a layer may be given as
+    ScaledLayer(q, scale) by every client: client i's rows then count as
+    q_i.to(float32) * np.float32(scale_i) (fold_stacked's scales=).
     """
     multi = _multi(devices)
     if multi is not None and device is None:
@@ -1659,9 +1780,17 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
     if n_eff == 0:
         return []
     total_weights = list(weights)
+    parameters, layer_scales = _unwrap_scaled(parameters, n_eff)
     L, shapes, dtypes = _layer_meta(parameters, n_eff)
     if L == 0:
         return []
+    for li in layer_scales:
+        if dtypes[li] not in _FP8_FORMATS:
+            raise InvalidParameterShapeError(f"layer {li}: a ScaledLayer holds fp8 rows, got {dtypes[li]}")
+    for li, dt in enumerate(dtypes):
+        if isinstance(dt, tuple) and any(d in _FP8_FORMATS for d in dt):
+            raise InvalidParameterShapeError(f"layer {li}: fp8 rows fold only with rows of their own format, every "
+                                             f"client's alike; got {sorted(set(map(str, dt)))}")
     on_device = isinstance(parameters[0][0], torch.Tensor)
     dev = device or (parameters[0][0].device if on_device else default_device())
     w = list(weights[:n_eff])
@@ -1673,6 +1802,13 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
     for _, lis in groups.items():
         sizes = [int(np.prod(shapes[li])) if len(shapes[li]) else 1 for li in lis]
         P = sum(sizes)
+        if dtypes[lis[0]] in _FP8_FORMATS:
+            # device fp8 layers: each folds from the clients' own bytes through its row table
+            for li in lis:
+                rows = [parameters[i][li].reshape(-1) for i in range(n_eff)]
+                outs[li] = fold_rows(rows, w, sc, total=sum(total_weights),
+                                     scales=layer_scales.get(li)).reshape(shapes[li])
+            continue
         fp32_result = result_dtype(np.dtype(np.float32), total_weights, sc) == np.float32
         if isinstance(dtypes[lis[0]], tuple):
             # rows of several dtypes: one stacked matrix per run of rows of one dtype,

@@ -668,6 +668,53 @@ int fa_fedavg_widen_layers(int kind, const void* const* xi, const fa_layer_plan*
                            int64_t tiles, int units, const void* a, const void* s, double divisor, void* out,
                            void* stream);
 
+/* ---- fp8 client rows with a scale per client (new symbols, ABI still 7) ------
+ * Client updates quantised to 8-bit floating point, one dequantisation scale
+ * per client tensor, folded from the bytes themselves: no float32 copy of the
+ * rows exists at any time.  No reference path; as the bf16 fold it is defined
+ * as the exact upcast followed by the float32 fold.  fmt names the OCP format:
+ *   FA_FP8_E4M3FN  torch.float8_e4m3fn: no infinities, NaN = 0x7f / 0xff
+ *   FA_FP8_E5M2    torch.float8_e5m2: IEEE-like (inf, NaN, subnormals)
+ * Per client i and column p, a, s, c [device, N float32] (s NULL for FedAvg, c
+ * NULL when the rows carry no scale: then no multiply is made):
+ *   x   = f32(q_i[p])                 exact, -0 and subnormals included
+ *   x   = fl32(x * c_i)               only with c
+ *   t   = fl32(x * a_i);  t = fl32(t * s_i) with s
+ *   acc = t_0;  acc = fl32(acc + t_i), i = 1..N-1 in client order, no FMA
+ *   out = fl32(acc / divisor)         IEEE divide
+ * -- bit for bit fa_fedavg_f32 over the rows f32(q_i) * c_i.  c_i * a_i is
+ * never formed.  out_f32 [P] and out_bf16 [P] (its RNE bf16 copy) are each
+ * optional, one of them given, as fa_fedavg_bf16.
+ *   fa_fedavg_fp8: X a stacked [N][ldx] byte matrix.  X and the outputs 16-B
+ *     aligned with ldx % 16 == 0 take the vector path; anything else one
+ *     column per lane.  No output may overlap X (they are wider than the
+ *     rows) -> FA_ERR_ARG.
+ *   fa_fedavg_fp8_ptrs: xi a [device] array of N [device] row pointers, as
+ *     fa_fedavg_bf16_ptrs: rows_aligned != 0 promises 16-B aligned rows and
+ *     outputs (an output off 16 B -> FA_ERR_ARG); with 0 rows at any byte
+ *     offset, one column per lane.  No output may overlap a row.
+ * The same bits with either path and either entry.  One fixed geometry, no
+ * tuner kind: a 16-byte load is 16 columns of one row; a lane owns 2 such
+ * units 256 lanes apart with 8 rows of loads ahead of the ordered adds, so a
+ * tile is FA_FP8_TILE_COLS columns; tiles are walked grid-stride in balanced
+ * passes over at most two blocks per CU; the next 8 rows are loaded while
+ * these fold, and a wave whose lanes all hold a unit exchanges its float32
+ * results through LDS so that each store instruction writes 1 KiB
+ * contiguous; the P % 16 trailing columns fold in one lane.  Argument checks and status codes as fa_fedavg_bf16 /
+ * fa_fedavg_bf16_ptrs; an unknown fmt -> FA_ERR_ARG.  Neither allocates nor
+ * synchronises.  Not covered: host rows, the layer tables, the sharded step,
+ * a tuner kind, the fnuz formats, fp8 output, block scales. */
+#define FA_FP8_E4M3FN 0
+#define FA_FP8_E5M2 1
+#define FA_FP8_TILE_COLS 8192
+#define FA_FP8_ROWS_AHEAD 8
+int fa_fedavg_fp8(int fmt, const uint8_t* X, int64_t N, int64_t P, int64_t ldx,
+                  const float* a, const float* s, const float* c, float divisor,
+                  float* out_f32, uint16_t* out_bf16, void* stream);
+int fa_fedavg_fp8_ptrs(int fmt, const uint8_t* const* xi, int64_t N, int64_t P,
+                       const float* a, const float* s, const float* c, float divisor, int rows_aligned,
+                       float* out_f32, uint16_t* out_bf16, void* stream);
+
 /* ---- host staging: page-locked documents and direct DMA ---------------------
  * A result store that keeps documents in page-locked memory lets the ingest
  * DMA each client's layers straight from the document into the device chunk,

@@ -107,6 +107,16 @@ int fa_fedavg_bf16_ptrs_form(const uint16_t* const* xi, int64_t N, int64_t P, co
                              int form);
 int fa_fedavg_f16_ptrs_form(const uint16_t* const* xi, int64_t N, int64_t P, const uint16_t* a, const uint16_t* s,
                             uint16_t divisor, int rows_aligned, uint16_t* out, void* stream, int form);
+/* The vector path of fa_fedavg_fp8 over e4m3fn rows in one form of the unit
+ * fold over a grid of blocks_per_cu (>= 1) blocks per CU, balanced passes:
+ * form bit 0 = the next row group's loads issued ahead of this group's adds,
+ * bit 1 = float32 results exchanged through LDS so that every store
+ * instruction writes 1 KiB contiguous; form 0 is the plain tile.  The same bits
+ * in every form.  X and the outputs 16-B aligned, ldx % 16 == 0, else
+ * FA_ERR_ARG; the other checks as fa_fedavg_fp8.  tools/fp8_bench.py --forms. */
+int fa_fedavg_fp8_form(const uint8_t* X, int64_t N, int64_t P, int64_t ldx, const float* a, const float* s,
+                       const float* c, float divisor, float* out_f32, uint16_t* out_bf16, void* stream, int form,
+                       int blocks_per_cu);
 /* The layer-table folds (fa_fedavg_*_layers) with the units per lane of the
  * caller's plan (fa_layers_plan with units = 1, 2 or 4) and a cap on the grid
  * (grid_cap > 0: at most that many blocks, so small models take several

@@ -1,0 +1,212 @@
+"""GPU parity of the fp8 folds (fa_fedavg_fp8, fa_fedavg_fp8_ptrs) through
+engine.fold_stacked, engine.fold_rows and the strategy classes.
+
+The specification is the upcast on the CPU: the committed float32 oracle over
+q.cpu().to(float32) times np.float32(scale), formed in numpy float32.  Results
+are compared as uint32 bit patterns (NaN positions by isnan); no tolerance.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+from fedlesscan_amd import _lib, synth
+from oracle import fedavg_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+T, U = _lib.FA_FP8_TILE_COLS, _lib.FA_FP8_ROWS_AHEAD  # the tile's columns, the rows of loads ahead
+FMTS = {"e4m3fn": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
+LAYOUTS = ["stacked", "pitched", "table", "table_odd_row"]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda", 0)
+
+
+@functools.lru_cache(maxsize=None)
+def _bytes(fmt: str, N: int, P: int) -> np.ndarray:
+    """[N, P] uniformly drawn bytes, the format's NaN / Inf encodings replaced by zero."""
+    b = np.random.default_rng(1000 * N + P).integers(0, 256, size=(N, P), dtype=np.uint8)
+    special = (b & 0x7F) == 0x7F if fmt == "e4m3fn" else (b & 0x7C) == 0x7C
+    b[special] = 0
+    b.setflags(write=False)
+    return b
+
+
+def _factors(N, scored, scaled):
+    w = synth.cardinalities(7, N)
+    sc = [(r + 1) / 11 for r in synth.round_ids(7, N, 10, 2)] if scored else None
+    scales = [float(x) for x in np.random.default_rng(N).uniform(0.01, 2.0, N)] if scaled else None
+    return w, sc, scales
+
+
+def _oracle(fmt, b, w, sc, scales):
+    """(float32 result, its RNE bf16 bits) of the float32 oracle over the rows upcast on the CPU."""
+    X = torch.from_numpy(np.array(b)).view(FMTS[fmt]).to(torch.float32).numpy()
+    with np.errstate(all="ignore"):
+        if scales is not None:
+            X = X * np.array([np.float32(c) for c in scales], dtype=np.float32)[:, None]
+        assert X.dtype == np.float32
+        e = O.fedavg_stacked(X, w, sc)
+    assert e.dtype == np.float32
+    return e, synth.f32_to_bf16_bits(e)
+
+
+@functools.lru_cache(maxsize=None)
+def _expect(fmt, N, P, scored, scaled):
+    return _oracle(fmt, _bytes(fmt, N, P), *_factors(N, scored, scaled))
+
+
+def _rows(b: np.ndarray, fmt, layout, dev):
+    """The byte rows on the device: a stacked matrix (tight, or at a pitch of
+    whole units above P), or a list of separately placed rows (16-B aligned, or
+    the middle one a byte off)."""
+    N, P = b.shape
+    if layout in ("stacked", "pitched"):
+        ld = P if layout == "stacked" else (P + 15) // 16 * 16 + 16
+        buf = torch.zeros((N, ld), dtype=torch.uint8, device=dev)
+        buf[:, :P] = torch.from_numpy(np.array(b)).to(dev)
+        return buf.view(FMTS[fmt])[:, :P]
+    pitch = (P + 15) // 16 * 16 + 32  # never a constant stride: each row in a buffer of its own
+    rows = []
+    for i in range(N):
+        off = 1 if (layout == "table_odd_row" and i == N // 2) else 0
+        buf = torch.zeros(pitch + 16 * (i % 3), dtype=torch.uint8, device=dev)
+        buf[off:off + P] = torch.from_numpy(np.array(b[i])).to(dev)
+        rows.append(buf[off:off + P].view(FMTS[fmt]))
+    return rows
+
+
+def _fold(rows, *args, **kw):
+    from fedlesscan_amd import engine
+    return (engine.fold_rows if isinstance(rows, list) else engine.fold_stacked)(rows, *args, **kw)
+
+
+def _same(got, exp, what):
+    """got: a float32 or bfloat16 CUDA tensor; exp: (float32, bf16 bits)."""
+    if got.dtype == torch.bfloat16:
+        g = got.view(torch.int16).cpu().numpy().view(np.uint16).astype(np.uint32) << 16
+        e = exp[1].astype(np.uint32) << 16
+    else:
+        assert got.dtype == torch.float32
+        g, e = got.cpu().numpy().view(np.uint32), exp[0].view(np.uint32)
+    assert g.shape == e.shape, what
+    gn, en = np.isnan(g.view(np.float32)), np.isnan(e.view(np.float32))
+    assert np.array_equal(gn, en), f"{what}: NaN positions"
+    bad = np.flatnonzero((g != e) & ~en)
+    assert bad.size == 0, f"{what}: {bad.size} columns differ, first {bad[:4]}: {g[bad[:4]]} != {e[bad[:4]]}"
+
+
+# ---------------------------------------------------------------------------
+# 1. all 256 byte values of each format: the conversion itself
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("layout", ["stacked", "table", "table_odd_row"])
+@pytest.mark.parametrize("w, scales", [([1], None), ([1, 2, 0], None), ([1, 2, 0], [0.25, 1.7, 3.0])])
+@pytest.mark.parametrize("fmt", list(FMTS))
+def test_every_byte_value(dev, fmt, w, scales, layout):
+    N = len(w)
+    b = np.stack([np.roll(np.arange(256, dtype=np.uint8), 85 * i) for i in range(N)])
+    exp = _oracle(fmt, b, w, None, scales)
+    assert np.isnan(exp[0]).sum() < 32 and np.unique(exp[0][np.isfinite(exp[0])]).size > 100
+    _same(_fold(_rows(b, fmt, layout, dev), w, scales=scales), exp, "float32")
+    _same(_fold(_rows(b, fmt, layout, dev), w, scales=scales, want_bf16=True)[1], exp, "bf16")
+
+
+def test_every_byte_value_one_column_stacked(dev):
+    """The stacked entry's one-lane-per-column path: the matrix starts a byte off."""
+    for fmt in FMTS:
+        b = np.stack([np.roll(np.arange(256, dtype=np.uint8), 85 * i) for i in range(3)])
+        buf = torch.zeros(3 * 272 + 1, dtype=torch.uint8, device=dev)
+        X = buf[1:].view(3, 272)[:, :256]
+        X.copy_(torch.from_numpy(b).to(dev))
+        _same(_fold(X.view(FMTS[fmt]), [1, 2, 0], scales=[0.25, 1.7, 3.0]),
+              _oracle(fmt, b, [1, 2, 0], None, [0.25, 1.7, 3.0]), fmt)
+
+
+# ---------------------------------------------------------------------------
+# 2. shape edges: columns around a unit and a tile, rows around the row group
+# ---------------------------------------------------------------------------
+SHAPES = [(1, 1), (2, 15), (U - 1, 16), (U, 17), (U + 1, T - 1), (2 * U + 1, T), (33, T + 1), (U + 1, 2 * T + 16 + 5),
+          (1, T + 1), (2, 2 * T + 16 + 5), (U, T - 1), (33, 17)]
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("N, P", SHAPES)
+@pytest.mark.parametrize("scaled", [False, True])
+@pytest.mark.parametrize("scored", [False, True])
+@pytest.mark.parametrize("fmt", list(FMTS))
+def test_shape_edges(dev, fmt, scored, scaled, N, P, layout):
+    exp = _expect(fmt, N, P, scored, scaled)
+    assert np.isfinite(exp[0]).all() and (exp[0] != 0).any()
+    w, sc, scales = _factors(N, scored, scaled)
+    rows = _rows(_bytes(fmt, N, P), fmt, layout, dev)
+    _same(_fold(rows, w, sc, scales=scales), exp, "float32 alone")
+    ob = torch.zeros(P + 8, dtype=torch.bfloat16, device=dev)
+    got = _fold(rows, w, sc, scales=scales, out_bf16=ob[:P])
+    assert got.data_ptr() == ob.data_ptr() and not ob[P:].any()
+    _same(got, exp, "bf16 alone")
+    f, h = _fold(rows, w, sc, scales=scales, want_bf16=True)
+    _same(f, exp, "float32 of both")
+    _same(h, exp, "bf16 of both")
+
+
+# ---------------------------------------------------------------------------
+# 3. several tiles per block of the grid-stride walk
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("layout", ["pitched", "table"])
+@pytest.mark.parametrize("fmt", list(FMTS))
+def test_several_tiles_per_block(dev, fmt, layout):
+    N, P = 3, 3 * torch.cuda.get_device_properties(dev).multi_processor_count * T + 37
+    w, sc, scales = _factors(N, True, True)
+    b = _bytes(fmt, N, P)
+    _same(_fold(_rows(b, fmt, layout, dev), w, sc, scales=scales), _oracle(fmt, b, w, sc, scales), layout)
+
+
+# ---------------------------------------------------------------------------
+# 4. the public interface
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("stall_aware", [False, True])
+def test_strategy_classes_fold_scaled_fp8_models(dev, stall_aware):
+    from fedlesscan_amd import FedAvgAggregator, StallAwareAggregator, engine
+    sizes, n = [(10,), (25, 32), (50, 1024)], 5
+    w, _, _ = _factors(n, False, False)
+    feats = [{"round_id": r} for r in synth.round_ids(7, n, 10, 2)]
+    sc = O.score_clients(feats, 10) if stall_aware else None
+    fmt = "e4m3fn"
+    bs = [[_bytes(fmt, n + li, int(np.prod(shp)))[i] for li, shp in enumerate(sizes)] for i in range(n)]
+    scales = [[0.5 + 0.37 * i + 0.11 * li for li in range(len(sizes))] for i in range(n)]
+    params = [[engine.ScaledLayer(torch.from_numpy(np.array(bs[i][li])).to(dev).view(FMTS[fmt]).reshape(shp),
+                                  scales[i][li]) for li, shp in enumerate(sizes)] for i in range(n)]
+    before = engine.stats["fp8_folds"]
+    if stall_aware:
+        outs = StallAwareAggregator(10, None)._aggregate(feats, params, w)
+    else:
+        outs = FedAvgAggregator()._aggregate(params, w)
+    assert engine.stats["fp8_folds"] == before + len(sizes)
+    for li, shp in enumerate(sizes):
+        exp = _oracle(fmt, np.stack([bs[i][li] for i in range(n)]), w, sc, [scales[i][li] for i in range(n)])
+        assert tuple(outs[li].shape) == shp
+        _same(outs[li].reshape(-1), exp, f"layer {li}")
+
+
+def test_scales_and_capture_are_refused(dev):
+    from fedlesscan_amd import InvalidParameterShapeError, engine
+    X32 = torch.ones((2, 64), dtype=torch.float32, device=dev)
+    with pytest.raises(InvalidParameterShapeError, match="scales"):
+        engine.fold_stacked(X32, [1, 2], scales=[1.0, 2.0])
+    with pytest.raises(InvalidParameterShapeError, match="scales"):
+        engine.fold_rows([X32[0], X32[1].clone()], [1, 2], scales=[1.0, 2.0])
+    X8 = _rows(_bytes("e5m2", 2, 64), "e5m2", "stacked", dev)
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    g = torch.cuda.CUDAGraph()
+    with pytest.raises(InvalidParameterShapeError, match="capture"):
+        with torch.cuda.graph(g, stream=side):
+            engine.fold_stacked(X8, [1, 2])
+    torch.cuda.synchronize()
+    _same(engine.fold_stacked(X8, [1, 2]), _oracle("e5m2", _bytes("e5m2", 2, 64), [1, 2], None, None), "afterwards")
