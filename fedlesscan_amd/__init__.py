@@ -18,4 +18,4 @@ from .aggregator import (  # noqa: F401,E402
     StreamStallAwareAggregator,
     UnknownCardinalityError,
 )
-from .engine import ScaledLayer  # noqa: F401,E402
+from .engine import MXLayer, ScaledLayer  # noqa: F401,E402

@@ -36,6 +36,9 @@ FA_OK, FA_ERR_ARG, FA_ERR_NO_CLIENTS, FA_ERR_SHAPE, FA_ERR_HIP = range(5)
 # fa_fedavg_fp8's formats (FA_FP8_* of the header) and its tile: columns, rows of loads ahead
 FA_FP8_E4M3FN, FA_FP8_E5M2 = range(2)
 FA_FP8_TILE_COLS, FA_FP8_ROWS_AHEAD = 8192, 8
+# fa_fedavg_mx's formats (FA_MX_* of the header), its tile's columns, the rows of loads ahead per format
+FA_MX_E4M3, FA_MX_E5M2, FA_MX_E2M1 = range(3)
+FA_MX_TILE_COLS, FA_MX_ROWS_AHEAD_FP8, FA_MX_ROWS_AHEAD_FP4 = 8192, 8, 16
 
 _i64 = ctypes.c_int64
 _vp = ctypes.c_void_p
@@ -106,6 +109,8 @@ _PROTOS = {
     "fa_fedavg_widen_layers": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _f64, _vp, _vp]),
     "fa_fedavg_fp8": (_int, [_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
     "fa_fedavg_fp8_ptrs": (_int, [_int, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _vp, _vp]),
+    "fa_fedavg_mx": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "fa_fedavg_mx_ptrs": (_int, [_int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _vp, _vp]),
     "fa_npz_index":(_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _int]),
     "fa_crc32": (_int, [_vp, _i64, ctypes.c_uint32, _int, ctypes.POINTER(ctypes.c_uint32)]),
     "fa_pack": (_int, [_vp, _vp, _vp, _vp, _i64, _int]),
@@ -175,6 +180,7 @@ _BENCH_PROTOS = {
     "fa_fedavg_bf16_ptrs_form": (_int, [_vp, _i64, _i64, _vp, _vp, _f32, _int, _vp, _vp, _vp, _int]),
     "fa_fedavg_f16_ptrs_form": (_int, [_vp, _i64, _i64, _vp, _vp, ctypes.c_uint16, _int, _vp, _vp, _int]),
     "fa_fedavg_fp8_form": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _int, _int]),
+    "fa_fedavg_mx_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _int, _int]),
     "fa_fedavg_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp, _vp]),
     "fa_fedavg_int_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp]),
     "fa_fedavg_widen_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp]),

@@ -283,6 +283,18 @@ int fa_fedavg_fp8_ptrs(int fmt, const uint8_t* const* xi, int64_t N, int64_t P, 
     return fp8_rows_fold(fmt, xi, N, P, a, s, c, divisor, rows_aligned, out_f32, out_bf16, stream);
 }
 
+int fa_fedavg_mx(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
+                 const float* a, const float* s, const float* c, float divisor, float* out_f32, uint16_t* out_bf16,
+                 void* stream) {
+    return mx_fold(fmt, X, E, N, P, ldx, lde, a, s, c, divisor, out_f32, out_bf16, stream);
+}
+
+int fa_fedavg_mx_ptrs(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, int64_t N, int64_t P,
+                      const float* a, const float* s, const float* c, float divisor, int rows_aligned, float* out_f32,
+                      uint16_t* out_bf16, void* stream) {
+    return mx_rows_fold(fmt, xi, ei, N, P, a, s, c, divisor, rows_aligned, out_f32, out_bf16, stream);
+}
+
 // ---- one launch per exchange step (struct fa_rounds: peer_exchange.hpp) ------
 
 int fa_rounds_create(fa_rounds** r, int device) {

@@ -685,6 +685,26 @@ int fa_fedavg_fp8_form(const uint8_t* X, int64_t N, int64_t P, int64_t ldx, cons
     }
     return check_launch("fa_fedavg_fp8_form");
 }
+int fa_fedavg_mx_form(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
+                      const float* a, const float* s, const float* c, float divisor, float* out_f32,
+                      uint16_t* out_bf16, void* stream, int form, int blocks_per_cu) {
+    bool go;
+    const int rc = mx_fold_checks(fmt, X, E, N, P, ldx, lde, a, out_f32, out_bf16, &go);
+    if (!go) return rc;
+    if (blocks_per_cu < 1 || !mx_vec(X, ldx, out_f32, out_bf16))
+        return fail(FA_ERR_ARG, "MX form %d over %d blocks per CU: aligned rows and outputs", form, blocks_per_cu);
+    StreamDevice on_stream_device(stream);
+    const MxPitched src{X, E, ldx, lde};
+    hipStream_t st = (hipStream_t)stream;
+    switch (form) {
+        case 1: launch_mx_fmt<1>(fmt, st, true, src, N, P, a, s, c, divisor, out_f32, out_bf16, blocks_per_cu); break;
+        case 2: launch_mx_fmt<2>(fmt, st, true, src, N, P, a, s, c, divisor, out_f32, out_bf16, blocks_per_cu); break;
+        case 3: launch_mx_fmt<3>(fmt, st, true, src, N, P, a, s, c, divisor, out_f32, out_bf16, blocks_per_cu); break;
+        case 7: launch_mx_fmt<7>(fmt, st, true, src, N, P, a, s, c, divisor, out_f32, out_bf16, blocks_per_cu); break;
+        default: return fail(FA_ERR_ARG, "MX form %d: forms 1, 2, 3 and 7", form);
+    }
+    return check_launch("fa_fedavg_mx_form");
+}
 int fa_fedavg_layers_form(int dtype, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
                           int64_t tiles, int units, int64_t grid_cap, const void* a, const void* s, double divisor,
                           void* out, void* out_bf16, void* stream) {

@@ -3392,6 +3392,359 @@ FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_fp8_scalar(
 }
 
 // ---------------------------------------------------------------------------
+// MX block-scaled rows (OCP Microscaling: MXFP8 e4m3 / e5m2 bytes, MXFP4 e2m1
+// nibbles; one E8M0 scale byte per 32 flat elements; fa_fedavg_mx,
+// fa_fedavg_mx_ptrs; DESIGN.md 2 and 5 MX).  Per client i and column p
+//   x = f32(q_i[p]);  x = fl(x * 2^(e_i[p >> 5] - 127))  (NaN for e = 255)
+//   x = fl(x * c_i) [scaled];  t = fl(x * a_i);  t = fl(t * s_i) [scored]
+//   acc = t_0;  acc = fl(acc + t_i) in row order;  out = fl(acc / divisor)
+// Geometry: a lane owns ONE MX block: 32 columns, 32 float32 accumulators and
+// one scale byte per row.  Its block of a row is 32 contiguous bytes (fp8: two
+// adjacent 16-byte loads) or 16 (fp4: one load); a wave's lanes read 2 KiB /
+// 1 KiB of the row and 64 contiguous scale bytes.  A tile is
+//   kMxTileCols = kBlock * 32 = 8192 columns,
+// walked grid-stride over balanced passes of at most two blocks per CU.  The
+// scale byte is loaded by its lane, in the load group of the row's data, so it
+// rides the same rows-ahead pipeline: F::kU rows per group (fp8 8, fp4 16: the
+// same 64 VGPRs of data per group), two groups alternating.  A full wave passes
+// its 64 x 32 float32 results through 8 KiB of LDS of its own, so each store
+// instruction writes 1 KiB contiguous where the lanes' own 128 B are 128 B apart.
+// Scale application, bit 2 of FORM: kMxHwScale converts and scales in one
+// instruction (v_cvt_scalef32_pk_f32_fp8 / _bf8 / _fp4, the byte as the
+// exponent field of the scale operand); without it the convert is the plain one
+// (fp4: the scaled convert with a scale of 1.0) and the scale is a float32
+// built in registers and applied by an IEEE multiply.  DESIGN.md 5 MX says
+// which one the product uses and why.
+// ---------------------------------------------------------------------------
+constexpr int kMxLG = 5;
+constexpr int kMxTileCols = kBlock << kMxLG;
+constexpr int kMxAhead = 1, kMxExchange = 2, kMxHwScale = 4;
+
+// The scale byte as the float32 the contract names: 2^(e-127), e = 0 the
+// subnormal 2^-127, e = 255 a quiet NaN
+__device__ __forceinline__ float mx_scale(uint32_t e) {
+    return __uint_as_float(e == 0 ? 0x00400000u : e == 255 ? 0x7FC00000u : e << 23);
+}
+
+// The element formats.  kV: 16-byte loads per block of a row; kU: rows per load
+// group; kColLg: columns per byte as a power of two.  word<HW>: the columns of
+// one 32-bit word in column order, scaled by the hardware (HW: sf's exponent
+// field is the scale byte) or converted plainly; one<HW>: column col of a byte.
+template <bool BF8>
+struct MxFp8 {
+    static constexpr int kV = 2, kU = 8, kColLg = 0, kPerWord = 4;
+    template <bool HW>
+    static __device__ __forceinline__ void word(uint32_t w, float sf, float (&x)[4]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        f32x2 lo, hi;
+        if constexpr (HW && BF8) {
+            lo = __builtin_amdgcn_cvt_scalef32_pk_f32_bf8(w, sf, false);
+            hi = __builtin_amdgcn_cvt_scalef32_pk_f32_bf8(w, sf, true);
+        } else if constexpr (HW) {
+            lo = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w, sf, false);
+            hi = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w, sf, true);
+        } else if constexpr (BF8) {
+            lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)w, false);
+            hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)w, true);
+        } else {
+            lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+            hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+        }
+        x[0] = lo.x, x[1] = lo.y, x[2] = hi.x, x[3] = hi.y;
+#else
+        x[0] = x[1] = x[2] = x[3] = 0.0f;
+#endif
+    }
+    template <bool HW>
+    static __device__ __forceinline__ float one(uint32_t byte, int64_t, float sf) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (HW && BF8) return __builtin_amdgcn_cvt_scalef32_f32_bf8(byte, sf, 0);
+        else if constexpr (HW) return __builtin_amdgcn_cvt_scalef32_f32_fp8(byte, sf, 0);
+        else if constexpr (BF8) return __builtin_amdgcn_cvt_f32_bf8((int)byte, 0);
+        else return __builtin_amdgcn_cvt_f32_fp8((int)byte, 0);
+#else
+        return 0.0f;
+#endif
+    }
+};
+typedef MxFp8<false> MxE4M3;
+typedef MxFp8<true> MxE5M2;
+struct MxE2M1 {  // two columns per byte, the even column in the low nibble
+    static constexpr int kV = 1, kU = 16, kColLg = 1, kPerWord = 8;
+    template <bool HW>
+    static __device__ __forceinline__ void word(uint32_t w, float sf, float (&x)[8]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const float f = HW ? sf : 1.0f;
+        const f32x2 b0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, f, 0), b1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, f, 1),
+                    b2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, f, 2), b3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, f, 3);
+        x[0] = b0.x, x[1] = b0.y, x[2] = b1.x, x[3] = b1.y, x[4] = b2.x, x[5] = b2.y, x[6] = b3.x, x[7] = b3.y;
+#else
+        for (int j = 0; j < 8; ++j) x[j] = 0.0f;
+#endif
+    }
+    template <bool HW>
+    static __device__ __forceinline__ float one(uint32_t byte, int64_t col, float sf) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const f32x2 b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(byte, HW ? sf : 1.0f, 0);
+        return (col & 1) ? b.y : b.x;
+#else
+        return 0.0f;
+#endif
+    }
+};
+
+// One client's term of one column: x as converted, e its block's scale byte
+// (HW: already applied by the convert)
+template <bool SCORED, bool SCALED, bool HW>
+__device__ __forceinline__ float mx_term(float x, float sf, float a, float s, float c) {
+    if constexpr (!HW) x = x * sf;
+    return fp8_term<SCORED, SCALED>(x, a, s, c);
+}
+// The scale operand of a block: the byte in the exponent field for the
+// hardware's scaled convert, else the float32 the multiply takes
+template <bool HW>
+__device__ __forceinline__ float mx_operand(uint32_t e) {
+    return HW ? __uint_as_float(e << 23) : mx_scale(e);
+}
+
+// The row sources, passed to the kernels by value.  block(o): the lane's MX
+// block o (data units and scale byte of row i); column(c): one column.
+template <class D, class S>
+struct MxRows {  // data(i), scale(i): the lane's pointers into row i
+    const D* d;
+    const S* e;
+    int64_t ldd, lde;  // in elements of D / S
+    __device__ __forceinline__ const D* data(int64_t i) const { return d + i * ldd; }
+    __device__ __forceinline__ const S* scale(int64_t i) const { return e + i * lde; }
+};
+template <class D>
+struct MxTableRows {  // two tables of N bases: the data rows and their scale rows
+    const uint8_t* const* xi;
+    const uint8_t* const* ei;
+    int64_t od, oe;
+    __device__ __forceinline__ const D* data(int64_t i) const { return (const D*)xi[i] + od; }
+    __device__ __forceinline__ gu8* scale(int64_t i) const { return (gu8*)ei[i] + oe; }
+};
+struct MxPitched {
+    const uint8_t *X, *E;
+    int64_t ldx, lde;
+    template <class F>
+    __device__ __forceinline__ MxRows<u32x4, uint8_t> block(int64_t o) const {
+        return {reinterpret_cast<const u32x4*>(X) + o * F::kV, E + o, ldx >> 4, lde};
+    }
+    template <class F>
+    __device__ __forceinline__ MxRows<uint8_t, uint8_t> column(int64_t c) const {
+        return {X + (c >> F::kColLg), E + (c >> kMxLG), ldx, lde};
+    }
+};
+struct MxTable {
+    const uint8_t* const* xi;
+    const uint8_t* const* ei;
+    template <class F>
+    __device__ __forceinline__ MxTableRows<gu32x4> block(int64_t o) const { return {xi, ei, o * F::kV, o}; }
+    template <class F>
+    __device__ __forceinline__ MxTableRows<gu8> column(int64_t c) const { return {xi, ei, c >> F::kColLg, c >> kMxLG}; }
+};
+
+// One row's block into the lane's 32 accumulators (FIRST: acc = t_0, not 0 + t_0)
+template <class F, bool SCORED, bool SCALED, bool HW, bool FIRST>
+__device__ __forceinline__ void mx_block_add(float (&acc)[32], const u32x4 (&v)[F::kV], uint32_t e, float a, float s,
+                                             float c) {
+    const float sf = mx_operand<HW>(e);
+#pragma unroll
+    for (int k = 0; k < 4 * F::kV; ++k) {
+        const u32x4 q = v[k >> 2];
+        const uint32_t w = (k & 3) == 0 ? q.x : (k & 3) == 1 ? q.y : (k & 3) == 2 ? q.z : q.w;
+        float x[F::kPerWord];
+        F::template word<HW>(w, sf, x);
+#pragma unroll
+        for (int j = 0; j < F::kPerWord; ++j) {
+            const float t = mx_term<SCORED, SCALED, HW>(x[j], sf, a, s, c);
+            acc[F::kPerWord * k + j] = FIRST ? t : acc[F::kPerWord * k + j] + t;
+        }
+    }
+}
+
+// One load group: U rows' data units and scale bytes of the lane's block
+template <class F, int U, class Rows>
+__device__ __forceinline__ void mx_ld(u32x4 (&v)[U][F::kV], uint32_t (&e)[U], Rows src, int64_t i) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const auto* r = src.data(i + u);
+#pragma unroll
+        for (int k = 0; k < F::kV; ++k) v[u][k] = __builtin_nontemporal_load(r + k);
+        e[u] = __builtin_nontemporal_load(src.scale(i + u));
+    }
+}
+template <class F, int U, bool SCORED, bool SCALED, bool HW>
+__device__ __forceinline__ void mx_group_add(float (&acc)[32], const u32x4 (&v)[U][F::kV], const uint32_t (&e)[U],
+                                             const float* __restrict__ a, const float* __restrict__ s,
+                                             const float* __restrict__ sc, int64_t i) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        mx_block_add<F, SCORED, SCALED, HW, false>(acc, v[u], e[u], a[i + u], SCORED ? s[i + u] : 1.0f,
+                                                   SCALED ? sc[i + u] : 1.0f);
+}
+
+// The lane's block o0 of rows 0..N-1 of src, in row order
+template <class F, bool SCORED, bool SCALED, int FORM, class Rows>
+__device__ __forceinline__ void fold_mx_block(Rows src, int64_t N, const float* __restrict__ a,
+                                              const float* __restrict__ s, const float* __restrict__ sc, float divisor,
+                                              float* __restrict__ out, uint16_t* __restrict__ outb, int64_t o0,
+                                              u32x4* wave_lds) {
+    constexpr int U = F::kU;
+    constexpr bool HW = (FORM & kMxHwScale) != 0;
+    float acc[32];
+    {
+        u32x4 v[1][F::kV];
+        uint32_t e[1];
+        mx_ld<F, 1>(v, e, src, 0);
+        mx_block_add<F, SCORED, SCALED, HW, true>(acc, v[0], e[0], a[0], SCORED ? s[0] : 1.0f, SCALED ? sc[0] : 1.0f);
+    }
+    int64_t i = 1;
+    if constexpr ((FORM & kMxAhead) != 0) {
+        if (i + U <= N) {
+            u32x4 va[U][F::kV], vb[U][F::kV];
+            uint32_t ea[U], eb[U];
+            mx_ld<F, U>(va, ea, src, i);
+            for (;;) {
+                const bool more_b = i + 2 * U <= N;
+                if (more_b) mx_ld<F, U>(vb, eb, src, i + U);
+                __builtin_amdgcn_sched_barrier(0);  // the younger group's loads are issued ahead of these adds
+                mx_group_add<F, U, SCORED, SCALED, HW>(acc, va, ea, a, s, sc, i);
+                i += U;
+                if (!more_b) break;
+                const bool more_a = i + 2 * U <= N;
+                if (more_a) mx_ld<F, U>(va, ea, src, i + U);
+                __builtin_amdgcn_sched_barrier(0);
+                mx_group_add<F, U, SCORED, SCALED, HW>(acc, vb, eb, a, s, sc, i);
+                i += U;
+                if (!more_a) break;
+            }
+        }
+    } else {
+        for (; i + U <= N; i += U) {
+            u32x4 v[U][F::kV];
+            uint32_t e[U];
+            mx_ld<F, U>(v, e, src, i);
+            mx_group_add<F, U, SCORED, SCALED, HW>(acc, v, e, a, s, sc, i);
+        }
+    }
+    for (; i < N; ++i) {
+        u32x4 v[1][F::kV];
+        uint32_t e[1];
+        mx_ld<F, 1>(v, e, src, i);
+        mx_block_add<F, SCORED, SCALED, HW, false>(acc, v[0], e[0], a[i], SCORED ? s[i] : 1.0f, SCALED ? sc[i] : 1.0f);
+    }
+    float q[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) q[j] = acc[j] / divisor;
+    // out (fp32) and outb (RNE bf16) are each optional, one of them given
+    if (out) {
+        f32x4* o4 = reinterpret_cast<f32x4*>(out) + 8 * o0;
+        bool exchanged = false;
+        if constexpr ((FORM & kMxExchange) != 0) {
+            // wave-uniform: all 64 lanes are here, so the wave's 64 blocks are 8 KiB contiguous in out
+            if (__builtin_amdgcn_ballot_w64(true) == ~0ull) {
+                const int lane = threadIdx.x & 63;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    wave_lds[8 * lane + k] =
+                        __builtin_bit_cast(u32x4, f32x4{q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]});
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                f32x4* wave_out = o4 - 8 * lane;  // the block of lane 0
+#pragma unroll
+                for (int k = 0; k < 8; ++k) st16(wave_out + 64 * k + lane, wave_lds[64 * k + lane]);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                exchanged = true;
+            }
+        }
+        if (!exchanged) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                st16(o4 + k, __builtin_bit_cast(u32x4, f32x4{q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]}));
+        }
+    }
+    if (outb) {
+        u32x4* o8 = reinterpret_cast<u32x4*>(outb) + 4 * o0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            u32x4 b;
+            b.x = (uint32_t)f2bf_rne(q[8 * k]) | ((uint32_t)f2bf_rne(q[8 * k + 1]) << 16);
+            b.y = (uint32_t)f2bf_rne(q[8 * k + 2]) | ((uint32_t)f2bf_rne(q[8 * k + 3]) << 16);
+            b.z = (uint32_t)f2bf_rne(q[8 * k + 4]) | ((uint32_t)f2bf_rne(q[8 * k + 5]) << 16);
+            b.w = (uint32_t)f2bf_rne(q[8 * k + 6]) | ((uint32_t)f2bf_rne(q[8 * k + 7]) << 16);
+            st16(o8 + k, b);
+        }
+    }
+}
+
+// One column, 8 rows of loads ahead of the ordered adds (a tail lane of the
+// vector path, every lane of the one-column kernel): the f32 quotient
+template <class F, bool SCORED, bool SCALED, bool HW, class Rows>
+__device__ __forceinline__ float fold_column_mx(Rows src, int64_t col, int64_t N, const float* __restrict__ a,
+                                                const float* __restrict__ s, const float* __restrict__ sc,
+                                                float divisor) {
+    auto term = [&](uint32_t byte, uint32_t e, int64_t i) {
+        const float sf = mx_operand<HW>(e);
+        return mx_term<SCORED, SCALED, HW>(F::template one<HW>(byte, col, sf), sf, a[i], SCORED ? s[i] : 1.0f,
+                                           SCALED ? sc[i] : 1.0f);
+    };
+    float acc = term(*src.data(0), *src.scale(0), 0);
+    int64_t i = 1;
+    for (; i + 8 <= N; i += 8) {
+        uint8_t v[8], e[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            v[u] = __builtin_nontemporal_load(src.data(i + u));
+            e[u] = __builtin_nontemporal_load(src.scale(i + u));
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc = acc + term(v[u], e[u], i + u);
+    }
+    for (; i < N; ++i) acc = acc + term(*src.data(i), *src.scale(i), i);
+    return acc / divisor;
+}
+
+// The vector path: data rows and outputs 16-B aligned (a stacked matrix:
+// ldx % 16 == 0 too; scale rows at any alignment), grid-stride over the tiles.
+// Src: MxPitched or MxTable.
+template <class F, bool SCORED, bool SCALED, int FORM, class Src>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_mx_gs(
+    Src src, int64_t N, int64_t P, const float* __restrict__ a, const float* __restrict__ s,
+    const float* __restrict__ sc, float divisor, float* __restrict__ out, uint16_t* __restrict__ outb,
+    int64_t ntiles) {
+    u32x4* wave_lds = nullptr;
+    if constexpr ((FORM & kMxExchange) != 0) {
+        __shared__ u32x4 lds[kBlock * 8];  // 64 lanes x 128 B per wave
+        wave_lds = lds + (threadIdx.x >> 6) * 512;
+    }
+    auto block = [&](int64_t o) {
+        fold_mx_block<F, SCORED, SCALED, FORM>(src.template block<F>(o), N, a, s, sc, divisor, out, outb, o, wave_lds);
+    };
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        octet_tile<1, kBlock, kMxLG>(bid, P, block, block, [&](int64_t col) {
+            for (; col < P; ++col)
+                st_column_bf16(fold_column_mx<F, SCORED, SCALED, (FORM & kMxHwScale) != 0>(
+                                   src.template column<F>(col), col, N, a, s, sc, divisor),
+                               out, outb, col);
+        });
+}
+
+// One lane per column: rows at any byte offset, any pitch, any output alignment
+template <class F, bool SCORED, bool SCALED, bool HW, class Src>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_mx_scalar(
+    Src src, int64_t N, int64_t P, const float* __restrict__ a, const float* __restrict__ s,
+    const float* __restrict__ sc, float divisor, float* __restrict__ out, uint16_t* __restrict__ outb) {
+    const int64_t col = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (col >= P) return;
+    st_column_bf16(fold_column_mx<F, SCORED, SCALED, HW>(src.template column<F>(col), col, N, a, s, sc, divisor), out,
+                   outb, col);
+}
+
+// ---------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------
 inline dim3 grid_for(int64_t lanes) { return dim3((unsigned)((lanes + kBlock - 1) / kBlock)); }
@@ -4980,6 +5333,112 @@ inline int fp8_rows_fold(int fmt, const uint8_t* const* xi, int64_t N, int64_t P
                      [&](hipStream_t st) {
                          return launch_fp8_fmt(fmt, st, rows_aligned != 0, Fp8Table{xi}, N, P, a, s, c, divisor, out_f32,
                                                out_bf16);
+                     });
+}
+
+// ---- the MX folds (fa_fedavg_mx, fa_fedavg_mx_ptrs) ----------------------------
+// One geometry per format, fixed on the host, no tuner kind.  vec: the vector
+// path (tiles of kMxTileCols columns, balanced passes over at most
+// kMxBlocksPerCu blocks per CU), else one column per lane.
+static_assert(kMxTileCols == FA_MX_TILE_COLS && MxE4M3::kU == FA_MX_ROWS_AHEAD_FP8 &&
+                  MxE5M2::kU == FA_MX_ROWS_AHEAD_FP8 && MxE2M1::kU == FA_MX_ROWS_AHEAD_FP4,
+              "the header states the MX geometry");
+constexpr int kMxBlocksPerCu = 2;
+// The product's form: loads ahead, the LDS exchange, and the scale applied by
+// the hardware's scaled convert: it gives the contract's bits for every scale
+// byte times every element code (e = 0 with its subnormal products, overflow,
+// e = 255, NaN codes, -0: tests/test_gpu_mx.py), one VALU instruction per
+// element fewer than the multiply (DESIGN.md 5 MX)
+constexpr int kMxForm = kMxAhead | kMxExchange | kMxHwScale;
+
+template <class F, int FORM, class Src>
+void launch_mx(hipStream_t st, bool vec, Src src, int64_t N, int64_t P, const float* a, const float* s, const float* c,
+               float d, float* out, uint16_t* outb, int blocks_per_cu = kMxBlocksPerCu) {
+    const OctetGrid g = octet_grid(P, 1, -blocks_per_cu, cu_count(), kMxLG);
+    with_scored(s != nullptr, [&](auto SC) {
+        with_scored(c != nullptr, [&](auto CS) {
+            constexpr bool kScored = decltype(SC)::value, kScaled = decltype(CS)::value;
+            if (vec)
+                hipLaunchKernelGGL((k_fedavg_mx_gs<F, kScored, kScaled, FORM, Src>), dim3((unsigned)g.grid),
+                                   dim3(kBlock), 0, st, src, N, P, a, s, c, d, out, outb, g.tiles);
+            else
+                hipLaunchKernelGGL((k_fedavg_mx_scalar<F, kScored, kScaled, (FORM & kMxHwScale) != 0, Src>), grid_for(P),
+                                   dim3(kBlock), 0, st, src, N, P, a, s, c, d, out, outb);
+        });
+    });
+}
+template <int FORM, class Src>
+void launch_mx_fmt(int fmt, hipStream_t st, bool vec, Src src, int64_t N, int64_t P, const float* a, const float* s,
+                   const float* c, float d, float* out, uint16_t* outb, int blocks_per_cu = kMxBlocksPerCu) {
+    if (fmt == FA_MX_E4M3) launch_mx<MxE4M3, FORM>(st, vec, src, N, P, a, s, c, d, out, outb, blocks_per_cu);
+    else if (fmt == FA_MX_E5M2) launch_mx<MxE5M2, FORM>(st, vec, src, N, P, a, s, c, d, out, outb, blocks_per_cu);
+    else launch_mx<MxE2M1, FORM>(st, vec, src, N, P, a, s, c, d, out, outb, blocks_per_cu);
+}
+
+// The bytes of a data row and of a scale row
+inline int64_t mx_row_bytes(int fmt, int64_t P) { return fmt == FA_MX_E2M1 ? P / 2 : P; }
+inline int64_t mx_scale_bytes(int64_t P) { return (P + 31) / 32; }
+inline int mx_format_check(int fmt, int64_t P) {
+    if (fmt != FA_MX_E4M3 && fmt != FA_MX_E5M2 && fmt != FA_MX_E2M1) return fail(FA_ERR_ARG, "unknown MX format %d", fmt);
+    if (fmt == FA_MX_E2M1 && (P & 1))
+        return fail(FA_ERR_ARG, "MXFP4 rows hold two columns per byte: P=%lld is odd", (long long)P);
+    return FA_OK;
+}
+
+// The checks of the stacked fold: *go = true to launch (false with FA_OK: nothing to fold)
+inline int mx_fold_checks(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
+                          const float* a, float* out_f32, uint16_t* out_bf16, bool* go) {
+    *go = false;
+    if (N < 0 || P < 0) return fail(FA_ERR_ARG, "negative size (N=%lld, P=%lld)", (long long)N, (long long)P);
+    if (N == 0) return fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
+    int rc = mx_format_check(fmt, P);
+    if (rc) return rc;
+    const int64_t xb = mx_row_bytes(fmt, P), eb = mx_scale_bytes(P);
+    if (ldx < xb || lde < eb)
+        return fail(FA_ERR_SHAPE, "row pitch ldx=%lld < %lld bytes or scale pitch lde=%lld < %lld bytes", (long long)ldx,
+                    (long long)xb, (long long)lde, (long long)eb);
+    if (P == 0) { g_err[0] = 0; return FA_OK; }
+    if (!X || !E || !a || !(out_f32 || out_bf16)) return fail(FA_ERR_ARG, "null X/E/a/out pointer");
+    const size_t xbytes = (size_t)(N - 1) * ldx + xb, ebytes = (size_t)(N - 1) * lde + eb;
+    for (int k = 0; k < 2; ++k) {
+        const void* o = k ? (const void*)out_bf16 : (const void*)out_f32;
+        const size_t ob = (size_t)P * (k ? 2 : 4);
+        if (o && (overlaps(o, ob, X, xbytes) || overlaps(o, ob, E, ebytes)))
+            return fail(FA_ERR_ARG, "fa_fedavg_mx: an output overlaps the rows or their scales");
+    }
+    *go = true;
+    return FA_OK;
+}
+inline bool mx_vec(const uint8_t* X, int64_t ldx, const float* out_f32, const uint16_t* out_bf16) {
+    return aligned16(X) && (ldx % 16 == 0) && aligned16(out_f32) && aligned16(out_bf16);
+}
+
+inline int mx_fold(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
+                   const float* a, const float* s, const float* c, float divisor, float* out_f32, uint16_t* out_bf16,
+                   void* stream) {
+    bool go;
+    const int rc = mx_fold_checks(fmt, X, E, N, P, ldx, lde, a, out_f32, out_bf16, &go);
+    if (!go) return rc;
+    StreamDevice on_stream_device(stream);
+    launch_mx_fmt<kMxForm>(fmt, (hipStream_t)stream, mx_vec(X, ldx, out_f32, out_bf16), MxPitched{X, E, ldx, lde}, N, P,
+                           a, s, c, divisor, out_f32, out_bf16);
+    return check_launch("fa_fedavg_mx");
+}
+
+// xi, ei: [device] tables of the N data rows and of their N scale rows
+inline int mx_rows_fold(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, int64_t N, int64_t P, const float* a, const float* s,
+                        const float* c, float divisor, int rows_aligned, float* out_f32, uint16_t* out_bf16,
+                        void* stream) {
+    const int rc = mx_format_check(fmt, P);
+    if (rc) return rc;
+    if (P > 0 && !ei) return fail(FA_ERR_ARG, "null scale-row table");
+    const bool fits = !rows_aligned || (aligned16(out_f32) && aligned16(out_bf16));
+    return rows_fold("fa_fedavg_mx_ptrs", xi, N, P, a, bf16_any_out(out_f32, out_bf16), stream,
+                     fits ? nullptr : "the vector path of the MX row-table fold needs 16-B aligned rows and outputs",
+                     [&](hipStream_t st) {
+                         launch_mx_fmt<kMxForm>(fmt, st, rows_aligned != 0, MxTable{xi, ei}, N, P, a, s, c, divisor,
+                                                out_f32, out_bf16);
+                         return 0;
                      });
 }
 

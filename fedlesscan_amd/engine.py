@@ -52,6 +52,32 @@ class ScaledLayer(NamedTuple):
     scale: float
 
 
+# the MX element dtypes (one E8M0 scale byte per 32 flat elements) -> fa_fedavg_mx's fmt
+_MX_FORMATS = {torch.float8_e4m3fn: _lib.FA_MX_E4M3, torch.float8_e5m2: _lib.FA_MX_E5M2,
+               torch.float4_e2m1fn_x2: _lib.FA_MX_E2M1}
+_MX_SCALE_DTYPES = (torch.uint8, torch.float8_e8m0fnu)
+
+
+class MXLayer(NamedTuple):
+    """A client's MX block-scaled layer, as aggregate_layers (and the strategy
+    classes' _aggregate) take it: q the elements (float8_e4m3fn, float8_e5m2, or
+    float4_e2m1fn_x2 with two columns per byte, the even one in the low nibble),
+    e the E8M0 scale bytes (uint8 or float8_e8m0fnu), one per 32 elements of the
+    FLATTENED layer (ceil(size / 32) of them, a last partial block allowed: a
+    layer whose last dimension is a multiple of 32 is in the standard MX layout
+    along it), scale an optional dequantisation scale of the whole tensor (as
+    ScaledLayer's).  The layer counts as upcast(q) * 2^(e - 127) [* scale]; the
+    result has q's shape, the last dimension doubled for float4.  Every client
+    wraps a layer, in one format, or none does."""
+    q: torch.Tensor
+    e: torch.Tensor
+    scale: Optional[float] = None
+
+
+def _mx_cols(dt: torch.dtype, nbytes: int) -> int:
+    return 2 * nbytes if dt == torch.float4_e2m1fn_x2 else nbytes
+
+
 def default_device() -> torch.device:
     if not torch.cuda.is_available():
         raise RuntimeError("fedlesscan_amd needs a ROCm GPU (torch.cuda.is_available() is False)")
@@ -433,7 +459,8 @@ def _check_matrix(X: torch.Tensor) -> tuple[int, int, int]:
 
 def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] = None, *,
                  out: Optional[torch.Tensor] = None, want_bf16: bool = False, total=None,
-                 exact: bool = True, out_bf16: Optional[torch.Tensor] = None, scales: Optional[Sequence] = None):
+                 exact: bool = True, out_bf16: Optional[torch.Tensor] = None, scales: Optional[Sequence] = None,
+                 block_scales: Optional[torch.Tensor] = None):
     """FedAvg (scores None) / stall-aware fold over the rows of X, in row order.
 
     `total` overrides the divisor sum (used when zip() truncated the rows but
@@ -450,12 +477,18 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
     and folded in float32 with the bf16 fold's outputs; scales= (N floats,
     rounded to float32 as the weights are) multiplies row i by scale_i before
     its weight, with a rounding of its own.
+    MX rows: block_scales= E, [N, ceil(P / 32)] E8M0 bytes (float8_e8m0fnu or
+    uint8, any pitch) with X [N, P] of float8_e4m3fn / float8_e5m2 or [N, P / 2]
+    of float4_e2m1fn_x2; element p of row i counts as upcast(q) * 2^(E[i, p >>
+    5] - 127), then scales= as for fp8 rows (MXLayer says the rest).
     """
     N, P, ldx = _check_matrix(X)
     if len(weights) != N or (scores is not None and len(scores) != N):
         raise InvalidParameterShapeError(f"{N} rows but {len(weights)} weights"
                                          + ("" if scores is None else f" / {len(scores)} scores"))
     dev = X.device
+    if block_scales is not None or X.dtype == torch.float4_e2m1fn_x2:
+        return _fold_mx(X, block_scales, None, weights, scores, scales, out, total, want_bf16, out_bf16)
     if X.dtype in _FP8_FORMATS:
         return _fold_fp8(X, None, weights, scores, scales, out, total, want_bf16, out_bf16)
     if scales is not None:
@@ -1032,9 +1065,11 @@ _NO_CAPTURE_TABLE = (torch.float64, torch.int32, torch.int64)
 # the narrow rows (fa_fedavg_widen; nothing else counts there), layers folded
 # through a widening row table (fa_fedavg_widen_ptrs, or each layer of a
 # fa_fedavg_widen_layers launch) and those launches (they move no other counter),
-# fp8 folds (fa_fedavg_fp8 and fa_fedavg_fp8_ptrs: one per layer of a model)
+# fp8 folds (fa_fedavg_fp8 and fa_fedavg_fp8_ptrs: one per layer of a model),
+# MX folds (fa_fedavg_mx and fa_fedavg_mx_ptrs, likewise)
 stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0, "layer_table_folds": 0, "rows_int_folds": 0,
-         "widened_folds": 0, "widened_row_folds": 0, "widened_table_folds": 0, "fp8_folds": 0}
+         "widened_folds": 0, "widened_row_folds": 0, "widened_table_folds": 0, "fp8_folds": 0,
+         "mx_folds": 0}
 
 
 class RowSet:
@@ -1056,9 +1091,16 @@ class RowSet:
         accepts the fold.
     fold_rows(rowset, weights) then costs the factor upload and the kernel.
     The RowSet keeps the tensors alive; their CONTENTS may change between
-    folds, their storage may not (re-create the RowSet after reallocating)."""
+    folds, their storage may not (re-create the RowSet after reallocating).
 
-    def __init__(self, rows: Sequence[torch.Tensor]):
+    block_scales: the rows are MX rows (fp8, or float4_e2m1fn_x2 with two
+    columns per byte) and block_scales[i] holds row i's ceil(columns / 32) E8M0
+    bytes, separately allocated, at any alignment: one device table of the 2N
+    bases for fa_fedavg_mx_ptrs (`cols`: the columns of the fold)."""
+
+    scale_rows = None  # the E8M0 scale rows of an MX row set (a set assembled without __init__ has none)
+
+    def __init__(self, rows: Sequence[torch.Tensor], block_scales: Optional[Sequence[torch.Tensor]] = None):
         rows = list(rows)
         N = len(rows)
         if N == 0:
@@ -1079,6 +1121,9 @@ class RowSet:
         self.ptrs = None
         self.host_ptrs = None
         self.aligned = False
+        if block_scales is not None:
+            self._mx_table(list(block_scales))
+            return
         # (float64 and integer rows met under a stream capture keep the stacked copy they had before the row table)
         if dt in _ROW_TABLE_DTYPES and P > 0 and not (dt in _NO_CAPTURE_TABLE
                                                       and torch.cuda.is_current_stream_capturing()):
@@ -1088,13 +1133,38 @@ class RowSet:
                 self.ptrs = torch.from_numpy(host_ptrs).to(dev)
                 self.aligned = not (host_ptrs % 16).any()
 
+    def _mx_table(self, es: list) -> None:
+        """The table of an MX row set: N data bases, then the N scale-row bases."""
+        N, dev = self.N, self.device
+        if self.dtype not in _MX_FORMATS:
+            raise InvalidParameterShapeError(f"block_scales are for fp8 / float4_e2m1fn_x2 rows, got {self.dtype}")
+        self.cols = _mx_cols(self.dtype, self.P)
+        nb = (self.cols + 31) // 32
+        if len(es) != N:
+            raise InvalidParameterShapeError(f"{N} rows but {len(es)} block-scale rows")
+        for i, e in enumerate(es):
+            if not (isinstance(e, torch.Tensor) and e.dtype in _MX_SCALE_DTYPES):
+                raise InvalidParameterShapeError(f"block_scales[{i}] must hold E8M0 bytes (float8_e8m0fnu or uint8), "
+                                                 f"got {getattr(e, 'dtype', type(e))}")
+            if e.numel() != nb or not e.is_contiguous() or e.device != dev:
+                raise InvalidParameterShapeError(f"block_scales[{i}]: {e.numel()} scale bytes for {self.cols} columns "
+                                                 f"(one per 32: {nb}, contiguous, on {dev})")
+        self.scale_rows = es
+        if self.P > 0:
+            self.host_ptrs = np.fromiter(map(torch.Tensor.data_ptr, self.rows + es), dtype=np.int64, count=2 * N)
+            self.ptrs = torch.from_numpy(self.host_ptrs).to(dev)
+            self.aligned = not (self.host_ptrs[:N] % 16).any()
+
     def overlaps(self, t: torch.Tensor) -> bool:
-        """Does tensor t share a byte with any row?"""
+        """Does tensor t share a byte with any row (or scale row)?"""
         if self.host_ptrs is None or self.P == 0 or t.numel() == 0:
             return False
         lo = t.data_ptr()
         hi = lo + t.numel() * t.element_size()
-        return bool(np.any((self.host_ptrs < hi) & (lo < self.host_ptrs + self.P * self.rows[0].element_size())))
+        size = self.P * self.rows[0].element_size()
+        if self.scale_rows is not None:
+            size = np.repeat([size, self.scale_rows[0].numel()], self.N)
+        return bool(np.any((self.host_ptrs < hi) & (lo < self.host_ptrs + size)))
 
     def stacked(self) -> torch.Tensor:
         """The rows copied into one [N, P] tensor (the fallbacks without a row-table fold)."""
@@ -1211,6 +1281,90 @@ def _fold_fp8(X: Optional[torch.Tensor], rs: Optional["RowSet"], weights, scores
     return out
 
 
+def _fold_mx(X: Optional[torch.Tensor], E: Optional[torch.Tensor], rs: Optional["RowSet"], weights, scores, scales,
+             out, total, want_bf16, out_bf16):
+    """MX rows, a stacked byte matrix X with its scale bytes E (fa_fedavg_mx) or
+    the 2N-pointer table of rs (fa_fedavg_mx_ptrs): float32 factors and scales
+    in ONE staged upload, the bf16 fold's outputs.  Everything is decided here
+    on the host before the launch; an output that shares bytes with a row or a
+    scale row is folded into a fresh buffer and copied."""
+    if torch.cuda.is_current_stream_capturing():
+        raise InvalidParameterShapeError("the MX fold does not run under stream capture "
+                                         "(its factors and scales are staged by a copy the graph would not own)")
+    if X is not None:
+        N, Pb, ldx = _check_matrix(X)
+        if X.dtype not in _MX_FORMATS:
+            raise InvalidParameterShapeError(f"block_scales are for fp8 / float4_e2m1fn_x2 rows, got {X.dtype}")
+        if E is None:
+            raise InvalidParameterShapeError(f"{X.dtype} rows fold only with their block_scales")
+        dev, fmt, P = X.device, _MX_FORMATS[X.dtype], _mx_cols(X.dtype, Pb)
+        nb = (P + 31) // 32
+        if not (isinstance(E, torch.Tensor) and E.dtype in _MX_SCALE_DTYPES):
+            raise InvalidParameterShapeError("block_scales must hold E8M0 bytes (float8_e8m0fnu or uint8), got "
+                                             f"{getattr(E, 'dtype', type(E))}")
+        if E.device != dev or tuple(E.shape) != (N, nb) or (nb > 1 and E.stride(1) != 1):
+            raise InvalidParameterShapeError(f"block_scales must be [{N}, {nb}] on {dev} with unit column stride (one "
+                                             f"byte per 32 of {P} columns), got {tuple(E.shape)}")
+        lde = E.stride(0) if N > 1 else max(nb, 1)
+        if lde < nb:
+            raise InvalidParameterShapeError(f"block_scales rows overlap (pitch {lde} < {nb})")
+        spans = [(X.data_ptr(), (N - 1) * ldx + Pb), (E.data_ptr(), (N - 1) * lde + nb)]
+    else:
+        N, P, dev, fmt = rs.N, rs.cols, rs.device, _MX_FORMATS[rs.dtype]
+    if fmt == _lib.FA_MX_E2M1 and P % 2:
+        raise InvalidParameterShapeError(f"float4_e2m1fn_x2 rows hold two columns per byte: {P} columns")
+    if scales is not None and len(scales) != N:
+        raise InvalidParameterShapeError(f"{N} rows but {len(scales)} scales")
+    _check_out("out", out, torch.float32, P)
+    _check_out("out_bf16", out_bf16, torch.bfloat16, P)
+
+    def clash(t) -> bool:
+        if t is None or P == 0:
+            return False
+        if X is None:
+            return rs.overlaps(t)
+        lo, hi = t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+        return any(lo < p + n and p < hi for p, n in spans)
+
+    dst, dstb = out, out_bf16
+    if clash(out):
+        out = None
+    outb = None if clash(out_bf16) else out_bf16
+    if outb is None and (want_bf16 or out_bf16 is not None):
+        outb = torch.empty(P, dtype=torch.bfloat16, device=dev)
+    if out is None and (dst is not None or outb is None or want_bf16):
+        out = torch.empty(P, dtype=torch.float32, device=dev)
+    f = Factors.weak_f32(weights, scores, total) or Factors(weights, scores, _F32, total=total)
+    parts = [f.a] if f.s is None else [f.a, f.s]
+    if scales is not None:
+        c = weak_f32(scales)
+        parts.append(c if c is not None else round_scalars(scales, _F32))
+    staged = stage_factors(parts, dev)
+    a, s = staged[0], (staged[1] if f.s is not None else None)
+    c = staged[-1] if scales is not None else None
+    if X is not None:
+        _lib.call("fa_fedavg_mx", fmt, X.data_ptr(), E.data_ptr(), N, P, ldx, lde, a.data_ptr(), _ptr(s), _ptr(c),
+                  float(f.div), _ptr(out), _ptr(outb), stream_ptr(dev))
+    else:
+        aligned = (rs.aligned and (out is None or out.data_ptr() % 16 == 0)
+                   and (outb is None or outb.data_ptr() % 16 == 0))
+        xi = rs.ptrs.data_ptr() if P else 0
+        _lib.call("fa_fedavg_mx_ptrs", fmt, xi, xi + 8 * N, N, P, a.data_ptr(), _ptr(s), _ptr(c), float(f.div),
+                  int(aligned), _ptr(out), _ptr(outb), stream_ptr(dev))
+    stats["mx_folds"] += 1
+    if dst is not None and dst is not out:
+        dst.reshape(-1)[:P].copy_(out)
+        out = dst
+    if dstb is not None and dstb is not outb:
+        dstb.reshape(-1)[:P].copy_(outb)
+        outb = dstb
+    if want_bf16:
+        return out, outb
+    if out_bf16 is not None:
+        return outb if out is None else (out, outb)
+    return out
+
+
 def _fold_rows_f16(rs: "RowSet", weights, scores, out, total):
     """float16 rows whose result stays float16 through the row table
     (fa_fedavg_f16_ptrs): the factors of fold_stacked's float16 branch."""
@@ -1305,7 +1459,8 @@ def _fold_rows_widen(rs: "RowSet", kind: int, f: Factors, out):
 
 def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
               out: Optional[torch.Tensor] = None, total=None, want_bf16: bool = False,
-              out_bf16: Optional[torch.Tensor] = None, scales: Optional[Sequence] = None):
+              out_bf16: Optional[torch.Tensor] = None, scales: Optional[Sequence] = None,
+              block_scales: Optional[Sequence[torch.Tensor]] = None):
     """The fold over separately allocated 1-D CUDA rows (no stacking copy for
     fp32, bfloat16, float16 / float64 rows whose result stays in their dtype,
     int32 / int64 rows whose products stay in their dtype: int_row_factors, and
@@ -1314,11 +1469,18 @@ def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
     RowSet (prepared once, reusable) or a sequence of tensors (a RowSet is
     built for this call).  want_bf16 / out_bf16: as fold_stacked (bf16 and
     fp8 rows); scales: as fold_stacked (fp8 rows, folded through their own row
-    table)."""
-    rs = rows if isinstance(rows, RowSet) else RowSet(rows)
+    table); block_scales: the rows are MX rows, block_scales[i] row i's E8M0
+    bytes (RowSet's block_scales=; a RowSet built with them needs none here)."""
+    rs = rows if isinstance(rows, RowSet) else RowSet(rows, block_scales)
     if len(weights) != rs.N or (scores is not None and len(scores) != rs.N):
         raise InvalidParameterShapeError(f"{rs.N} rows but {len(weights)} weights"
                                          + ("" if scores is None else f" / {len(scores)} scores"))
+    if rs.scale_rows is not None:
+        if block_scales is not None and rs is rows:
+            raise InvalidParameterShapeError("this RowSet already holds its block_scales")
+        return _fold_mx(None, None, rs, weights, scores, scales, out, total, want_bf16, out_bf16)
+    if block_scales is not None or rs.dtype == torch.float4_e2m1fn_x2:
+        raise InvalidParameterShapeError(f"{rs.dtype} rows and block_scales: build the RowSet with block_scales=")
     if rs.dtype in _FP8_FORMATS:
         if rs.view is not None or rs.P == 0:
             # rows of one allocation at a fixed pitch (or no columns): the stacked fold, no pointer table
@@ -1740,6 +1902,33 @@ def _unwrap_scaled(parameters, n_eff):
     return plain, scales
 
 
+def _unwrap_mx(parameters, n_eff):
+    """aggregate_layers' parameters with every MXLayer replaced by its element
+    tensor, and {layer index: (the clients' scale-byte tensors, their scales or
+    None)}; the parameters themselves and {} when no layer is wrapped."""
+    if not any(isinstance(x, MXLayer) for p in parameters[:n_eff] for x in p):
+        return parameters, {}
+    L = min(len(p) for p in parameters[:n_eff])
+    plain = [list(p[:L]) for p in parameters[:n_eff]]
+    mx = {}
+    for li in range(L):
+        wrapped = [isinstance(p[li], MXLayer) for p in plain]
+        if not any(wrapped):
+            continue
+        if not all(wrapped):
+            raise InvalidParameterShapeError(f"layer {li}: every client gives an MXLayer or none does")
+        given = [p[li].scale is not None for p in plain]
+        if any(given) and not all(given):
+            raise InvalidParameterShapeError(f"layer {li}: every client's MXLayer carries a scale or none does")
+        if len({p[li].q.dtype for p in plain}) != 1 or plain[0][li].q.dtype not in _MX_FORMATS:
+            raise InvalidParameterShapeError(f"layer {li}: MX layers fold in one format, every client's alike; got "
+                                             f"{sorted({str(p[li].q.dtype) for p in plain})}")
+        mx[li] = ([p[li].e.reshape(-1) for p in plain], [p[li].scale for p in plain] if all(given) else None)
+        for p in plain:
+            p[li] = p[li].q
+    return plain, mx
+
+
 def _multi(devices) -> Optional[list]:
     """The device list of a multi-GPU call, or None for a one-GPU call."""
     if devices is None:
@@ -1768,7 +1957,10 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
     Device fp8 layers (float8_e4m3fn, float8_e5m2) fold one layer at a time
     through their row table, where they lie; such a layer may be given as
     ScaledLayer(q, scale) by every client: client i's rows then count as
-    q_i.to(float32) * np.float32(scale_i) (fold_stacked's scales=).
+    q_i.to(float32) * np.float32(scale_i) (fold_stacked's scales=).  Device MX
+    layers are given as MXLayer(q, e, scale=None) by every client and fold the
+    same way (fa_fedavg_mx_ptrs); a float4 layer's result has its last
+    dimension doubled.
     """
     multi = _multi(devices)
     if multi is not None and device is None:
@@ -1781,9 +1973,13 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
         return []
     total_weights = list(weights)
     parameters, layer_scales = _unwrap_scaled(parameters, n_eff)
+    parameters, layer_mx = _unwrap_mx(parameters, n_eff)
     L, shapes, dtypes = _layer_meta(parameters, n_eff)
     if L == 0:
         return []
+    for li, dt in enumerate(dtypes):
+        if dt == torch.float4_e2m1fn_x2 and li not in layer_mx:
+            raise InvalidParameterShapeError(f"layer {li}: float4_e2m1fn_x2 rows fold only as MXLayers")
     for li in layer_scales:
         if dtypes[li] not in _FP8_FORMATS:
             raise InvalidParameterShapeError(f"layer {li}: a ScaledLayer holds fp8 rows, got {dtypes[li]}")
@@ -1802,10 +1998,16 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
     for _, lis in groups.items():
         sizes = [int(np.prod(shapes[li])) if len(shapes[li]) else 1 for li in lis]
         P = sum(sizes)
-        if dtypes[lis[0]] in _FP8_FORMATS:
+        if dtypes[lis[0]] in _MX_FORMATS:
             # device fp8 layers: each folds from the clients' own bytes through its row table
             for li in lis:
                 rows = [parameters[i][li].reshape(-1) for i in range(n_eff)]
+                if li in layer_mx:
+                    es, cs = layer_mx[li]
+                    shp = shapes[li][:-1] + (_mx_cols(dtypes[li], shapes[li][-1]),) if shapes[li] else ()
+                    outs[li] = fold_rows(rows, w, sc, total=sum(total_weights), scales=cs,
+                                         block_scales=es).reshape(shp)
+                    continue
                 outs[li] = fold_rows(rows, w, sc, total=sum(total_weights),
                                      scales=layer_scales.get(li)).reshape(shapes[li])
             continue

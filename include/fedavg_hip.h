@@ -715,6 +715,62 @@ int fa_fedavg_fp8_ptrs(int fmt, const uint8_t* const* xi, int64_t N, int64_t P,
                        const float* a, const float* s, const float* c, float divisor, int rows_aligned,
                        float* out_f32, uint16_t* out_bf16, void* stream);
 
+/* ---- MX block-scaled client rows (new symbols, ABI still 7) -------------------
+ * Client updates in OCP Microscaling formats: blocks of 32 elements share one
+ * E8M0 power-of-two scale byte.  Elements are e4m3 or e5m2 bytes (MXFP8) or
+ * e2m1 nibbles (MXFP4: two columns per byte, the even column in the low
+ * nibble).  Folded from the bytes themselves; no float32 copy of the rows
+ * exists at any time.  No reference path: as the bf16 and fp8 folds it is
+ * defined as the exact upcast followed by the float32 fold.
+ * Blocks run over the FLATTENED row: block b covers columns [32b, 32b + 32), a
+ * last partial block is allowed, so a scale row has ceil(P / 32) bytes.  A
+ * layer whose last dimension is a multiple of 32 is thereby in the standard
+ * MX layout along that dimension.
+ * Per client i and column p, a, s, c [device, N float32] (s NULL for FedAvg, c
+ * NULL without per-client scales: then no multiply is made):
+ *   x   = f32(q_i[p])                 exact; e2m1: +-{0, .5, 1, 1.5, 2, 3, 4, 6}
+ *   x   = fl32(x * f32(e_i[p >> 5]))  f32(e) = 2^(e-127), e = 0 the subnormal
+ *                                     2^-127, e = 255 NaN; exact when finite,
+ *                                     overflow to +-inf, subnormals kept
+ *   x   = fl32(x * c_i)               only with c
+ *   t   = fl32(x * a_i);  t = fl32(t * s_i) with s
+ *   acc = t_0;  acc = fl32(acc + t_i), i = 1..N-1 in client order, no FMA
+ *   out = fl32(acc / divisor)         IEEE divide
+ * -- bit for bit fa_fedavg_f32 over the dequantised rows.  No two factors are
+ * ever combined before they meet the element.  out_f32 [P] and out_bf16 [P]
+ * (its RNE bf16 copy) are each optional, one of them given, as fa_fedavg_bf16.
+ *   fa_fedavg_mx: X a stacked byte matrix of pitch ldx bytes (>= P, MXFP4:
+ *     >= P / 2), E its scale bytes at pitch lde (>= ceil(P / 32)), any
+ *     alignment.  X and the outputs 16-B aligned with ldx % 16 == 0 take the
+ *     vector path; anything else one column per lane.  No output may overlap
+ *     X or E -> FA_ERR_ARG.  MXFP4 with odd P -> FA_ERR_ARG.
+ *   fa_fedavg_mx_ptrs: xi, ei [device] arrays of N [device] pointers, the data
+ *     rows and their scale rows; rows_aligned != 0 promises 16-B aligned data
+ *     rows and outputs (an output off 16 B -> FA_ERR_ARG); with 0 rows at any
+ *     byte offset, one column per lane.  No output may overlap a row.
+ * The same bits with either path and either entry.  One fixed geometry per
+ * format, no tuner kind: a lane owns one MX block (32 columns, 32 float32
+ * accumulators, one scale byte per row), so a tile is FA_MX_TILE_COLS columns;
+ * tiles are walked grid-stride in balanced passes over at most two blocks per
+ * CU; the lane loads FA_MX_ROWS_AHEAD_* rows (data and scale byte) while it
+ * folds the previous group, and a full wave exchanges its float32 results
+ * through LDS so that each store instruction writes 1 KiB contiguous; the
+ * P % 32 trailing columns fold in one lane.  Neither allocates nor
+ * synchronises.  Not covered: host rows, the layer tables, the sharded step,
+ * stream capture, a tuner kind, MXFP6, NVFP4, quantised output. */
+#define FA_MX_E4M3 0
+#define FA_MX_E5M2 1
+#define FA_MX_E2M1 2
+#define FA_MX_TILE_COLS 8192
+#define FA_MX_ROWS_AHEAD_FP8 8
+#define FA_MX_ROWS_AHEAD_FP4 16
+int fa_fedavg_mx(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P,
+                 int64_t ldx, int64_t lde, const float* a, const float* s, const float* c, float divisor,
+                 float* out_f32, uint16_t* out_bf16, void* stream);
+int fa_fedavg_mx_ptrs(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, int64_t N, int64_t P,
+                      const float* a, const float* s, const float* c, float divisor, int rows_aligned,
+                      float* out_f32, uint16_t* out_bf16, void* stream);
+
 /* ---- host staging: page-locked documents and direct DMA ---------------------
  * A result store that keeps documents in page-locked memory lets the ingest
  * DMA each client's layers straight from the document into the device chunk,

@@ -117,6 +117,17 @@ int fa_fedavg_f16_ptrs_form(const uint16_t* const* xi, int64_t N, int64_t P, con
 int fa_fedavg_fp8_form(const uint8_t* X, int64_t N, int64_t P, int64_t ldx, const float* a, const float* s,
                        const float* c, float divisor, float* out_f32, uint16_t* out_bf16, void* stream, int form,
                        int blocks_per_cu);
+/* The vector path of fa_fedavg_mx in one form of the block fold over a grid of
+ * blocks_per_cu (>= 1) blocks per CU, balanced passes: form bit 0 = the next
+ * row group's loads issued ahead of this group's adds, bit 1 = float32 results
+ * exchanged through LDS, bit 2 = the scale applied by the hardware's scaled
+ * convert instead of an IEEE multiply (NOT the contract's bits at the edges of
+ * the scale range: DESIGN.md 5 MX).  Forms 1, 2, 3 (the product's) and 7.  X
+ * and the outputs 16-B aligned, ldx % 16 == 0, else FA_ERR_ARG; the other
+ * checks as fa_fedavg_mx.  tools/mx_bench.py --forms. */
+int fa_fedavg_mx_form(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
+                      const float* a, const float* s, const float* c, float divisor, float* out_f32,
+                      uint16_t* out_bf16, void* stream, int form, int blocks_per_cu);
 /* The layer-table folds (fa_fedavg_*_layers) with the units per lane of the
  * caller's plan (fa_layers_plan with units = 1, 2 or 4) and a cap on the grid
  * (grid_cap > 0: at most that many blocks, so small models take several
