@@ -111,6 +111,10 @@ _PROTOS = {
     "fa_fedavg_fp8_ptrs": (_int, [_int, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _vp, _vp]),
     "fa_fedavg_mx": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
     "fa_fedavg_mx_ptrs": (_int, [_int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _vp, _vp]),
+    "fa_fedavg_mx_q": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _int, _vp, _vp, _vp]),
+    "fa_fedavg_mx_q_ptrs": (_int, [_int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _int, _vp, _vp, _vp]),
+    "fa_fedavg_fp8_q": (_int, [_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _int, _vp, _vp, _vp]),
+    "fa_fedavg_fp8_q_ptrs": (_int, [_int, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _int, _vp, _vp, _vp]),
     "fa_npz_index":(_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _int]),
     "fa_crc32": (_int, [_vp, _i64, ctypes.c_uint32, _int, ctypes.POINTER(ctypes.c_uint32)]),
     "fa_pack": (_int, [_vp, _vp, _vp, _vp, _i64, _int]),
@@ -181,6 +185,7 @@ _BENCH_PROTOS = {
     "fa_fedavg_f16_ptrs_form": (_int, [_vp, _i64, _i64, _vp, _vp, ctypes.c_uint16, _int, _vp, _vp, _int]),
     "fa_fedavg_fp8_form": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _int, _int]),
     "fa_fedavg_mx_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _int, _int]),
+    "fa_fedavg_mx_q_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _f32, _vp, _int, _vp, _vp, _vp, _int]),
     "fa_fedavg_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp, _vp]),
     "fa_fedavg_int_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp]),
     "fa_fedavg_widen_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp]),

@@ -705,6 +705,26 @@ int fa_fedavg_mx_form(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, in
     }
     return check_launch("fa_fedavg_mx_form");
 }
+int fa_fedavg_mx_q_form(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
+                        const float* a, float divisor, float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e,
+                        void* stream, int qform) {
+    bool go;
+    const int rc = mx_q_fold_checks(fmt, X, E, N, P, ldx, lde, a, out_f32, out_fmt, out_q, out_e, &go);
+    if (!go) return rc;
+    if (qform < 0 || qform > 4 || !mx_vec(X, ldx, out_f32, nullptr) || !aligned16(out_q))
+        return fail(FA_ERR_ARG, "MX output form %d: forms 0..4, aligned rows and outputs", qform);
+    StreamDevice on_stream_device(stream);
+    const MxPitched src{X, E, ldx, lde};
+    hipStream_t st = (hipStream_t)stream;
+    switch (qform) {
+        case 0: launch_mx_q_fmt<kMxForm, 0, true>(fmt, st, true, src, N, P, a, nullptr, nullptr, divisor, out_f32, out_fmt, out_q, out_e); break;
+        case 1: launch_mx_q_fmt<kMxForm, 1, true>(fmt, st, true, src, N, P, a, nullptr, nullptr, divisor, out_f32, out_fmt, out_q, out_e); break;
+        case 2: launch_mx_q_fmt<kMxForm, 2, true>(fmt, st, true, src, N, P, a, nullptr, nullptr, divisor, out_f32, out_fmt, out_q, out_e); break;
+        case 3: launch_mx_q_fmt<kMxForm, 3, true>(fmt, st, true, src, N, P, a, nullptr, nullptr, divisor, out_f32, out_fmt, out_q, out_e); break;
+        default: launch_mx_q_fmt<kMxForm, 4, true>(fmt, st, true, src, N, P, a, nullptr, nullptr, divisor, out_f32, out_fmt, out_q, out_e); break;
+    }
+    return check_launch("fa_fedavg_mx_q_form");
+}
 int fa_fedavg_layers_form(int dtype, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
                           int64_t tiles, int units, int64_t grid_cap, const void* a, const void* s, double divisor,
                           void* out, void* out_bf16, void* stream) {

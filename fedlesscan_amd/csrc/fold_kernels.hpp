@@ -3224,6 +3224,156 @@ __device__ __forceinline__ void fp8_group_add(float (&acc)[C][16], const u32x4 (
     }
 }
 
+// ---------------------------------------------------------------------------
+// MX output of the fp8 and MX folds (fa_fedavg_fp8_q, fa_fedavg_mx_q and their
+// _ptrs entries; DESIGN.md 2 and 5 MX output).  The float32 quotients v[j] of
+// one block of 32 flat columns leave as one E8M0 byte and 32 element codes:
+//   m = max |v[j]| as bits;  any NaN / inf (m >= 0x7F800000): E = 255, codes 0
+//   E = max((m >> 23) - emax, 0);  y = v / 2^(E-127), |y| clamped to maxnorm
+//   code = RNE_F(y), the sign bit of v kept
+// The maximum is an unsigned integer maximum over the magnitudes' bits, so one
+// compare chain finds the amax's exponent field and the non-finite flag at
+// once.  The clamp is one v_med3_f32 against +-maxnorm * 2^(E-127) (a normal
+// float32 for every E), taken BEFORE the division so that nothing depends on
+// what a convert does above maxnorm.  Forms (bits of QFORM): kMxQHwScale: the
+// convert divides (v_cvt_scalef32_pk_{fp8,bf8,fp4}_f32 with E in the exponent
+// field of its scale operand), else an IEEE multiply by 2^(127-E), a normal
+// float32 for E in 0..252, and the convert with a scale of 1.0; kMxQSign: the
+// codes' sign bits are written from v's; kMxQExchange: a full wave's fp8 codes
+// pass through its LDS so each store instruction writes 1 KiB contiguous.
+// DESIGN.md 5 MX output says which the product uses and why.
+// ---------------------------------------------------------------------------
+constexpr int kMxQExchange = 1, kMxQHwScale = 2, kMxQSign = 4;
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+
+struct MxQNone {
+    static constexpr bool kOn = false;
+};
+// FMT: FA_MX_E4M3 / _E5M2 / _E2M1, the element format of the result
+template <int FMT, int QFORM>
+struct MxQ {
+    static constexpr bool kOn = true, kFp4 = FMT == FA_MX_E2M1, kExchange = !kFp4 && (QFORM & kMxQExchange) != 0;
+    static constexpr int kBits = kFp4 ? 4 : 8, kPerWord = 32 / kBits;
+    static constexpr uint32_t kEmax = FMT == FA_MX_E4M3 ? 8 : FMT == FA_MX_E5M2 ? 15 : 2;
+    // maxnorm as float32 bits: 448, 57344, 6
+    static constexpr uint32_t kMaxBits = FMT == FA_MX_E4M3 ? 0x43E00000u : FMT == FA_MX_E5M2 ? 0x47600000u : 0x40C00000u;
+    struct Block {
+        float lim, mul, sf;  // the clamp, 2^(127-E), the convert's scale operand
+        bool dead;           // a non-finite block: every code 0
+    };
+    static __device__ __forceinline__ uint32_t scale_byte(uint32_t m) {
+        const uint32_t eb = m >> 23;
+        return m >= 0x7F800000u ? 255u : eb > kEmax ? eb - kEmax : 0u;
+    }
+    static __device__ __forceinline__ Block prepare(uint32_t E) {
+        const bool dead = E == 255u;
+        const uint32_t e = dead ? 127u : E;
+        return {__uint_as_float(kMaxBits + (e << 23) - (127u << 23)), __uint_as_float((254u - e) << 23),
+                (QFORM & kMxQHwScale) ? __uint_as_float(e << 23) : 1.0f, dead};
+    }
+    // The codes of two columns into pair SEL of the word `old`
+    template <int SEL>
+    static __device__ __forceinline__ uint32_t pair(uint32_t old, float v0, float v1, const Block& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        float y0 = __builtin_amdgcn_fmed3f(v0, -b.lim, b.lim), y1 = __builtin_amdgcn_fmed3f(v1, -b.lim, b.lim);
+        if constexpr ((QFORM & kMxQHwScale) == 0) y0 = y0 * b.mul, y1 = y1 * b.mul;
+        uint32_t r;
+        if constexpr (kFp4) {
+            r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(old, y0, y1, b.sf, SEL);
+        } else {
+            const s16x2 o = __builtin_bit_cast(s16x2, old);
+            r = __builtin_bit_cast(uint32_t, FMT == FA_MX_E5M2
+                                                 ? __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(o, y0, y1, b.sf, SEL != 0)
+                                                 : __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(o, y0, y1, b.sf, SEL != 0));
+        }
+        if constexpr ((QFORM & kMxQSign) != 0) {
+            constexpr int s0 = SEL * 2 * kBits + kBits - 1, s1 = s0 + kBits;
+            r = (r & ~((1u << s0) | (1u << s1))) | (__float_as_uint(v0) >> 31 << s0) | (__float_as_uint(v1) >> 31 << s1);
+        }
+        return r;
+#else
+        return 0u;
+#endif
+    }
+    // One 32-bit word of codes: 4 (fp8) or 8 (fp4) columns in column order
+    static __device__ __forceinline__ uint32_t word(const float* v, const Block& b) {
+        uint32_t r = pair<0>(0u, v[0], v[1], b);
+        r = pair<1>(r, v[2], v[3], b);
+        if constexpr (kFp4) {
+            r = pair<2>(r, v[4], v[5], b);
+            r = pair<3>(r, v[6], v[7], b);
+        }
+        return b.dead ? 0u : r;
+    }
+    static __device__ __forceinline__ uint32_t one(float v, const Block& b) {
+        return b.dead ? 0u : pair<0>(0u, v, 0.0f, b) & ((1u << kBits) - 1);
+    }
+};
+
+__device__ __forceinline__ uint32_t mx_q_mag(float v) { return __float_as_uint(v) & 0x7FFFFFFFu; }
+template <int K>
+__device__ __forceinline__ uint32_t mx_q_amax(const float (&q)[K]) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) m = max(m, mx_q_mag(q[j]));
+    return m;
+}
+// K quotients of one block as K * kBits / 128 stores of 16 B (K = 16, fp4: one of 8 B) at oq
+template <class Q, int K>
+__device__ __forceinline__ void mx_q_codes(const float (&q)[K], const typename Q::Block& b, uint8_t* oq) {
+    constexpr int W = K / Q::kPerWord;
+    uint32_t w[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) w[k] = Q::word(&q[k * Q::kPerWord], b);
+    if constexpr (W == 2) {
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        __builtin_nontemporal_store(u32x2{w[0], w[1]}, reinterpret_cast<u32x2*>(oq));
+    } else {
+#pragma unroll
+        for (int k = 0; k < W / 4; ++k) st16(oq + 16 * k, u32x4{w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]});
+    }
+}
+// A partial last block, one lane, two passes over fold(col) (the same
+// instructions give the same quotient twice): the amax of columns [col, P),
+// their float32 results stored on the way; then their codes, byte by byte
+template <class Fold>
+__device__ __forceinline__ uint32_t mx_q_tail_amax(int64_t col, int64_t P, Fold fold, float* out) {
+    uint32_t m = 0;
+    for (; col < P; ++col) {
+        const float q = fold(col);
+        if (out) out[col] = q;
+        m = max(m, mx_q_mag(q));
+    }
+    return m;
+}
+template <class Q, class Fold>
+__device__ __forceinline__ void mx_q_tail_codes(int64_t col, int64_t P, Fold fold, const typename Q::Block& b,
+                                                uint8_t* outq) {
+    if constexpr (Q::kFp4) {
+        for (; col < P; col += 2) outq[col >> 1] = (uint8_t)(Q::one(fold(col), b) | Q::one(fold(col + 1), b) << 4);
+    } else {
+        for (; col < P; ++col) outq[col] = (uint8_t)Q::one(fold(col), b);
+    }
+}
+// One lane per column: the 32 lanes of a half-wave hold one block (a block of
+// kBlock lanes starts on a multiple of 32 columns).  Lanes past P carry 0 and
+// stay in the reduction; fp4 lanes pair their nibbles.
+template <class Q>
+__device__ __forceinline__ void mx_q_column(float q, bool valid, int64_t col, uint8_t* outq, uint8_t* oute) {
+    uint32_t m = valid ? mx_q_mag(q) : 0u;
+#pragma unroll
+    for (int d = 16; d > 0; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d));
+    const uint32_t E = Q::scale_byte(m);
+    const uint32_t code = Q::one(q, Q::prepare(E));
+    if constexpr (Q::kFp4) {
+        const uint32_t hi = (uint32_t)__shfl_xor((int)code, 1);
+        if (valid && !(col & 1)) outq[col >> 1] = (uint8_t)(code | hi << 4);
+    } else {
+        if (valid) outq[col] = (uint8_t)code;
+    }
+    if (valid && !(col & 31)) oute[col >> 5] = (uint8_t)E;
+}
+
 // The forms of the unit fold (bits of FORM).  kFp8Ahead: two groups of loads
 // alternate, the next group's loads issued before this group's converts and
 // adds, so a wave's arithmetic runs while its own loads are in flight (the
@@ -3235,11 +3385,18 @@ constexpr int kFp8Ahead = 1, kFp8Exchange = 2;
 constexpr int kFp8Form = kFp8Ahead | kFp8Exchange;  // the product's form
 
 // The lane's C units of rows 0..N-1 of src, in row order; o0 = its first unit in out / outb
-template <class F, int U, int C, bool SCORED, bool SCALED, int FORM, class Rows>
+// Q (an MxQ): the quotients also leave as MX codes in outq and scale bytes in
+// oute.  A block is the units of lanes 2k and 2k+1 (no: the row's full units);
+// the one unit whose block runs into the trailing columns calls tail_amax() /
+// tail_codes(block) for them.  Paired lanes must arrive here together.
+template <class F, int U, int C, bool SCORED, bool SCALED, int FORM, class Rows, class Q = MxQNone, class TA = int,
+          class TC = int>
 __device__ __forceinline__ void fold_fp8_units(Rows src, int64_t N, const float* __restrict__ a,
                                                const float* __restrict__ s, const float* __restrict__ sc,
                                                float divisor, float* __restrict__ out, uint16_t* __restrict__ outb,
-                                               int64_t o0, u32x4* wave_lds) {
+                                               int64_t o0, u32x4* wave_lds, Q = Q(), uint8_t* __restrict__ outq = nullptr,
+                                               uint8_t* __restrict__ oute = nullptr, int64_t no = 0,
+                                               TA tail_amax = TA(), TC tail_codes = TC()) {
     float acc[C][16];
     {
         const auto* r = src.row(0);
@@ -3328,6 +3485,17 @@ __device__ __forceinline__ void fold_fp8_units(Rows src, int64_t N, const float*
                 st16(o8 + k, b);
             }
         }
+        if constexpr (Q::kOn) {
+            uint32_t m = mx_q_amax(q);
+            const bool lone = (oc | 1) >= no;  // no partner unit: the block ends in the trailing columns
+            if (lone) m = max(m, tail_amax());
+            else m = max(m, (uint32_t)__shfl_xor((int)m, 1));
+            const uint32_t E = Q::scale_byte(m);
+            const typename Q::Block b = Q::prepare(E);
+            mx_q_codes<Q>(q, b, outq + oc * (2 * Q::kBits));
+            if (!(oc & 1)) oute[oc >> 1] = (uint8_t)E;
+            if (lone) tail_codes(b);
+        }
     }
 }
 
@@ -3389,6 +3557,61 @@ FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_fp8_scalar(
     const int64_t col = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (col >= P) return;
     st_column_bf16(fold_column_fp8<F, SCORED, SCALED>(src.column(col), N, a, s, sc, divisor), out, outb, col);
+}
+
+// The vector path with MX output (Q): out is optional.  A tile is full for all
+// of its lanes or for none, so the two lanes of a block take the same path.
+template <class F, int U, int C, bool SCORED, bool SCALED, int FORM, class Q, class Src>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_fp8_q_gs(
+    Src src, int64_t N, int64_t P, const float* __restrict__ a, const float* __restrict__ s,
+    const float* __restrict__ sc, float divisor, float* __restrict__ out, uint8_t* __restrict__ outq,
+    uint8_t* __restrict__ oute, int64_t ntiles) {
+    u32x4* wave_lds = nullptr;
+    if constexpr ((FORM & kFp8Exchange) != 0) {
+        __shared__ u32x4 lds[kBlock * 4];  // 64 lanes x 64 B per wave
+        wave_lds = lds + (threadIdx.x >> 6) * 256;
+    }
+    const int64_t no = P >> kFp8LG;
+    auto column = [&](int64_t col) { return fold_column_fp8<F, SCORED, SCALED>(src.column(col), N, a, s, sc, divisor); };
+    auto tail_amax = [&] { return mx_q_tail_amax(no << kFp8LG, P, column, out); };
+    auto tail_codes = [&](const typename Q::Block& b) { mx_q_tail_codes<Q>(no << kFp8LG, P, column, b, outq); };
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+        const int64_t o0 = bid * (kBlock * C) + threadIdx.x;
+        if ((bid + 1) * (kBlock * C) <= no) {
+            fold_fp8_units<F, U, C, SCORED, SCALED, FORM>(src.units(o0), N, a, s, sc, divisor, out, nullptr, o0, wave_lds,
+                                                          Q(), outq, oute, no, tail_amax, tail_codes);
+            continue;
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const int64_t o = o0 + (int64_t)c * kBlock;
+            if (o < no)
+                fold_fp8_units<F, U, 1, SCORED, SCALED, FORM>(src.units(o), N, a, s, sc, divisor, out, nullptr, o,
+                                                              wave_lds, Q(), outq, oute, no, tail_amax, tail_codes);
+        }
+        // an even count of full units: the trailing columns are a block of their own, the first idle lane's
+        if (!(no & 1) && (P & 15) && bid == no / (kBlock * C) && (int64_t)threadIdx.x == (no % (kBlock * C)) % kBlock) {
+            const uint32_t E = Q::scale_byte(tail_amax());
+            oute[no >> 1] = (uint8_t)E;
+            tail_codes(Q::prepare(E));
+        }
+    }
+}
+
+// One lane per column with MX output: every lane stays for its block's reduction
+template <class F, bool SCORED, bool SCALED, class Q, class Src>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_fp8_q_scalar(
+    Src src, int64_t N, int64_t P, const float* __restrict__ a, const float* __restrict__ s,
+    const float* __restrict__ sc, float divisor, float* __restrict__ out, uint8_t* __restrict__ outq,
+    uint8_t* __restrict__ oute) {
+    const int64_t col = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = col < P;
+    float q = 0.0f;
+    if (valid) {
+        q = fold_column_fp8<F, SCORED, SCALED>(src.column(col), N, a, s, sc, divisor);
+        if (out) out[col] = q;
+    }
+    mx_q_column<Q>(q, valid, col, outq, oute);
 }
 
 // ---------------------------------------------------------------------------
@@ -3587,11 +3810,15 @@ __device__ __forceinline__ void mx_group_add(float (&acc)[32], const u32x4 (&v)[
 }
 
 // The lane's block o0 of rows 0..N-1 of src, in row order
-template <class F, bool SCORED, bool SCALED, int FORM, class Rows>
+// Q (an MxQ): the block also leaves as MX codes in outq and its scale byte in
+// oute[o0]; the lane owns the whole block, so nothing crosses lanes but the
+// optional exchange of the fp8 codes' stores.
+template <class F, bool SCORED, bool SCALED, int FORM, class Rows, class Q = MxQNone>
 __device__ __forceinline__ void fold_mx_block(Rows src, int64_t N, const float* __restrict__ a,
                                               const float* __restrict__ s, const float* __restrict__ sc, float divisor,
                                               float* __restrict__ out, uint16_t* __restrict__ outb, int64_t o0,
-                                              u32x4* wave_lds) {
+                                              u32x4* wave_lds, Q = Q(), uint8_t* __restrict__ outq = nullptr,
+                                              uint8_t* __restrict__ oute = nullptr) {
     constexpr int U = F::kU;
     constexpr bool HW = (FORM & kMxHwScale) != 0;
     float acc[32];
@@ -3679,6 +3906,32 @@ __device__ __forceinline__ void fold_mx_block(Rows src, int64_t N, const float* 
             st16(o8 + k, b);
         }
     }
+    if constexpr (Q::kOn) {
+        const uint32_t E = Q::scale_byte(mx_q_amax(q));
+        const typename Q::Block b = Q::prepare(E);
+        oute[o0] = (uint8_t)E;
+        uint8_t* oq = outq + o0 * (4 * Q::kBits);
+        bool exchanged = false;
+        if constexpr (Q::kExchange && (FORM & kMxExchange) != 0) {
+            // wave-uniform: the wave's 64 blocks of codes are 2 KiB contiguous in outq
+            if (__builtin_amdgcn_ballot_w64(true) == ~0ull) {
+                const int lane = threadIdx.x & 63;
+#pragma unroll
+                for (int k = 0; k < 2; ++k)
+                    wave_lds[2 * lane + k] = u32x4{Q::word(&q[16 * k], b), Q::word(&q[16 * k + 4], b),
+                                                   Q::word(&q[16 * k + 8], b), Q::word(&q[16 * k + 12], b)};
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                u32x4* wave_out = reinterpret_cast<u32x4*>(oq) - 2 * lane;  // the block of lane 0
+#pragma unroll
+                for (int k = 0; k < 2; ++k) st16(wave_out + 64 * k + lane, wave_lds[64 * k + lane]);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                exchanged = true;
+            }
+        }
+        if (!exchanged) mx_q_codes<Q>(q, b, oq);
+    }
 }
 
 // One column, 8 rows of loads ahead of the ordered adds (a tail lane of the
@@ -3742,6 +3995,50 @@ FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_mx_scalar(
     if (col >= P) return;
     st_column_bf16(fold_column_mx<F, SCORED, SCALED, HW>(src.template column<F>(col), col, N, a, s, sc, divisor), out,
                    outb, col);
+}
+
+// The vector path with MX output (Q): out is optional; the trailing P % 32
+// columns are a partial block, one lane's
+template <class F, bool SCORED, bool SCALED, int FORM, class Q, class Src>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_mx_q_gs(
+    Src src, int64_t N, int64_t P, const float* __restrict__ a, const float* __restrict__ s,
+    const float* __restrict__ sc, float divisor, float* __restrict__ out, uint8_t* __restrict__ outq,
+    uint8_t* __restrict__ oute, int64_t ntiles) {
+    u32x4* wave_lds = nullptr;
+    if constexpr ((FORM & kMxExchange) != 0) {
+        __shared__ u32x4 lds[kBlock * 8];  // 64 lanes x 128 B per wave
+        wave_lds = lds + (threadIdx.x >> 6) * 512;
+    }
+    auto block = [&](int64_t o) {
+        fold_mx_block<F, SCORED, SCALED, FORM>(src.template block<F>(o), N, a, s, sc, divisor, out, nullptr, o, wave_lds,
+                                               Q(), outq, oute);
+    };
+    auto column = [&](int64_t col) {
+        return fold_column_mx<F, SCORED, SCALED, (FORM & kMxHwScale) != 0>(src.template column<F>(col), col, N, a, s, sc,
+                                                                          divisor);
+    };
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        octet_tile<1, kBlock, kMxLG>(bid, P, block, block, [&](int64_t col) {
+            const uint32_t E = Q::scale_byte(mx_q_tail_amax(col, P, column, out));
+            oute[col >> kMxLG] = (uint8_t)E;
+            mx_q_tail_codes<Q>(col, P, column, Q::prepare(E), outq);
+        });
+}
+
+// One lane per column with MX output: every lane stays for its block's reduction
+template <class F, bool SCORED, bool SCALED, bool HW, class Q, class Src>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_mx_q_scalar(
+    Src src, int64_t N, int64_t P, const float* __restrict__ a, const float* __restrict__ s,
+    const float* __restrict__ sc, float divisor, float* __restrict__ out, uint8_t* __restrict__ outq,
+    uint8_t* __restrict__ oute) {
+    const int64_t col = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = col < P;
+    float q = 0.0f;
+    if (valid) {
+        q = fold_column_mx<F, SCORED, SCALED, HW>(src.template column<F>(col), col, N, a, s, sc, divisor);
+        if (out) out[col] = q;
+    }
+    mx_q_column<Q>(q, valid, col, outq, oute);
 }
 
 // ---------------------------------------------------------------------------
@@ -5294,10 +5591,11 @@ int launch_fp8_fmt(int fmt, hipStream_t st, bool vec, Src src, int64_t N, int64_
 }
 
 // The checks of the stacked fold: *go = true to launch (false with FA_OK: nothing to fold)
+// (q_out: the required output of a quantising fold, which checks its own outputs' bytes)
 inline int fp8_fold_checks(int fmt, const uint8_t* X, int64_t N, int64_t P, int64_t ldx, const float* a,
-                           float* out_f32, uint16_t* out_bf16, bool* go) {
+                           float* out_f32, uint16_t* out_bf16, bool* go, const void* q_out = nullptr) {
     *go = false;
-    int rc = check_common(N, P, ldx, X, a, bf16_any_out(out_f32, out_bf16));
+    int rc = check_common(N, P, ldx, X, a, q_out ? q_out : bf16_any_out(out_f32, out_bf16));
     if (rc) return rc;
     if (fmt != FA_FP8_E4M3FN && fmt != FA_FP8_E5M2) return fail(FA_ERR_ARG, "unknown fp8 format %d", fmt);
     if (P == 0) { g_err[0] = 0; return FA_OK; }
@@ -5387,7 +5685,7 @@ inline int mx_format_check(int fmt, int64_t P) {
 
 // The checks of the stacked fold: *go = true to launch (false with FA_OK: nothing to fold)
 inline int mx_fold_checks(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
-                          const float* a, float* out_f32, uint16_t* out_bf16, bool* go) {
+                          const float* a, float* out_f32, uint16_t* out_bf16, bool* go, const void* q_out = nullptr) {
     *go = false;
     if (N < 0 || P < 0) return fail(FA_ERR_ARG, "negative size (N=%lld, P=%lld)", (long long)N, (long long)P);
     if (N == 0) return fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
@@ -5398,7 +5696,7 @@ inline int mx_fold_checks(int fmt, const uint8_t* X, const uint8_t* E, int64_t N
         return fail(FA_ERR_SHAPE, "row pitch ldx=%lld < %lld bytes or scale pitch lde=%lld < %lld bytes", (long long)ldx,
                     (long long)xb, (long long)lde, (long long)eb);
     if (P == 0) { g_err[0] = 0; return FA_OK; }
-    if (!X || !E || !a || !(out_f32 || out_bf16)) return fail(FA_ERR_ARG, "null X/E/a/out pointer");
+    if (!X || !E || !a || !(out_f32 || out_bf16 || q_out)) return fail(FA_ERR_ARG, "null X/E/a/out pointer");
     const size_t xbytes = (size_t)(N - 1) * ldx + xb, ebytes = (size_t)(N - 1) * lde + eb;
     for (int k = 0; k < 2; ++k) {
         const void* o = k ? (const void*)out_bf16 : (const void*)out_f32;
@@ -5438,6 +5736,176 @@ inline int mx_rows_fold(int fmt, const uint8_t* const* xi, const uint8_t* const*
                      [&](hipStream_t st) {
                          launch_mx_fmt<kMxForm>(fmt, st, rows_aligned != 0, MxTable{xi, ei}, N, P, a, s, c, divisor,
                                                 out_f32, out_bf16);
+                         return 0;
+                     });
+}
+
+// ---- MX output of the MX and fp8 folds (fa_fedavg_mx_q, fa_fedavg_fp8_q, _ptrs) --
+// The folds above with the quantising epilogue: the parents' geometry and
+// forms, the epilogue's form fixed here (DESIGN.md 5 MX output): behind the
+// clamp the hardware's scaled convert gives the contract's bytes for every
+// input scale byte times every element code (tests/test_gpu_mx_out.py), so the
+// product lets it divide: one VALU instruction per element fewer than the
+// multiply form.  The fp8 codes are stored directly, 32 B per lane.
+constexpr int kMxQForm = kMxQHwScale;
+
+// fn(MxQ<out_fmt, QFORM>()); out_fmt was checked
+template <int QFORM, class Fn>
+void with_mx_q(int out_fmt, Fn fn) {
+    if (out_fmt == FA_MX_E4M3) fn(MxQ<FA_MX_E4M3, QFORM>());
+    else if (out_fmt == FA_MX_E5M2) fn(MxQ<FA_MX_E5M2, QFORM>());
+    else fn(MxQ<FA_MX_E2M1, QFORM>());
+}
+
+// PLAIN (the bench library's forms): FedAvg without per-client scales only, the vector path only
+template <class F, int FORM, int QFORM, bool PLAIN, class Src>
+void launch_mx_q(hipStream_t st, bool vec, Src src, int64_t N, int64_t P, const float* a, const float* s,
+                 const float* c, float d, float* out, int out_fmt, uint8_t* outq, uint8_t* oute) {
+    const OctetGrid g = octet_grid(P, 1, -kMxBlocksPerCu, cu_count(), kMxLG);
+    auto launch = [&](auto SC, auto CS) {
+        with_mx_q<QFORM>(out_fmt, [&](auto q) {
+            constexpr bool kScored = decltype(SC)::value, kScaled = decltype(CS)::value;
+            typedef decltype(q) Q;
+            if (vec || PLAIN)
+                hipLaunchKernelGGL((k_fedavg_mx_q_gs<F, kScored, kScaled, FORM, Q, Src>), dim3((unsigned)g.grid),
+                                   dim3(kBlock), 0, st, src, N, P, a, s, c, d, out, outq, oute, g.tiles);
+            else if constexpr (!PLAIN)
+                hipLaunchKernelGGL((k_fedavg_mx_q_scalar<F, kScored, kScaled, (FORM & kMxHwScale) != 0, Q, Src>),
+                                   grid_for(P), dim3(kBlock), 0, st, src, N, P, a, s, c, d, out, outq, oute);
+        });
+    };
+    if constexpr (PLAIN) launch(std::false_type(), std::false_type());
+    else with_scored(s != nullptr, [&](auto SC) { with_scored(c != nullptr, [&](auto CS) { launch(SC, CS); }); });
+}
+template <int FORM, int QFORM, bool PLAIN = false, class Src>
+void launch_mx_q_fmt(int fmt, hipStream_t st, bool vec, Src src, int64_t N, int64_t P, const float* a, const float* s,
+                     const float* c, float d, float* out, int out_fmt, uint8_t* outq, uint8_t* oute) {
+    if (fmt == FA_MX_E4M3) launch_mx_q<MxE4M3, FORM, QFORM, PLAIN>(st, vec, src, N, P, a, s, c, d, out, out_fmt, outq, oute);
+    else if (fmt == FA_MX_E5M2)
+        launch_mx_q<MxE5M2, FORM, QFORM, PLAIN>(st, vec, src, N, P, a, s, c, d, out, out_fmt, outq, oute);
+    else launch_mx_q<MxE2M1, FORM, QFORM, PLAIN>(st, vec, src, N, P, a, s, c, d, out, out_fmt, outq, oute);
+}
+template <class F, int QFORM, class Src>
+void launch_fp8_q(hipStream_t st, bool vec, Src src, int64_t N, int64_t P, const float* a, const float* s,
+                  const float* c, float d, float* out, int out_fmt, uint8_t* outq, uint8_t* oute) {
+    const OctetGrid g = octet_grid(P, kFp8C, -Src::kBlocksPerCu, cu_count(), kFp8LG);
+    with_scored(s != nullptr, [&](auto SC) {
+        with_scored(c != nullptr, [&](auto CS) {
+            with_mx_q<QFORM>(out_fmt, [&](auto q) {
+                constexpr bool kScored = decltype(SC)::value, kScaled = decltype(CS)::value;
+                typedef decltype(q) Q;
+                if (vec)
+                    hipLaunchKernelGGL((k_fedavg_fp8_q_gs<F, kFp8U, kFp8C, kScored, kScaled, kFp8Form, Q, Src>),
+                                       dim3((unsigned)g.grid), dim3(kBlock), 0, st, src, N, P, a, s, c, d, out, outq,
+                                       oute, g.tiles);
+                else
+                    hipLaunchKernelGGL((k_fedavg_fp8_q_scalar<F, kScored, kScaled, Q, Src>), grid_for(P), dim3(kBlock),
+                                       0, st, src, N, P, a, s, c, d, out, outq, oute);
+            });
+        });
+    });
+}
+template <class Src>
+void launch_fp8_q_fmt(int fmt, hipStream_t st, bool vec, Src src, int64_t N, int64_t P, const float* a, const float* s,
+                      const float* c, float d, float* out, int out_fmt, uint8_t* outq, uint8_t* oute) {
+    if (fmt == FA_FP8_E4M3FN) launch_fp8_q<Fp8E4M3, kMxQForm>(st, vec, src, N, P, a, s, c, d, out, out_fmt, outq, oute);
+    else launch_fp8_q<Fp8E5M2, kMxQForm>(st, vec, src, N, P, a, s, c, d, out, out_fmt, outq, oute);
+}
+
+// The outputs of a quantising fold: the format, the required pointers, and no
+// two of out_f32 [P floats], out_q [P or P / 2 bytes], out_e [ceil(P / 32)] sharing bytes
+inline int mx_q_out_checks(const char* what, int out_fmt, int64_t P, const float* out_f32, const uint8_t* out_q,
+                           const uint8_t* out_e) {
+    if (out_fmt != FA_MX_E4M3 && out_fmt != FA_MX_E5M2 && out_fmt != FA_MX_E2M1)
+        return fail(FA_ERR_ARG, "%s: unknown MX output format %d", what, out_fmt);
+    if (out_fmt == FA_MX_E2M1 && (P & 1))
+        return fail(FA_ERR_ARG, "%s: an MXFP4 result holds two columns per byte: P=%lld is odd", what, (long long)P);
+    if (P <= 0) return FA_OK;
+    if (!out_q || !out_e) return fail(FA_ERR_ARG, "%s: null out_q / out_e pointer", what);
+    const size_t qb = (size_t)mx_row_bytes(out_fmt, P), eb = (size_t)mx_scale_bytes(P);
+    if (overlaps(out_q, qb, out_e, eb) ||
+        (out_f32 && (overlaps(out_f32, (size_t)P * 4, out_q, qb) || overlaps(out_f32, (size_t)P * 4, out_e, eb))))
+        return fail(FA_ERR_ARG, "%s: the outputs overlap one another", what);
+    return FA_OK;
+}
+// Does any output share bytes with [p, p + n)?
+inline bool mx_q_outs_overlap(int out_fmt, int64_t P, const float* out_f32, const uint8_t* out_q, const uint8_t* out_e,
+                              const void* p, size_t n) {
+    return (out_f32 && overlaps(out_f32, (size_t)P * 4, p, n)) ||
+           overlaps(out_q, (size_t)mx_row_bytes(out_fmt, P), p, n) || overlaps(out_e, (size_t)mx_scale_bytes(P), p, n);
+}
+
+// *go = true to launch (false with FA_OK: nothing to fold)
+inline int mx_q_fold_checks(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx,
+                            int64_t lde, const float* a, float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e,
+                            bool* go) {
+    int rc = mx_fold_checks(fmt, X, E, N, P, ldx, lde, a, out_f32, nullptr, go, out_q);
+    const bool launch = *go;
+    *go = false;
+    if (rc) return rc;
+    if ((rc = mx_q_out_checks("fa_fedavg_mx_q", out_fmt, P, out_f32, out_q, out_e))) return rc;
+    if (!launch) return FA_OK;
+    if (mx_q_outs_overlap(out_fmt, P, out_f32, out_q, out_e, X, (size_t)(N - 1) * ldx + mx_row_bytes(fmt, P)) ||
+        mx_q_outs_overlap(out_fmt, P, out_f32, out_q, out_e, E, (size_t)(N - 1) * lde + mx_scale_bytes(P)))
+        return fail(FA_ERR_ARG, "fa_fedavg_mx_q: an output overlaps the rows or their scales");
+    *go = true;
+    return FA_OK;
+}
+inline int mx_q_fold(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
+                     const float* a, const float* s, const float* c, float divisor, float* out_f32, int out_fmt,
+                     uint8_t* out_q, uint8_t* out_e, void* stream) {
+    bool go;
+    const int rc = mx_q_fold_checks(fmt, X, E, N, P, ldx, lde, a, out_f32, out_fmt, out_q, out_e, &go);
+    if (!go) return rc;
+    StreamDevice on_stream_device(stream);
+    launch_mx_q_fmt<kMxForm, kMxQForm>(fmt, (hipStream_t)stream, mx_vec(X, ldx, out_f32, nullptr) && aligned16(out_q),
+                                       MxPitched{X, E, ldx, lde}, N, P, a, s, c, divisor, out_f32, out_fmt, out_q, out_e);
+    return check_launch("fa_fedavg_mx_q");
+}
+inline int mx_q_rows_fold(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, int64_t N, int64_t P,
+                          const float* a, const float* s, const float* c, float divisor, int rows_aligned,
+                          float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e, void* stream) {
+    int rc = mx_format_check(fmt, P);
+    if (rc) return rc;
+    if ((rc = mx_q_out_checks("fa_fedavg_mx_q_ptrs", out_fmt, P, out_f32, out_q, out_e))) return rc;
+    if (P > 0 && !ei) return fail(FA_ERR_ARG, "null scale-row table");
+    const bool fits = !rows_aligned || (aligned16(out_f32) && aligned16(out_q));
+    return rows_fold("fa_fedavg_mx_q_ptrs", xi, N, P, a, out_q, stream,
+                     fits ? nullptr : "the vector path of the MX row-table fold needs 16-B aligned rows, out_f32 and out_q",
+                     [&](hipStream_t st) {
+                         launch_mx_q_fmt<kMxForm, kMxQForm>(fmt, st, rows_aligned != 0, MxTable{xi, ei}, N, P, a, s, c,
+                                                            divisor, out_f32, out_fmt, out_q, out_e);
+                         return 0;
+                     });
+}
+
+inline int fp8_q_fold(int fmt, const uint8_t* X, int64_t N, int64_t P, int64_t ldx, const float* a, const float* s,
+                      const float* c, float divisor, float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e,
+                      void* stream) {
+    bool go;
+    int rc = fp8_fold_checks(fmt, X, N, P, ldx, a, out_f32, nullptr, &go, out_q);
+    if (rc) return rc;
+    if ((rc = mx_q_out_checks("fa_fedavg_fp8_q", out_fmt, P, out_f32, out_q, out_e))) return rc;
+    if (!go) return FA_OK;
+    if (mx_q_outs_overlap(out_fmt, P, out_f32, out_q, out_e, X, (size_t)(N - 1) * ldx + P))
+        return fail(FA_ERR_ARG, "fa_fedavg_fp8_q: an output overlaps the rows");
+    StreamDevice on_stream_device(stream);
+    launch_fp8_q_fmt(fmt, (hipStream_t)stream, fp8_vec(X, ldx, out_f32, nullptr) && aligned16(out_q), Fp8Pitched{X, ldx},
+                     N, P, a, s, c, divisor, out_f32, out_fmt, out_q, out_e);
+    return check_launch("fa_fedavg_fp8_q");
+}
+inline int fp8_q_rows_fold(int fmt, const uint8_t* const* xi, int64_t N, int64_t P, const float* a, const float* s,
+                           const float* c, float divisor, int rows_aligned, float* out_f32, int out_fmt,
+                           uint8_t* out_q, uint8_t* out_e, void* stream) {
+    if (fmt != FA_FP8_E4M3FN && fmt != FA_FP8_E5M2) return fail(FA_ERR_ARG, "unknown fp8 format %d", fmt);
+    const int rc = mx_q_out_checks("fa_fedavg_fp8_q_ptrs", out_fmt, P, out_f32, out_q, out_e);
+    if (rc) return rc;
+    const bool fits = !rows_aligned || (aligned16(out_f32) && aligned16(out_q));
+    return rows_fold("fa_fedavg_fp8_q_ptrs", xi, N, P, a, out_q, stream,
+                     fits ? nullptr : "the vector path of the fp8 row-table fold needs 16-B aligned rows, out_f32 and out_q",
+                     [&](hipStream_t st) {
+                         launch_fp8_q_fmt(fmt, st, rows_aligned != 0, Fp8Table{xi}, N, P, a, s, c, divisor, out_f32,
+                                          out_fmt, out_q, out_e);
                          return 0;
                      });
 }

@@ -460,7 +460,8 @@ def _check_matrix(X: torch.Tensor) -> tuple[int, int, int]:
 def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] = None, *,
                  out: Optional[torch.Tensor] = None, want_bf16: bool = False, total=None,
                  exact: bool = True, out_bf16: Optional[torch.Tensor] = None, scales: Optional[Sequence] = None,
-                 block_scales: Optional[torch.Tensor] = None):
+                 block_scales: Optional[torch.Tensor] = None, out_format: Optional[torch.dtype] = None,
+                 out_mx=None):
     """FedAvg (scores None) / stall-aware fold over the rows of X, in row order.
 
     `total` overrides the divisor sum (used when zip() truncated the rows but
@@ -481,6 +482,13 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
     uint8, any pitch) with X [N, P] of float8_e4m3fn / float8_e5m2 or [N, P / 2]
     of float4_e2m1fn_x2; element p of row i counts as upcast(q) * 2^(E[i, p >>
     5] - 127), then scales= as for fp8 rows (MXLayer says the rest).
+    fp8 and MX rows: out_format= (float8_e4m3fn, float8_e5m2 or
+    float4_e2m1fn_x2) quantises the result to MX in the same launch
+    (fa_fedavg_fp8_q / fa_fedavg_mx_q; the contract is DESIGN.md 2's) and
+    returns MXLayer(q, e): q flat in that dtype, e [ceil(P / 32)]
+    float8_e8m0fnu, a valid MX row of a further fold.  out_mx=(q, e) supplies
+    the buffers; out= still receives the float32 result.  Not with want_bf16 /
+    out_bf16, nor with rows of another dtype.
     """
     N, P, ldx = _check_matrix(X)
     if len(weights) != N or (scores is not None and len(scores) != N):
@@ -488,9 +496,12 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
                                          + ("" if scores is None else f" / {len(scores)} scores"))
     dev = X.device
     if block_scales is not None or X.dtype == torch.float4_e2m1fn_x2:
-        return _fold_mx(X, block_scales, None, weights, scores, scales, out, total, want_bf16, out_bf16)
+        return _fold_mx(X, block_scales, None, weights, scores, scales, out, total, want_bf16, out_bf16, out_format,
+                        out_mx)
     if X.dtype in _FP8_FORMATS:
-        return _fold_fp8(X, None, weights, scores, scales, out, total, want_bf16, out_bf16)
+        return _fold_fp8(X, None, weights, scores, scales, out, total, want_bf16, out_bf16, out_format, out_mx)
+    if out_format is not None or out_mx is not None:
+        raise InvalidParameterShapeError(f"out_format / out_mx are for fp8 and MX rows, got {X.dtype}")
     if scales is not None:
         raise InvalidParameterShapeError(f"scales are for fp8 rows, got {X.dtype}")
     st = stream_ptr(dev)
@@ -1069,7 +1080,7 @@ _NO_CAPTURE_TABLE = (torch.float64, torch.int32, torch.int64)
 # MX folds (fa_fedavg_mx and fa_fedavg_mx_ptrs, likewise)
 stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0, "layer_table_folds": 0, "rows_int_folds": 0,
          "widened_folds": 0, "widened_row_folds": 0, "widened_table_folds": 0, "fp8_folds": 0,
-         "mx_folds": 0}
+         "mx_folds": 0, "mx_out_folds": 0}
 
 
 class RowSet:
@@ -1216,8 +1227,55 @@ def _fold_rows_bf16(rs: "RowSet", weights, scores, out, total, want_bf16, out_bf
     return out
 
 
+class _MXOut:
+    """The buffers of a fold's MX result (out_format= / out_mx= of fold_stacked
+    and fold_rows): the caller's, or fresh ones where it gave none or gave
+    buffers that share bytes with an input (clash), copied back by result()."""
+
+    def __init__(self, out_format, out_mx, P: int, dev, bf16: bool, clash):
+        if out_format is None:
+            out_format = out_mx[0].dtype
+        if out_format not in _MX_FORMATS:
+            raise InvalidParameterShapeError("out_format must be float8_e4m3fn, float8_e5m2 or float4_e2m1fn_x2, got "
+                                             f"{out_format}")
+        if bf16:
+            raise InvalidParameterShapeError("out_format gives an MX result: want_bf16 / out_bf16 do not go with it")
+        fp4 = out_format == torch.float4_e2m1fn_x2
+        if fp4 and P % 2:
+            raise InvalidParameterShapeError(f"a float4_e2m1fn_x2 result holds two columns per byte: {P} columns")
+        nq, nb = (P // 2 if fp4 else P), (P + 31) // 32
+        self.fmt, self.dst = _MX_FORMATS[out_format], out_mx
+        if out_mx is not None:
+            q, e = out_mx
+            if not (isinstance(q, torch.Tensor) and q.dtype == out_format and q.device == dev and q.is_contiguous()
+                    and q.numel() == nq):
+                raise InvalidParameterShapeError(f"out_mx[0] must be a contiguous {out_format} tensor of {nq} elements "
+                                                 f"on {dev}")
+            if not (isinstance(e, torch.Tensor) and e.dtype in _MX_SCALE_DTYPES and e.device == dev
+                    and e.is_contiguous() and e.numel() == nb):
+                raise InvalidParameterShapeError(f"out_mx[1] must hold {nb} contiguous E8M0 bytes (float8_e8m0fnu or "
+                                                 f"uint8) on {dev}")
+        self.fresh = out_mx is None or clash(out_mx[0]) or clash(out_mx[1])
+        if self.fresh:
+            self.q = torch.empty(nq, dtype=torch.uint8, device=dev).view(out_format)
+            self.e = torch.empty(nb, dtype=torch.uint8, device=dev).view(torch.float8_e8m0fnu)
+        else:
+            self.q, self.e = out_mx[0].reshape(-1), out_mx[1].reshape(-1)
+
+    def args(self):
+        return self.fmt, self.q.data_ptr(), self.e.data_ptr()
+
+    def result(self) -> "MXLayer":
+        stats["mx_out_folds"] += 1
+        if self.dst is not None and self.fresh:
+            self.dst[0].view(torch.uint8).reshape(-1).copy_(self.q.view(torch.uint8))
+            self.dst[1].view(torch.uint8).reshape(-1).copy_(self.e.view(torch.uint8))
+            return MXLayer(self.dst[0].reshape(-1), self.dst[1].reshape(-1))
+        return MXLayer(self.q, self.e)
+
+
 def _fold_fp8(X: Optional[torch.Tensor], rs: Optional["RowSet"], weights, scores, scales, out, total, want_bf16,
-              out_bf16):
+              out_bf16, out_format=None, out_mx=None):
     """fp8 rows, a stacked [N, P] matrix X (fa_fedavg_fp8) or the row table of
     rs (fa_fedavg_fp8_ptrs): float32 factors and scales in ONE staged upload,
     the bf16 fold's outputs.  The outputs are wider than the rows, so one that
@@ -1243,13 +1301,16 @@ def _fold_fp8(X: Optional[torch.Tensor], rs: Optional["RowSet"], weights, scores
         lo, hi = t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
         return lo < X.data_ptr() + (N - 1) * ldx + P and X.data_ptr() < hi
 
+    qo = None
+    if out_format is not None or out_mx is not None:
+        qo = _MXOut(out_format, out_mx, P, dev, want_bf16 or out_bf16 is not None, clash)
     dst, dstb = out, out_bf16
     if clash(out):
         out = None
     outb = None if clash(out_bf16) else out_bf16
     if outb is None and (want_bf16 or out_bf16 is not None):
         outb = torch.empty(P, dtype=torch.bfloat16, device=dev)
-    if out is None and (dst is not None or outb is None or want_bf16):
+    if out is None and (dst is not None or (outb is None and qo is None) or want_bf16):
         out = torch.empty(P, dtype=torch.float32, device=dev)
     f = Factors.weak_f32(weights, scores, total) or Factors(weights, scores, _F32, total=total)
     parts = [f.a] if f.s is None else [f.a, f.s]
@@ -1259,7 +1320,14 @@ def _fold_fp8(X: Optional[torch.Tensor], rs: Optional["RowSet"], weights, scores
     staged = stage_factors(parts, dev)
     a, s = staged[0], (staged[1] if f.s is not None else None)
     c = staged[-1] if scales is not None else None
-    if X is not None:
+    if qo is not None and X is not None:
+        _lib.call("fa_fedavg_fp8_q", fmt, X.data_ptr(), N, P, ldx, a.data_ptr(), _ptr(s), _ptr(c), float(f.div),
+                  _ptr(out), *qo.args(), stream_ptr(dev))
+    elif qo is not None:
+        aligned = rs.aligned and (out is None or out.data_ptr() % 16 == 0) and qo.q.data_ptr() % 16 == 0
+        _lib.call("fa_fedavg_fp8_q_ptrs", fmt, rs.ptrs.data_ptr(), N, P, a.data_ptr(), _ptr(s), _ptr(c), float(f.div),
+                  int(aligned), _ptr(out), *qo.args(), stream_ptr(dev))
+    elif X is not None:
         _lib.call("fa_fedavg_fp8", fmt, X.data_ptr(), N, P, ldx, a.data_ptr(), _ptr(s), _ptr(c), float(f.div),
                   _ptr(out), _ptr(outb), stream_ptr(dev))
     else:
@@ -1274,6 +1342,8 @@ def _fold_fp8(X: Optional[torch.Tensor], rs: Optional["RowSet"], weights, scores
     if dstb is not None and dstb is not outb:
         dstb.reshape(-1)[:P].copy_(outb)
         outb = dstb
+    if qo is not None:
+        return qo.result()
     if want_bf16:
         return out, outb
     if out_bf16 is not None:
@@ -1282,7 +1352,7 @@ def _fold_fp8(X: Optional[torch.Tensor], rs: Optional["RowSet"], weights, scores
 
 
 def _fold_mx(X: Optional[torch.Tensor], E: Optional[torch.Tensor], rs: Optional["RowSet"], weights, scores, scales,
-             out, total, want_bf16, out_bf16):
+             out, total, want_bf16, out_bf16, out_format=None, out_mx=None):
     """MX rows, a stacked byte matrix X with its scale bytes E (fa_fedavg_mx) or
     the 2N-pointer table of rs (fa_fedavg_mx_ptrs): float32 factors and scales
     in ONE staged upload, the bf16 fold's outputs.  Everything is decided here
@@ -1326,13 +1396,16 @@ def _fold_mx(X: Optional[torch.Tensor], E: Optional[torch.Tensor], rs: Optional[
         lo, hi = t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
         return any(lo < p + n and p < hi for p, n in spans)
 
+    qo = None
+    if out_format is not None or out_mx is not None:
+        qo = _MXOut(out_format, out_mx, P, dev, want_bf16 or out_bf16 is not None, clash)
     dst, dstb = out, out_bf16
     if clash(out):
         out = None
     outb = None if clash(out_bf16) else out_bf16
     if outb is None and (want_bf16 or out_bf16 is not None):
         outb = torch.empty(P, dtype=torch.bfloat16, device=dev)
-    if out is None and (dst is not None or outb is None or want_bf16):
+    if out is None and (dst is not None or (outb is None and qo is None) or want_bf16):
         out = torch.empty(P, dtype=torch.float32, device=dev)
     f = Factors.weak_f32(weights, scores, total) or Factors(weights, scores, _F32, total=total)
     parts = [f.a] if f.s is None else [f.a, f.s]
@@ -1342,7 +1415,15 @@ def _fold_mx(X: Optional[torch.Tensor], E: Optional[torch.Tensor], rs: Optional[
     staged = stage_factors(parts, dev)
     a, s = staged[0], (staged[1] if f.s is not None else None)
     c = staged[-1] if scales is not None else None
-    if X is not None:
+    if qo is not None and X is not None:
+        _lib.call("fa_fedavg_mx_q", fmt, X.data_ptr(), E.data_ptr(), N, P, ldx, lde, a.data_ptr(), _ptr(s), _ptr(c),
+                  float(f.div), _ptr(out), *qo.args(), stream_ptr(dev))
+    elif qo is not None:
+        aligned = rs.aligned and (out is None or out.data_ptr() % 16 == 0) and qo.q.data_ptr() % 16 == 0
+        xi = rs.ptrs.data_ptr() if P else 0
+        _lib.call("fa_fedavg_mx_q_ptrs", fmt, xi, xi + 8 * N, N, P, a.data_ptr(), _ptr(s), _ptr(c), float(f.div),
+                  int(aligned), _ptr(out), *qo.args(), stream_ptr(dev))
+    elif X is not None:
         _lib.call("fa_fedavg_mx", fmt, X.data_ptr(), E.data_ptr(), N, P, ldx, lde, a.data_ptr(), _ptr(s), _ptr(c),
                   float(f.div), _ptr(out), _ptr(outb), stream_ptr(dev))
     else:
@@ -1358,6 +1439,8 @@ def _fold_mx(X: Optional[torch.Tensor], E: Optional[torch.Tensor], rs: Optional[
     if dstb is not None and dstb is not outb:
         dstb.reshape(-1)[:P].copy_(outb)
         outb = dstb
+    if qo is not None:
+        return qo.result()
     if want_bf16:
         return out, outb
     if out_bf16 is not None:
@@ -1460,7 +1543,8 @@ def _fold_rows_widen(rs: "RowSet", kind: int, f: Factors, out):
 def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
               out: Optional[torch.Tensor] = None, total=None, want_bf16: bool = False,
               out_bf16: Optional[torch.Tensor] = None, scales: Optional[Sequence] = None,
-              block_scales: Optional[Sequence[torch.Tensor]] = None):
+              block_scales: Optional[Sequence[torch.Tensor]] = None, out_format: Optional[torch.dtype] = None,
+              out_mx=None):
     """The fold over separately allocated 1-D CUDA rows (no stacking copy for
     fp32, bfloat16, float16 / float64 rows whose result stays in their dtype,
     int32 / int64 rows whose products stay in their dtype: int_row_factors, and
@@ -1470,7 +1554,8 @@ def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
     built for this call).  want_bf16 / out_bf16: as fold_stacked (bf16 and
     fp8 rows); scales: as fold_stacked (fp8 rows, folded through their own row
     table); block_scales: the rows are MX rows, block_scales[i] row i's E8M0
-    bytes (RowSet's block_scales=; a RowSet built with them needs none here)."""
+    bytes (RowSet's block_scales=; a RowSet built with them needs none here);
+    out_format / out_mx: as fold_stacked (fp8 and MX rows)."""
     rs = rows if isinstance(rows, RowSet) else RowSet(rows, block_scales)
     if len(weights) != rs.N or (scores is not None and len(scores) != rs.N):
         raise InvalidParameterShapeError(f"{rs.N} rows but {len(weights)} weights"
@@ -1478,15 +1563,17 @@ def fold_rows(rows, weights: Sequence, scores: Optional[Sequence] = None, *,
     if rs.scale_rows is not None:
         if block_scales is not None and rs is rows:
             raise InvalidParameterShapeError("this RowSet already holds its block_scales")
-        return _fold_mx(None, None, rs, weights, scores, scales, out, total, want_bf16, out_bf16)
+        return _fold_mx(None, None, rs, weights, scores, scales, out, total, want_bf16, out_bf16, out_format, out_mx)
     if block_scales is not None or rs.dtype == torch.float4_e2m1fn_x2:
         raise InvalidParameterShapeError(f"{rs.dtype} rows and block_scales: build the RowSet with block_scales=")
     if rs.dtype in _FP8_FORMATS:
         if rs.view is not None or rs.P == 0:
             # rows of one allocation at a fixed pitch (or no columns): the stacked fold, no pointer table
             X = rs.view if rs.view is not None else torch.empty((rs.N, 0), dtype=rs.dtype, device=rs.device)
-            return _fold_fp8(X, None, weights, scores, scales, out, total, want_bf16, out_bf16)
-        return _fold_fp8(None, rs, weights, scores, scales, out, total, want_bf16, out_bf16)
+            return _fold_fp8(X, None, weights, scores, scales, out, total, want_bf16, out_bf16, out_format, out_mx)
+        return _fold_fp8(None, rs, weights, scores, scales, out, total, want_bf16, out_bf16, out_format, out_mx)
+    if out_format is not None or out_mx is not None:
+        raise InvalidParameterShapeError(f"out_format / out_mx are for fp8 and MX rows, got {rs.dtype}")
     if scales is not None:
         raise InvalidParameterShapeError(f"scales are for fp8 rows, got {rs.dtype}")
     if out_bf16 is not None and rs.dtype != torch.bfloat16:
@@ -1939,7 +2026,8 @@ def _multi(devices) -> Optional[list]:
 
 
 def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: Optional[Sequence] = None,
-                     device: Optional[torch.device] = None, devices=None) -> List:
+                     device: Optional[torch.device] = None, devices=None, *,
+                     out_format: Optional[torch.dtype] = None) -> List:
     """Reference-shaped FedAvg / stall-aware aggregation.
 
     parameters: N clients x L layers (numpy arrays, or CUDA tensors).  Returns
@@ -1961,6 +2049,12 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
     layers are given as MXLayer(q, e, scale=None) by every client and fold the
     same way (fa_fedavg_mx_ptrs); a float4 layer's result has its last
     dimension doubled.
+
+    out_format (float8_e4m3fn, float8_e5m2, float4_e2m1fn_x2): every layer
+    must be a device fp8 or MX layer, and each comes back as MXLayer(q, e)
+    quantised in its fold's launch (fold_stacked's out_format=): q in the
+    layer's logical shape, the last dimension halved for a float4 result, e the
+    ceil(size / 32) scale bytes of the flattened layer.
     """
     multi = _multi(devices)
     if multi is not None and device is None:
@@ -1988,6 +2082,13 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
             raise InvalidParameterShapeError(f"layer {li}: fp8 rows fold only with rows of their own format, every "
                                              f"client's alike; got {sorted(set(map(str, dt)))}")
     on_device = isinstance(parameters[0][0], torch.Tensor)
+    if out_format is not None:
+        if out_format not in _MX_FORMATS:
+            raise InvalidParameterShapeError("out_format must be float8_e4m3fn, float8_e5m2 or float4_e2m1fn_x2, got "
+                                             f"{out_format}")
+        for li, dt in enumerate(dtypes):
+            if dt not in _MX_FORMATS or not (on_device and parameters[0][li].is_cuda):
+                raise InvalidParameterShapeError(f"layer {li}: out_format is for device fp8 and MX layers, got {dt}")
     dev = device or (parameters[0][0].device if on_device else default_device())
     w = list(weights[:n_eff])
     sc = None if scores is None else list(scores[:n_eff])
@@ -2005,11 +2106,21 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
                 if li in layer_mx:
                     es, cs = layer_mx[li]
                     shp = shapes[li][:-1] + (_mx_cols(dtypes[li], shapes[li][-1]),) if shapes[li] else ()
-                    outs[li] = fold_rows(rows, w, sc, total=sum(total_weights), scales=cs,
-                                         block_scales=es).reshape(shp)
-                    continue
-                outs[li] = fold_rows(rows, w, sc, total=sum(total_weights),
-                                     scales=layer_scales.get(li)).reshape(shapes[li])
+                    res = fold_rows(rows, w, sc, total=sum(total_weights), scales=cs, block_scales=es,
+                                    out_format=out_format)
+                else:
+                    shp = shapes[li]
+                    res = fold_rows(rows, w, sc, total=sum(total_weights), scales=layer_scales.get(li),
+                                    out_format=out_format)
+                if out_format is None:
+                    outs[li] = res.reshape(shp)
+                elif out_format == torch.float4_e2m1fn_x2:
+                    if not shp or shp[-1] % 2:
+                        raise InvalidParameterShapeError(f"layer {li}: a float4_e2m1fn_x2 result packs pairs of the last "
+                                                         f"dimension: shape {shp}")
+                    outs[li] = MXLayer(res.q.reshape(shp[:-1] + (shp[-1] // 2,)), res.e)
+                else:
+                    outs[li] = MXLayer(res.q.reshape(shp), res.e)
             continue
         fp32_result = result_dtype(np.dtype(np.float32), total_weights, sc) == np.float32
         if isinstance(dtypes[lis[0]], tuple):

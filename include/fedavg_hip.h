@@ -703,7 +703,7 @@ int fa_fedavg_widen_layers(int kind, const void* const* xi, const fa_layer_plan*
  * contiguous; the P % 16 trailing columns fold in one lane.  Argument checks and status codes as fa_fedavg_bf16 /
  * fa_fedavg_bf16_ptrs; an unknown fmt -> FA_ERR_ARG.  Neither allocates nor
  * synchronises.  Not covered: host rows, the layer tables, the sharded step,
- * a tuner kind, the fnuz formats, fp8 output, block scales. */
+ * a tuner kind, the fnuz formats, block scales.  MX output: fa_fedavg_fp8_q below. */
 #define FA_FP8_E4M3FN 0
 #define FA_FP8_E5M2 1
 #define FA_FP8_TILE_COLS 8192
@@ -757,7 +757,7 @@ int fa_fedavg_fp8_ptrs(int fmt, const uint8_t* const* xi, int64_t N, int64_t P,
  * through LDS so that each store instruction writes 1 KiB contiguous; the
  * P % 32 trailing columns fold in one lane.  Neither allocates nor
  * synchronises.  Not covered: host rows, the layer tables, the sharded step,
- * stream capture, a tuner kind, MXFP6, NVFP4, quantised output. */
+ * stream capture, a tuner kind, MXFP6, NVFP4.  MX output: fa_fedavg_mx_q below. */
 #define FA_MX_E4M3 0
 #define FA_MX_E5M2 1
 #define FA_MX_E2M1 2
@@ -770,6 +770,54 @@ int fa_fedavg_mx(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t
 int fa_fedavg_mx_ptrs(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, int64_t N, int64_t P,
                       const float* a, const float* s, const float* c, float divisor, int rows_aligned,
                       float* out_f32, uint16_t* out_bf16, void* stream);
+
+/* ---- MX output of the MX and fp8 folds (new symbols, ABI still 7) -------------
+ * The folds above with their result quantised to MX in the same launch: the
+ * arguments of fa_fedavg_mx / _mx_ptrs / _fp8 / _fp8_ptrs with out_bf16
+ * replaced by the result's element format out_fmt (FA_MX_*), its codes out_q
+ * [P bytes, MXFP4: P / 2] and its scale bytes out_e [ceil(P / 32)], both
+ * required.  out_f32 [P] stays an optional further output with the parent's
+ * bits.  The result is a valid input row of fa_fedavg_mx.
+ * Let v[j] be the float32 quotients of block b, flat columns [32b, 32b + 32)
+ * (fewer in a last partial block), bit for bit what out_f32 holds.  emax is 8
+ * (e4m3), 15 (e5m2), 2 (e2m1); maxnorm 448, 57344, 6.
+ *   any v[j] NaN or +-inf:  out_e[b] = 255, every code of the block 0x00
+ *   else  amax = max |v[j]|, eb = amax's float32 exponent field (0 for zero
+ *         and subnormals)
+ *         out_e[b] = E = max(eb - emax, 0)      never above 252
+ *         y    = v[j] / 2^(E-127)               exact, or below every F's range
+ *         code = RNE_F(y), F's subnormals included; |y| > maxnorm saturates to
+ *                +-maxnorm (no inf or NaN code is written); the code's sign
+ *                bit is v[j]'s, for zeros and -0 too; float32 subnormal
+ *                quotients are not flushed
+ * e2m1 codes are packed two per byte, the even column in the low nibble.
+ * Checks as the parents'; further an unknown out_fmt, an e2m1 result with odd
+ * P, an output that overlaps X, E or another output -> FA_ERR_ARG (the _ptrs
+ * entries cannot see their rows: no output may overlap one).  The vector path
+ * needs out_q, and out_f32 if given, 16-B aligned (stacked: else one column
+ * per lane; _ptrs with rows_aligned != 0: FA_ERR_ARG); out_e at any alignment.
+ * The same bits on either path.  Geometry: an MX source's lane owns the block
+ * and quantises it alone (one 16-byte store of e2m1 codes or two of fp8 codes
+ * per lane, 64 contiguous scale bytes per wave); an fp8 source's block is the
+ * 16-column units of two adjacent lanes, which exchange their amax in one
+ * shuffle; a block that ends in the trailing columns is one lane's; the
+ * one-column kernels reduce the amax over the 32 lanes of a half-wave.
+ * Neither entry allocates nor synchronises.  Not covered: MX output of the
+ * float32 / bf16 / float16 / float64 folds, fp8 output with a per-tensor scale,
+ * the layer tables, the sharded step, stream capture, MXFP6, NVFP4, stochastic
+ * rounding. */
+int fa_fedavg_mx_q(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P,
+                   int64_t ldx, int64_t lde, const float* a, const float* s, const float* c, float divisor,
+                   float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e, void* stream);
+int fa_fedavg_mx_q_ptrs(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, int64_t N, int64_t P,
+                        const float* a, const float* s, const float* c, float divisor, int rows_aligned,
+                        float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e, void* stream);
+int fa_fedavg_fp8_q(int fmt, const uint8_t* X, int64_t N, int64_t P, int64_t ldx,
+                    const float* a, const float* s, const float* c, float divisor,
+                    float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e, void* stream);
+int fa_fedavg_fp8_q_ptrs(int fmt, const uint8_t* const* xi, int64_t N, int64_t P,
+                         const float* a, const float* s, const float* c, float divisor, int rows_aligned,
+                         float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e, void* stream);
 
 /* ---- host staging: page-locked documents and direct DMA ---------------------
  * A result store that keeps documents in page-locked memory lets the ingest

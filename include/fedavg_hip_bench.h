@@ -128,6 +128,18 @@ int fa_fedavg_fp8_form(const uint8_t* X, int64_t N, int64_t P, int64_t ldx, cons
 int fa_fedavg_mx_form(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
                       const float* a, const float* s, const float* c, float divisor, float* out_f32,
                       uint16_t* out_bf16, void* stream, int form, int blocks_per_cu);
+/* The vector path of fa_fedavg_mx_q (FedAvg, no per-client scales) in one form
+ * of the quantising epilogue: bit 0 = a full wave's fp8 codes exchanged
+ * through LDS (1 KiB contiguous per store instruction; nothing for an e2m1
+ * result), bit 1 = the division by the block's scale made by the hardware's
+ * scaled convert instead of an IEEE multiply, form 4 = form 0 with the codes'
+ * sign bits written from the quotients'.  Forms 0..4; which of them give the
+ * contract's bits, and their times: DESIGN.md 5 MX output.  X, out_f32 and
+ * out_q 16-B aligned, ldx % 16 == 0, else FA_ERR_ARG; the other checks as
+ * fa_fedavg_mx_q.  tools/mx_out_bench.py --forms. */
+int fa_fedavg_mx_q_form(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
+                        const float* a, float divisor, float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e,
+                        void* stream, int qform);
 /* The layer-table folds (fa_fedavg_*_layers) with the units per lane of the
  * caller's plan (fa_layers_plan with units = 1, 2 or 4) and a cap on the grid
  * (grid_cap > 0: at most that many blocks, so small models take several
