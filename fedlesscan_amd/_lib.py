@@ -39,6 +39,7 @@ FA_FP8_TILE_COLS, FA_FP8_ROWS_AHEAD = 8192, 8
 # fa_fedavg_mx's formats (FA_MX_* of the header), its tile's columns, the rows of loads ahead per format
 FA_MX_E4M3, FA_MX_E5M2, FA_MX_E2M1 = range(3)
 FA_MX_TILE_COLS, FA_MX_ROWS_AHEAD_FP8, FA_MX_ROWS_AHEAD_FP4 = 8192, 8, 16
+FA_MX_WAVE_TILE_COLS = 2048  # the wave tile of the MX layer tables (fa_fedavg_mx_layers)
 
 _i64 = ctypes.c_int64
 _vp = ctypes.c_void_p
@@ -115,6 +116,10 @@ _PROTOS = {
     "fa_fedavg_mx_q_ptrs": (_int, [_int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _int, _vp, _vp, _vp]),
     "fa_fedavg_fp8_q": (_int, [_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _int, _vp, _vp, _vp]),
     "fa_fedavg_fp8_q_ptrs": (_int, [_int, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _int, _vp, _vp, _vp]),
+    "fa_mx_layers_plan": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "fa_fedavg_mx_layers": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "fa_fedavg_mx_q_layers": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _int, _vp, _vp,
+                                     _vp]),
     "fa_npz_index":(_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _int]),
     "fa_crc32": (_int, [_vp, _i64, ctypes.c_uint32, _int, ctypes.POINTER(ctypes.c_uint32)]),
     "fa_pack": (_int, [_vp, _vp, _vp, _vp, _i64, _int]),
@@ -189,6 +194,9 @@ _BENCH_PROTOS = {
     "fa_fedavg_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp, _vp]),
     "fa_fedavg_int_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp]),
     "fa_fedavg_widen_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp]),
+    "fa_fedavg_mx_layers_form": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64]),
+    "fa_fedavg_mx_q_layers_form": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _int, _vp,
+                                          _vp, _vp, _i64]),
     "fa_fedavg_bf16_variant": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _int]),
     "fa_num_bf16_variants": (_int, []),
     "fa_bf16_variant_name": (ctypes.c_char_p, [_int]),

@@ -632,6 +632,26 @@ int fa_fedavg_i64_layers(const int64_t* const* xi, const fa_layer_plan* plan, in
                                       stream);
 }
 
+// ---- every MX layer of a device-resident model in one launch (mx_layers_fold) ----
+int fa_mx_layers_plan(const int64_t* cols, const int32_t* aligned, int64_t L, fa_layer_plan* plan, int64_t* tiles,
+                      int64_t* elems) {
+    return mx_layers_plan(cols, aligned, L, plan, tiles, elems);
+}
+
+int fa_fedavg_mx_layers(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, const fa_layer_plan* plan,
+                        int64_t L, int64_t N, int64_t tiles, const float* a, const float* s, const float* c,
+                        float divisor, float* out_f32, uint16_t* out_bf16, void* stream) {
+    return mx_layers_fold("fa_fedavg_mx_layers", fmt, xi, ei, plan, L, N, tiles, 0, a, s, c, divisor, out_f32, out_bf16,
+                          stream);
+}
+
+int fa_fedavg_mx_q_layers(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, const fa_layer_plan* plan,
+                          int64_t L, int64_t N, int64_t tiles, const float* a, const float* s, const float* c,
+                          float divisor, float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e, void* stream) {
+    return mx_q_layers_fold("fa_fedavg_mx_q_layers", fmt, xi, ei, plan, L, N, tiles, 0, a, s, c, divisor, out_f32,
+                            out_fmt, out_q, out_e, stream);
+}
+
 // ---- promoted folds from the narrow rows (widen_fold) ------------------------
 int fa_fedavg_widen(int kind, const void* X, int64_t N, int64_t P, int64_t ldx, const void* a, const void* s,
                     double divisor, void* out, void* stream) {

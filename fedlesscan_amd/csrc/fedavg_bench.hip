@@ -748,6 +748,19 @@ int fa_fedavg_widen_layers_form(int kind, const void* const* xi, const fa_layer_
     return widen_layers_fold("fa_fedavg_widen_layers_form", kind, xi, plan, L, N, tiles, units, grid_cap, a, s, divisor,
                              out, stream);
 }
+int fa_fedavg_mx_layers_form(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, const fa_layer_plan* plan,
+                             int64_t L, int64_t N, int64_t tiles, const float* a, const float* s, const float* c,
+                             float divisor, float* out_f32, uint16_t* out_bf16, void* stream, int64_t grid_cap) {
+    return mx_layers_fold("fa_fedavg_mx_layers_form", fmt, xi, ei, plan, L, N, tiles, grid_cap, a, s, c, divisor,
+                          out_f32, out_bf16, stream);
+}
+int fa_fedavg_mx_q_layers_form(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, const fa_layer_plan* plan,
+                               int64_t L, int64_t N, int64_t tiles, const float* a, const float* s, const float* c,
+                               float divisor, float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e,
+                               void* stream, int64_t grid_cap) {
+    return mx_q_layers_fold("fa_fedavg_mx_q_layers_form", fmt, xi, ei, plan, L, N, tiles, grid_cap, a, s, c, divisor,
+                            out_f32, out_fmt, out_q, out_e, stream);
+}
 const char* fa_variant_name(int variant) {
     return (variant >= 0 && variant < kNumVariants) ? kVariants[variant] : "";
 }

@@ -4042,6 +4042,121 @@ FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_mx_q_scalar(
 }
 
 // ---------------------------------------------------------------------------
+// The MX layer tables (fa_fedavg_mx_layers, fa_fedavg_mx_q_layers): every MX
+// layer of a device-resident model in one launch (DESIGN.md 5 MX layer table).
+// In k_fedavg_mx_gs nothing but the grid-stride loop is shared between the
+// waves of a block -- a lane owns its MX block, the exchange buffer is a
+// wave's own and fenced with wave barriers -- so the plan's tile is a WAVE
+// tile: kMxWaveCols = 64 MX blocks = 2048 columns of one layer, where a tile of
+// kMxTileCols would leave 254 of 256 lanes idle on a 64-element bias.  A block
+// takes four consecutive wave tiles, which may lie in four layers; there is no
+// __syncthreads.  Each wave makes its tile index uniform, finds the layer by
+// layer_tile's search over plan[].tile0 (scalar loads; the search starts at
+// the layer of the wave's previous tile) and runs the row-table fold's own
+// bodies over that layer's xi + l*N, ei + l*N and c + l*N: fold_mx_block for
+// the full blocks, fold_column_mx for the cols % 32 trailing columns (the lane
+// after the last full block), so layer l holds the bits of k_fedavg_mx_gs /
+// k_fedavg_mx_q_gs on that layer alone.  A layer with a data row off 16-B
+// alignment is tiled one column per lane, 64 columns per wave tile, with the
+// bodies of the one-column kernels; a wave tile starts at a multiple of 64
+// columns, so mx_q_column's half-wave still holds one block.  The outputs are
+// flat: layer l at plan[l].offset elements of out / outb, offset >> colLg
+// bytes of outq and offset >> 5 bytes of oute.  No arithmetic is new.
+// ---------------------------------------------------------------------------
+constexpr int kMxWave = 64;                       // lanes, and MX blocks, per wave tile
+constexpr int kMxWaveCols = kMxWave << kMxLG;     // columns of an aligned layer's wave tile
+constexpr int kMxWavesPerBlock = kBlock / kMxWave;
+
+template <class F, bool SCORED, bool SCALED, int FORM, class Q>
+__device__ __forceinline__ void mx_layers_walk(const uint8_t* const* __restrict__ xi,
+                                               const uint8_t* const* __restrict__ ei,
+                                               const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N,
+                                               const float* __restrict__ a, const float* __restrict__ s,
+                                               const float* __restrict__ c, float divisor, float* __restrict__ out,
+                                               uint16_t* __restrict__ outb, uint8_t* __restrict__ outq,
+                                               uint8_t* __restrict__ oute, int64_t ntiles) {
+    constexpr bool HW = (FORM & kMxHwScale) != 0;
+    u32x4* wave_lds = nullptr;
+    if constexpr ((FORM & kMxExchange) != 0) {
+        __shared__ u32x4 lds[kBlock * 8];  // 64 lanes x 128 B per wave
+        wave_lds = lds + (threadIdx.x >> 6) * 512;
+    }
+    const int lane = threadIdx.x & (kMxWave - 1);
+    // the wave's tile index, the same in every lane: the search below is scalar loads and compares
+    const int64_t w0 = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)(blockIdx.x * kMxWavesPerBlock + (threadIdx.x >> 6)));
+    const int64_t step = (int64_t)gridDim.x * kMxWavesPerBlock;
+    int64_t l = 0;
+    for (int64_t wt = w0; wt < ntiles; wt += step) {
+        const LayerTile t = layer_tile(plan, L, wt, l);
+        l = t.l;
+        const MxTable src{xi + l * N, ei + l * N};
+        const float* sc = SCALED ? c + l * N : nullptr;
+        float* o = out ? out + t.offset : nullptr;
+        uint16_t* ob = outb ? outb + t.offset : nullptr;
+        uint8_t* oq = nullptr;
+        uint8_t* oe = nullptr;
+        if constexpr (Q::kOn) {
+            oq = outq + (t.offset >> (Q::kFp4 ? 1 : 0));
+            oe = oute + (t.offset >> kMxLG);
+        }
+        auto column = [&](int64_t col) {
+            return fold_column_mx<F, SCORED, SCALED, HW>(src.template column<F>(col), col, N, a, s, sc, divisor);
+        };
+        if (!t.aligned) {  // one column per lane, as k_fedavg_mx_scalar / k_fedavg_mx_q_scalar
+            const int64_t col = t.bid * kMxWave + lane;
+            const bool valid = col < t.cols;
+            if constexpr (Q::kOn) {
+                float q = 0.0f;
+                if (valid) {
+                    q = column(col);
+                    if (o) o[col] = q;
+                }
+                mx_q_column<Q>(q, valid, col, oq, oe);
+            } else {
+                if (valid) st_column_bf16(column(col), o, ob, col);
+            }
+            continue;
+        }
+        const int64_t nb = t.cols >> kMxLG;  // full blocks
+        const int64_t b = t.bid * kMxWave + lane;
+        if (b < nb) {
+            fold_mx_block<F, SCORED, SCALED, FORM>(src.template block<F>(b), N, a, s, sc, divisor, o, ob, b, wave_lds, Q(),
+                                                   oq, oe);
+        } else if (b == nb && (t.cols & ((1 << kMxLG) - 1))) {  // the trailing columns, as octet_tile's tail
+            int64_t col = nb << kMxLG;
+            if constexpr (Q::kOn) {
+                const uint32_t E = Q::scale_byte(mx_q_tail_amax(col, t.cols, column, o));
+                oe[nb] = (uint8_t)E;
+                mx_q_tail_codes<Q>(col, t.cols, column, Q::prepare(E), oq);
+            } else {
+                for (; col < t.cols; ++col) st_column_bf16(column(col), o, ob, col);
+            }
+        }
+    }
+}
+
+template <class F, bool SCORED, bool SCALED, int FORM>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_mx_layers(
+    const uint8_t* const* __restrict__ xi, const uint8_t* const* __restrict__ ei,
+    const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N, const float* __restrict__ a,
+    const float* __restrict__ s, const float* __restrict__ c, float divisor, float* __restrict__ out,
+    uint16_t* __restrict__ outb, int64_t ntiles) {
+    mx_layers_walk<F, SCORED, SCALED, FORM, MxQNone>(xi, ei, plan, L, N, a, s, c, divisor, out, outb, nullptr, nullptr,
+                                                     ntiles);
+}
+
+// The same with MX output (Q): out is optional
+template <class F, bool SCORED, bool SCALED, int FORM, class Q>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_mx_q_layers(
+    const uint8_t* const* __restrict__ xi, const uint8_t* const* __restrict__ ei,
+    const fa_layer_plan* __restrict__ plan, int64_t L, int64_t N, const float* __restrict__ a,
+    const float* __restrict__ s, const float* __restrict__ c, float divisor, float* __restrict__ out,
+    uint8_t* __restrict__ outq, uint8_t* __restrict__ oute, int64_t ntiles) {
+    mx_layers_walk<F, SCORED, SCALED, FORM, Q>(xi, ei, plan, L, N, a, s, c, divisor, out, nullptr, outq, oute, ntiles);
+}
+
+// ---------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------
 inline dim3 grid_for(int64_t lanes) { return dim3((unsigned)((lanes + kBlock - 1) / kBlock)); }
@@ -6048,6 +6163,93 @@ inline int layers_fold(int kind, const char* what, const void* const* xi, const 
         });
     });
     return check_launch(what);
+}
+
+// ---- the MX layer tables (fa_fedavg_mx_layers, fa_fedavg_mx_q_layers) --------
+// The product's forms of the MX folds (kMxForm, kMxQForm) over the wave tiles
+// of fa_mx_layers_plan.  Grid: balanced passes over ceil(tiles / 4) blocks, at
+// most kMxBlocksPerCu per CU -- the MX fold's own rule on the model's tiles;
+// reasoned, not measured.  grid_cap > 0 (the bench library): at most that many
+// blocks.  The plan lies in device memory, so what it says of a layer (an odd
+// column count under a two-per-byte format) is the caller's to check.
+static_assert(kMxWaveCols == FA_MX_WAVE_TILE_COLS, "the header states the MX wave tile");
+inline dim3 mx_layers_grid(int64_t tiles, int64_t grid_cap) {
+    int64_t g = tile_grid((tiles + kMxWavesPerBlock - 1) / kMxWavesPerBlock, -kMxBlocksPerCu, cu_count());
+    if (grid_cap > 0 && g > grid_cap) g = grid_cap;
+    return dim3((unsigned)g);
+}
+template <class Fn>
+void with_mx_format(int fmt, Fn fn) {
+    if (fmt == FA_MX_E4M3) fn(MxE4M3());
+    else if (fmt == FA_MX_E5M2) fn(MxE5M2());
+    else fn(MxE2M1());
+}
+
+inline int mx_layers_fold(const char* what, int fmt, const uint8_t* const* xi, const uint8_t* const* ei,
+                          const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles, int64_t grid_cap,
+                          const float* a, const float* s, const float* c, float divisor, float* out_f32,
+                          uint16_t* out_bf16, void* stream) {
+    int rc = mx_format_check(fmt, 0);
+    if (rc) return rc;
+    bool empty;
+    rc = check_layers(what, L, N, tiles, 1, grid_cap, xi && ei && plan && a && (out_f32 || out_bf16),
+                      aligned16(out_f32) && aligned16(out_bf16), &empty);
+    if (rc || empty) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    StreamDevice on_stream_device(stream);
+    const dim3 g = mx_layers_grid(tiles, grid_cap);
+    with_mx_format(fmt, [&](auto f) {
+        with_scored(s != nullptr, [&](auto SC) {
+            with_scored(c != nullptr, [&](auto CS) {
+                hipLaunchKernelGGL((k_fedavg_mx_layers<decltype(f), decltype(SC)::value, decltype(CS)::value, kMxForm>),
+                                   g, dim3(kBlock), 0, st, xi, ei, plan, L, N, a, s, c, divisor, out_f32, out_bf16,
+                                   tiles);
+            });
+        });
+    });
+    return check_launch(what);
+}
+
+inline int mx_q_layers_fold(const char* what, int fmt, const uint8_t* const* xi, const uint8_t* const* ei,
+                            const fa_layer_plan* plan, int64_t L, int64_t N, int64_t tiles, int64_t grid_cap,
+                            const float* a, const float* s, const float* c, float divisor, float* out_f32,
+                            int out_fmt, uint8_t* out_q, uint8_t* out_e, void* stream) {
+    int rc = mx_format_check(fmt, 0);
+    if (rc) return rc;
+    if ((rc = mx_q_out_checks(what, out_fmt, 0, out_f32, out_q, out_e))) return rc;
+    bool empty;
+    rc = check_layers(what, L, N, tiles, 1, grid_cap, xi && ei && plan && a && out_q && out_e,
+                      aligned16(out_f32) && aligned16(out_q), &empty);
+    if (rc || empty) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    StreamDevice on_stream_device(stream);
+    const dim3 g = mx_layers_grid(tiles, grid_cap);
+    with_mx_format(fmt, [&](auto f) {
+        with_scored(s != nullptr, [&](auto SC) {
+            with_scored(c != nullptr, [&](auto CS) {
+                with_mx_q<kMxQForm>(out_fmt, [&](auto q) {
+                    hipLaunchKernelGGL((k_fedavg_mx_q_layers<decltype(f), decltype(SC)::value, decltype(CS)::value,
+                                                             kMxForm, decltype(q)>),
+                                       g, dim3(kBlock), 0, st, xi, ei, plan, L, N, a, s, c, divisor, out_f32, out_q,
+                                       out_e, tiles);
+                });
+            });
+        });
+    });
+    return check_launch(what);
+}
+
+inline int mx_layers_plan(const int64_t* cols, const int32_t* aligned, int64_t L, fa_layer_plan* plan, int64_t* tiles,
+                          int64_t* elems) {
+    if (L < 0) return fail(FA_ERR_ARG, "fa_mx_layers_plan: L=%lld", (long long)L);
+    if (!tiles || !elems || (L > 0 && (!cols || !aligned || !plan)))
+        return fail(FA_ERR_ARG, "fa_mx_layers_plan: null pointer");
+    for (int64_t l = 0; l < L; ++l)
+        if (cols[l] < 0) return fail(FA_ERR_ARG, "fa_mx_layers_plan: layer %lld has %lld columns", (long long)l,
+                                     (long long)cols[l]);
+    *tiles = fill_mx_layer_plan(cols, aligned, L, plan, elems);
+    g_err[0] = 0;
+    return FA_OK;
 }
 
 // ---- the integer row-table folds (fa_fedavg_i32/i64_ptrs, _layers) ----------

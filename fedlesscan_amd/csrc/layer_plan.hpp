@@ -56,3 +56,35 @@ inline int64_t fill_layer_plan(const int64_t* cols, const int32_t* aligned, int6
     *elems = off;
     return t;
 }
+
+// The MX layer tables (fa_fedavg_mx_layers, fa_fedavg_mx_q_layers) tile by the
+// wave, not the block: a lane owns one MX block of 32 columns, so a wave tile
+// of an aligned layer is 64 blocks = 2048 columns (the lane after the last full
+// block folding the cols % 32 trailing columns: ceil(cols / 32) lanes), and a
+// layer with a data row off 16-B alignment is tiled one column per lane, 64
+// columns per wave tile.  tile0 counts wave tiles; the offsets are the rule
+// above, so layer l's codes start at offset >> colLg bytes (a multiple of 32:
+// 16-B aligned under an aligned base) and its scale bytes, which need no
+// alignment, at offset >> 5.
+constexpr int64_t kMxPlanWave = 64, kMxPlanBlockCols = 32;
+
+inline int64_t mx_layer_tiles(int64_t cols, bool aligned) {
+    if (cols <= 0) return 0;
+    const int64_t lanes = aligned ? (cols + kMxPlanBlockCols - 1) / kMxPlanBlockCols : cols;
+    return (lanes + kMxPlanWave - 1) / kMxPlanWave;
+}
+
+inline int64_t fill_mx_layer_plan(const int64_t* cols, const int32_t* aligned, int64_t L, fa_layer_plan* plan,
+                                  int64_t* elems) {
+    int64_t t = 0, off = 0;
+    for (int64_t l = 0; l < L; ++l) {
+        plan[l].cols = cols[l];
+        plan[l].offset = off;
+        plan[l].tile0 = t;
+        plan[l].aligned = aligned[l] != 0;
+        t += mx_layer_tiles(cols[l], aligned[l] != 0);
+        off += (cols[l] + kLayerOutAlign - 1) / kLayerOutAlign * kLayerOutAlign;
+    }
+    *elems = off;
+    return t;
+}

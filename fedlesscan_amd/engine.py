@@ -1077,10 +1077,12 @@ _NO_CAPTURE_TABLE = (torch.float64, torch.int32, torch.int64)
 # through a widening row table (fa_fedavg_widen_ptrs, or each layer of a
 # fa_fedavg_widen_layers launch) and those launches (they move no other counter),
 # fp8 folds (fa_fedavg_fp8 and fa_fedavg_fp8_ptrs: one per layer of a model),
-# MX folds (fa_fedavg_mx and fa_fedavg_mx_ptrs, likewise)
+# MX folds (fa_fedavg_mx and fa_fedavg_mx_ptrs, likewise; an MX layer-table
+# launch, fa_fedavg_mx_layers / _mx_q_layers, counts each of its non-empty layers
+# there and itself in mx_table_folds)
 stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0, "layer_table_folds": 0, "rows_int_folds": 0,
          "widened_folds": 0, "widened_row_folds": 0, "widened_table_folds": 0, "fp8_folds": 0,
-         "mx_folds": 0, "mx_out_folds": 0}
+         "mx_folds": 0, "mx_out_folds": 0, "mx_table_folds": 0}
 
 
 class RowSet:
@@ -1681,6 +1683,22 @@ def layer_plan(cols: Sequence[int], aligned: Sequence[bool], unit_lg: int, cus: 
     return plan, tiles.value, elems.value, u.value
 
 
+def mx_layer_plan(cols: Sequence[int], aligned: Sequence[bool]):
+    """fa_mx_layers_plan, the host planner of the MX layer tables (no GPU):
+    (plan, tiles, elems) with plan an [L, 4] int64 array of (cols, offset,
+    tile0, aligned) rows.  cols are logical columns; tile0 counts WAVE tiles:
+    ceil(ceil(cols / 32) / 64) per aligned layer, ceil(cols / 64) per layer
+    with a data row off 16-B alignment."""
+    L = len(cols)
+    c = np.ascontiguousarray(cols, dtype=np.int64)
+    al = np.ascontiguousarray(aligned, dtype=np.int32)
+    plan = np.zeros((L, 4), dtype=np.int64)
+    tiles, elems = ctypes.c_int64(), ctypes.c_int64()
+    _lib.call("fa_mx_layers_plan", c.ctypes.data, al.ctypes.data, L, plan.ctypes.data, ctypes.addressof(tiles),
+              ctypes.addressof(elems))
+    return plan, tiles.value, elems.value
+
+
 def plan_at_units(host_plan: np.ndarray, elems: int, unit_lg: int, cus: int, units: int):
     """The layers of `host_plan` (a layer_plan result) planned again at `units`
     units per lane: (plan, tiles).  Only tile0 may differ: a layer's offset is
@@ -1702,7 +1720,19 @@ class ModelRowSet:
     row bases, plans the tiles of all layers with the host planner
     (fa_layers_plan) and uploads table and plan in ONE copy; fold_model_rows
     then costs the factor upload and one kernel.  The set keeps the tensors
-    alive; their CONTENTS may change between folds, their storage may not."""
+    alive; their CONTENTS may change between folds, their storage may not.
+
+    An MX model: every client gives every layer as MXLayer(q, e, scale=None),
+    all layers in ONE element format on one device; per layer every client
+    carries a scale or none does, and within the set all layers carry scales
+    or none does.  The set then holds the L*N data-row bases, the L*N scale-row
+    bases, the optional L*N float32 scales and the wave-tile plan
+    (fa_mx_layers_plan), uploaded in one copy, for fa_fedavg_mx_layers /
+    fa_fedavg_mx_q_layers; shapes and sizes are the layers' LOGICAL ones (a
+    float4 layer's last dimension doubled)."""
+
+    mx = False  # an MX set (a set of plain tensors has no scale rows, scales or wave-tile plan)
+    scale_rows = scales = dev_scales = scale_ptrs = None
 
     def __init__(self, parameters: Sequence[Sequence[torch.Tensor]], layers: Optional[Sequence[int]] = None):
         params = list(parameters)
@@ -1712,6 +1742,9 @@ class ModelRowSet:
         lis = list(range(min(map(len, params)))) if layers is None else list(layers)
         # one C-level pass per property and layer (as RowSet: no reshape per tensor)
         cols_of = [list(map(operator.itemgetter(li), params)) for li in lis]
+        if any(isinstance(x, MXLayer) for col in cols_of for x in col):
+            self._init_mx(cols_of, lis, N)
+            return
         t0 = cols_of[0][0] if cols_of else None
         if t0 is not None and not (isinstance(t0, torch.Tensor) and t0.is_cuda):
             raise ValueError("layers must be CUDA (HIP) tensors")
@@ -1747,6 +1780,80 @@ class ModelRowSet:
             self.ptrs, self.plan = both[:self.L * N], both[self.L * N:]
         self.offsets = [int(o) for o in self.host_plan[:, 1]] if self.host_plan is not None else []
 
+    def _init_mx(self, cols_of: list, lis: list, N: int) -> None:
+        """The tables of an MX model: validated as RowSet._mx_table validates one layer."""
+        L = len(lis)
+        m0 = cols_of[0][0]
+        if not (isinstance(m0, MXLayer) and isinstance(m0.q, torch.Tensor) and m0.q.is_cuda):
+            raise InvalidParameterShapeError("every client gives every layer of an MX model as an MXLayer of CUDA (HIP) "
+                                             "tensors")
+        dt, dev = m0.q.dtype, m0.q.device
+        if dt not in _MX_FORMATS:
+            raise InvalidParameterShapeError(f"MX layers hold fp8 / float4_e2m1fn_x2 elements, got {dt}")
+        self.mx = True
+        self.N, self.L, self.layers, self.device, self.dtype = N, L, lis, dev, dt
+        self.shapes, self.sizes, self.tensors, self.scale_rows = [], [], [], []
+        self.esize, self.entry, self._rowsets, self._plans = 1, None, {}, {}
+        ptrs = np.zeros((2, L, N), dtype=np.int64)
+        scaled = []
+        for k, col in enumerate(cols_of):
+            if not all(isinstance(x, MXLayer) for x in col):
+                raise InvalidParameterShapeError(f"layer {lis[k]}: every client gives an MXLayer or none does")
+            qs, es = [x.q for x in col], [x.e for x in col]
+            if not all(isinstance(q, torch.Tensor) for q in qs) or set(map(_dtype_of, qs)) != {dt}:
+                raise InvalidParameterShapeError(f"layer {lis[k]}: the MX layers of one set fold in one format ({dt}), "
+                                                 f"got {sorted({str(getattr(q, 'dtype', type(q))) for q in qs})}")
+            shp = qs[0].shape
+            if (set(map(_shape_of, qs)) != {shp} or not all(map(torch.Tensor.is_contiguous, qs))
+                    or set(map(torch.Tensor.get_device, qs)) != {m0.q.get_device()}):
+                raise InvalidParameterShapeError(
+                    f"layer {lis[k]}: all clients' tensors must be contiguous with one shape, dtype and device")
+            cols = _mx_cols(dt, qs[0].numel())
+            nb = (cols + 31) // 32
+            for i, e in enumerate(es):
+                if not (isinstance(e, torch.Tensor) and e.dtype in _MX_SCALE_DTYPES):
+                    raise InvalidParameterShapeError(f"layer {lis[k]}, client {i}: the scale row must hold E8M0 bytes "
+                                                     f"(float8_e8m0fnu or uint8), got {getattr(e, 'dtype', type(e))}")
+                if e.numel() != nb or not e.is_contiguous() or e.device != dev:
+                    raise InvalidParameterShapeError(f"layer {lis[k]}, client {i}: {e.numel()} scale bytes for {cols} "
+                                                     f"columns (one per 32: {nb}, contiguous, on {dev})")
+            given = [x.scale is not None for x in col]
+            if any(given) and not all(given):
+                raise InvalidParameterShapeError(f"layer {lis[k]}: every client's MXLayer carries a scale or none does")
+            scaled.append(all(given))
+            # the logical shape: a float4 layer's last dimension doubled (a 0-dim one: its two columns)
+            self.shapes.append(tuple(shp[:-1]) + (_mx_cols(dt, shp[-1]),) if len(shp) else () if cols == 1 else (cols,))
+            self.sizes.append(cols)
+            self.tensors.append(qs)
+            self.scale_rows.append(es)
+            ptrs[0, k] = np.fromiter(map(torch.Tensor.data_ptr, qs), dtype=np.int64, count=N)
+            ptrs[1, k] = np.fromiter(map(torch.Tensor.data_ptr, es), dtype=np.int64, count=N)
+        if any(scaled) and not all(scaled):
+            raise InvalidParameterShapeError("within one MX set all layers carry client scales or none does "
+                                             f"(layers with: {[li for li, c in zip(lis, scaled) if c]})")
+        self.host_ptrs = ptrs
+        self.ptrs = self.plan = self.host_plan = None
+        self.tiles = self.elems = self.units = 0
+        self.offsets = []
+        if not L:
+            return
+        if scaled[0]:
+            self.scales = np.array([[np.float32(x.scale) for x in col] for col in cols_of], dtype=np.float32)
+        sizes = np.asarray(self.sizes, dtype=np.int64)
+        aligned = ~((ptrs[0] % 16) != 0).any(axis=1) | (sizes == 0)
+        self.host_plan, self.tiles, self.elems = mx_layer_plan(sizes, aligned)
+        self.units = 1
+        self.offsets = [int(o) for o in self.host_plan[:, 1]]
+        parts = [ptrs.reshape(-1).view(np.uint8), self.host_plan.reshape(-1).view(np.uint8)]
+        if self.scales is not None:
+            parts.append(self.scales.reshape(-1).view(np.uint8))
+        both = torch.from_numpy(np.concatenate(parts)).to(dev)  # ONE copy: bases, plan, scales
+        n = 8 * L * N
+        self.ptrs, self.scale_ptrs = both[:n].view(torch.int64), both[n:2 * n].view(torch.int64)
+        self.plan = both[2 * n:2 * n + 32 * L].view(torch.int64)
+        if self.scales is not None:
+            self.dev_scales = both[2 * n + 32 * L:].view(torch.float32)
+
     def plan_for(self, units: int):
         """(device plan, tiles) of the set's layers at `units` units per lane:
         the set's own where its rule chose that many, else planned on first
@@ -1760,12 +1867,15 @@ class ModelRowSet:
         return hit
 
     def overlaps(self, t: torch.Tensor) -> bool:
-        """Does tensor t share a byte with any client tensor of the set?"""
+        """Does tensor t share a byte with any client tensor (an MX set: or scale row) of the set?"""
         if self.L == 0 or t.numel() == 0:
             return False
         lo = t.data_ptr()
         hi = lo + t.numel() * t.element_size()
         nbytes = (np.asarray(self.sizes, dtype=np.int64) * self.esize)[:, None]
+        if self.mx:  # [2, L, N] bases: the data rows' bytes, then the scale rows'
+            cols = np.asarray(self.sizes, dtype=np.int64)[:, None]
+            nbytes = np.stack([cols // 2 if self.dtype == torch.float4_e2m1fn_x2 else cols, (cols + 31) // 32])
         return bool(np.any((self.host_ptrs < hi) & (lo < self.host_ptrs + nbytes)))
 
     def rowset(self, k: int) -> RowSet:
@@ -1775,7 +1885,9 @@ class ModelRowSet:
         rs = self._rowsets.get(k)
         if rs is None:
             rows = [t.reshape(-1) for t in self.tensors[k]]
-            if self.ptrs is None or self.sizes[k] == 0:
+            if self.mx:  # a table of its own: the 2N bases of one layer are not adjacent in the set's
+                rs = RowSet(rows, block_scales=[e.reshape(-1) for e in self.scale_rows[k]])
+            elif self.ptrs is None or self.sizes[k] == 0:
                 rs = RowSet(rows)
             else:
                 rs = RowSet.__new__(RowSet)
@@ -1813,9 +1925,116 @@ def _layer_factors(dt: torch.dtype, weights, scores, total) -> Optional[Factors]
     return f64_factors(weights, scores, total)
 
 
+def _fold_model_mx(ms: "ModelRowSet", weights, scores, out, total, want_bf16, out_bf16, out_format, out_mx, scales):
+    """An MX model through the MX layer table (fa_fedavg_mx_layers, with
+    out_format / out_mx fa_fedavg_mx_q_layers): one launch for all L layers,
+    the factors (and scales= of this call) in ONE staged upload.  Everything is
+    decided here on the host before the launch."""
+    if torch.cuda.is_current_stream_capturing():
+        raise InvalidParameterShapeError("the MX layer table does not run under stream capture "
+                                         "(its factors and scales are staged by a copy the graph would not own)")
+    N, L, dev, E = ms.N, ms.L, ms.device, ms.elems
+    if L == 0:
+        return []
+    quant = out_format is not None or out_mx is not None
+    bf16 = want_bf16 or out_bf16 is not None
+    lg = 0
+    if quant:
+        if out_format is None:
+            out_format = out_mx[0].dtype
+        if out_format not in _MX_FORMATS:
+            raise InvalidParameterShapeError("out_format must be float8_e4m3fn, float8_e5m2 or float4_e2m1fn_x2, got "
+                                             f"{out_format}")
+        if bf16:
+            raise InvalidParameterShapeError("out_format gives an MX result: want_bf16 / out_bf16 do not go with it")
+        if out_format == torch.float4_e2m1fn_x2:
+            lg = 1
+            for k, (n, shp) in enumerate(zip(ms.sizes, ms.shapes)):
+                if n % 2 or (shp and shp[-1] % 2):
+                    raise InvalidParameterShapeError(f"layer {ms.layers[k]}: a float4_e2m1fn_x2 result holds two columns "
+                                                     f"per byte, pairs of the last dimension: shape {shp}")
+    c = ms.dev_scales
+    host_c = None
+    if scales is not None:
+        if len(scales) != L or any(len(cs) != N for cs in scales):
+            raise InvalidParameterShapeError(f"scales= takes {L} sequences of {N} numbers, one per layer")
+        host_c = np.array([[np.float32(x) for x in cs] for cs in scales], dtype=np.float32).reshape(-1)
+    _check_out("out", out, torch.float32, E)
+    _check_out("out_bf16", out_bf16, torch.bfloat16, E)
+    nq, ne = E >> lg, E >> 5
+    if out_mx is not None:
+        q, e = out_mx
+        if not (isinstance(q, torch.Tensor) and q.dtype == out_format and q.device == dev and q.is_contiguous()
+                and q.numel() >= nq):
+            raise InvalidParameterShapeError(f"out_mx[0] must be a contiguous {out_format} tensor of >= {nq} elements "
+                                             f"on {dev}")
+        if not (isinstance(e, torch.Tensor) and e.dtype in _MX_SCALE_DTYPES and e.device == dev and e.is_contiguous()
+                and e.numel() >= ne):
+            raise InvalidParameterShapeError(f"out_mx[1] must hold >= {ne} contiguous E8M0 bytes (float8_e8m0fnu or "
+                                             f"uint8) on {dev}")
+
+    def usable(t):  # the tables live in device memory: the library cannot see an alias
+        return t is not None and t.data_ptr() % 16 == 0 and not ms.overlaps(t)
+
+    dst, dstb = out, out_bf16
+    out = out if usable(out) else None
+    outb = out_bf16 if usable(out_bf16) else None
+    if outb is None and bf16:
+        outb = torch.empty(E, dtype=torch.bfloat16, device=dev)
+    if out is None and (dst is not None or (outb is None and not quant) or want_bf16):
+        out = torch.empty(E, dtype=torch.float32, device=dev)
+    qf = ef = None
+    if quant:
+        if out_mx is not None and usable(out_mx[0]) and not ms.overlaps(out_mx[1]):
+            qf, ef = out_mx[0].reshape(-1), out_mx[1].reshape(-1)
+        else:
+            qf = torch.empty(nq, dtype=torch.uint8, device=dev).view(out_format)
+            ef = torch.empty(ne, dtype=torch.uint8, device=dev).view(torch.float8_e8m0fnu)
+    f = Factors.weak_f32(weights, scores, total) or Factors(weights, scores, _F32, total=total)
+    parts = [f.a] if f.s is None else [f.a, f.s]
+    if host_c is not None:
+        parts.append(host_c)
+    staged = stage_factors(parts, dev)
+    a, s = staged[0], (staged[1] if f.s is not None else None)
+    if host_c is not None:
+        c = staged[-1]
+    args = [_MX_FORMATS[ms.dtype], ms.ptrs.data_ptr(), ms.scale_ptrs.data_ptr(), ms.plan.data_ptr(), L, N, ms.tiles,
+            a.data_ptr(), _ptr(s), _ptr(c), float(f.div), _ptr(out)]
+    if quant:
+        _lib.call("fa_fedavg_mx_q_layers", *args, _MX_FORMATS[out_format], qf.data_ptr(), ef.data_ptr(), stream_ptr(dev))
+    else:
+        _lib.call("fa_fedavg_mx_layers", *args, _ptr(outb), stream_ptr(dev))
+    folded = sum(1 for n in ms.sizes if n)  # the layers fold_rows would count
+    stats["mx_table_folds"] += 1
+    stats["mx_folds"] += folded
+    if dst is not None and dst is not out:
+        dst.reshape(-1)[:E].copy_(out)
+        out = dst
+    if dstb is not None and dstb is not outb:
+        dstb.reshape(-1)[:E].copy_(outb)
+        outb = dstb
+    if quant:
+        stats["mx_out_folds"] += folded
+        if out_mx is not None and qf.data_ptr() != out_mx[0].data_ptr():
+            out_mx[0].view(torch.uint8).reshape(-1)[:nq].copy_(qf.view(torch.uint8))
+            out_mx[1].view(torch.uint8).reshape(-1)[:ne].copy_(ef.view(torch.uint8))
+            qf, ef = out_mx[0].reshape(-1), out_mx[1].reshape(-1)
+        res = []
+        for o, n, shp in zip(ms.offsets, ms.sizes, ms.shapes):
+            qshape = shp[:-1] + (shp[-1] >> lg,) if shp else ()
+            res.append(MXLayer(qf[o >> lg:(o + n) >> lg].reshape(qshape), ef[o >> 5:(o >> 5) + (n + 31) // 32]))
+        return res
+    if want_bf16:
+        return ms.split(out.reshape(-1)), ms.split(outb.reshape(-1))
+    if out_bf16 is not None:
+        return ms.split(outb.reshape(-1)) if out is None else (ms.split(out.reshape(-1)), ms.split(outb.reshape(-1)))
+    return ms.split(out.reshape(-1))
+
+
 def fold_model_rows(model, weights: Sequence, scores: Optional[Sequence] = None, *,
                     out: Optional[torch.Tensor] = None, total=None, want_bf16: bool = False,
-                    out_bf16: Optional[torch.Tensor] = None):
+                    out_bf16: Optional[torch.Tensor] = None, out_format: Optional[torch.dtype] = None,
+                    out_mx=None, scales: Optional[Sequence[Sequence]] = None):
     """fold_rows over every layer of a device-resident model in ONE launch.
 
     model: a ModelRowSet (prepared once, reusable) or N lists of device
@@ -1834,12 +2053,31 @@ def fold_model_rows(model, weights: Sequence, scores: Optional[Sequence] = None,
     would leave the row table (a fold numpy types term by term, a dtype
     without a table, FEDAVG_WIDEN=0 under promoting factors, a stream capture
     in progress) every layer goes through fold_rows on its own, over the set's
-    own table and into fresh tensors (out / out_bf16 are refused there)."""
+    own table and into fresh tensors (out / out_bf16 are refused there).
+
+    An MX model (a ModelRowSet of MXLayers, or N lists of them) folds through
+    the MX layer table, one launch (fa_fedavg_mx_layers): L float32 tensors in
+    the layers' logical shapes; out= / want_bf16 / out_bf16 as for bf16 layers.
+    scales=: L sequences of N numbers, each rounded as np.float32(scale),
+    replace the set's own client scales for this call.  out_format (or out_mx =
+    (q_flat, e_flat), flat buffers of model.elems elements' codes and
+    model.elems / 32 scale bytes) quantises the result in the same launch
+    (fa_fedavg_mx_q_layers) and returns L MXLayer(q, e): q in the layer's
+    logical shape, the last dimension halved for a float4 result, e its
+    ceil(size / 32) scale bytes, both views of the flat buffers (layer k's
+    codes at offsets[k] elements, its scale bytes at offsets[k] / 32) and each
+    a valid row of a further MX fold.  Refused before any launch
+    (InvalidParameterShapeError): out_format with bf16 outputs, a float4 result
+    of a layer of odd size, a stream capture in progress."""
     ms = model if isinstance(model, ModelRowSet) else ModelRowSet(model)
     N = ms.N
     if len(weights) != N or (scores is not None and len(scores) != N):
         raise InvalidParameterShapeError(f"{N} clients but {len(weights)} weights"
                                          + ("" if scores is None else f" / {len(scores)} scores"))
+    if ms.mx:
+        return _fold_model_mx(ms, weights, scores, out, total, want_bf16, out_bf16, out_format, out_mx, scales)
+    if out_format is not None or out_mx is not None or scales is not None:
+        raise InvalidParameterShapeError("out_format / out_mx / scales are for MX models (layers given as MXLayer)")
     bf16 = ms.dtype == torch.bfloat16
     if (out_bf16 is not None or want_bf16) and not bf16:
         raise InvalidParameterShapeError("want_bf16 / out_bf16 are for bfloat16 layers")
@@ -2016,6 +2254,20 @@ def _unwrap_mx(parameters, n_eff):
     return plain, mx
 
 
+def _mx_group_here(parameters, layer_mx, n_eff, lis, dev) -> bool:
+    """Do the MX layers `lis` take the MX layer table?  Every client's element
+    tensor and scale row contiguous and on the device the fold was asked for
+    (the per-layer route folds a layer wherever it lies)."""
+    d = torch.device(dev)
+    want = (d.type, d.index if d.index is not None else torch.cuda.current_device())
+    for li in lis:
+        for t in [parameters[i][li] for i in range(n_eff)] + list(layer_mx[li][0]):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()
+                    and (t.device.type, t.device.index) == want):
+                return False
+    return True
+
+
 def _multi(devices) -> Optional[list]:
     """The device list of a multi-GPU call, or None for a one-GPU call."""
     if devices is None:
@@ -2048,7 +2300,11 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
     q_i.to(float32) * np.float32(scale_i) (fold_stacked's scales=).  Device MX
     layers are given as MXLayer(q, e, scale=None) by every client and fold the
     same way (fa_fedavg_mx_ptrs); a float4 layer's result has its last
-    dimension doubled.
+    dimension doubled.  Two or more MX layers of one format on the fold's
+    device, contiguous, fold in ONE launch per sub-group (the layers with
+    client scales, the layers without) through the MX layer table
+    (fold_model_rows, fa_fedavg_mx_layers) unless FEDAVG_LAYER_TABLE=0 or a
+    stream capture is in progress; the same bits either way.
 
     out_format (float8_e4m3fn, float8_e5m2, float4_e2m1fn_x2): every layer
     must be a device fp8 or MX layer, and each comes back as MXLayer(q, e)
@@ -2100,7 +2356,23 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
         sizes = [int(np.prod(shapes[li])) if len(shapes[li]) else 1 for li in lis]
         P = sum(sizes)
         if dtypes[lis[0]] in _MX_FORMATS:
-            # device fp8 layers: each folds from the clients' own bytes through its row table
+            # device fp8 layers: each folds from the clients' own bytes through its row table.  Two or more
+            # MX layers on the fold's device: one table and one launch per sub-group (the layers with client
+            # scales, the layers without; FEDAVG_LAYER_TABLE=0: a fold per layer); the same bits either way
+            tabled = [li for li in lis if li in layer_mx]
+            if (len(tabled) >= 2 and layer_table_enabled() and not torch.cuda.is_current_stream_capturing()
+                    and _mx_group_here(parameters, layer_mx, n_eff, tabled, dev)):
+                for sub in ([li for li in tabled if layer_mx[li][1] is None],
+                            [li for li in tabled if layer_mx[li][1] is not None]):
+                    if not sub:
+                        continue
+                    model = [[MXLayer(parameters[i][li], layer_mx[li][0][i],
+                                      None if layer_mx[li][1] is None else layer_mx[li][1][i]) for li in sub]
+                             for i in range(n_eff)]
+                    for li, r in zip(sub, fold_model_rows(ModelRowSet(model), w, sc, total=sum(total_weights),
+                                                          out_format=out_format)):
+                        outs[li] = r
+                lis = [li for li in lis if li not in layer_mx]
             for li in lis:
                 rows = [parameters[i][li].reshape(-1) for i in range(n_eff)]
                 if li in layer_mx:

@@ -756,8 +756,9 @@ int fa_fedavg_fp8_ptrs(int fmt, const uint8_t* const* xi, int64_t N, int64_t P,
  * folds the previous group, and a full wave exchanges its float32 results
  * through LDS so that each store instruction writes 1 KiB contiguous; the
  * P % 32 trailing columns fold in one lane.  Neither allocates nor
- * synchronises.  Not covered: host rows, the layer tables, the sharded step,
- * stream capture, a tuner kind, MXFP6, NVFP4.  MX output: fa_fedavg_mx_q below. */
+ * synchronises.  Not covered: host rows, the sharded step, stream capture, a
+ * tuner kind, MXFP6, NVFP4.  MX output: fa_fedavg_mx_q below; every layer of a
+ * model in one launch: fa_fedavg_mx_layers further below. */
 #define FA_MX_E4M3 0
 #define FA_MX_E5M2 1
 #define FA_MX_E2M1 2
@@ -804,8 +805,8 @@ int fa_fedavg_mx_ptrs(int fmt, const uint8_t* const* xi, const uint8_t* const* e
  * one-column kernels reduce the amax over the 32 lanes of a half-wave.
  * Neither entry allocates nor synchronises.  Not covered: MX output of the
  * float32 / bf16 / float16 / float64 folds, fp8 output with a per-tensor scale,
- * the layer tables, the sharded step, stream capture, MXFP6, NVFP4, stochastic
- * rounding. */
+ * the layer tables of the fp8 sources, the sharded step, stream capture, MXFP6,
+ * NVFP4, stochastic rounding. */
 int fa_fedavg_mx_q(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P,
                    int64_t ldx, int64_t lde, const float* a, const float* s, const float* c, float divisor,
                    float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e, void* stream);
@@ -818,6 +819,58 @@ int fa_fedavg_fp8_q(int fmt, const uint8_t* X, int64_t N, int64_t P, int64_t ldx
 int fa_fedavg_fp8_q_ptrs(int fmt, const uint8_t* const* xi, int64_t N, int64_t P,
                          const float* a, const float* s, const float* c, float divisor, int rows_aligned,
                          float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e, void* stream);
+
+/* ---- every MX layer of a device-resident model in one launch (new symbols, ABI still 7)
+ * fa_fedavg_mx_ptrs / fa_fedavg_mx_q_ptrs over the L layers of a model whose N
+ * clients keep every layer as an MX row of one element format fmt:
+ *   xi    [device] L*N data-row bases, layer-major: xi[l*N + i] = client i's layer l
+ *   ei    [device] L*N scale-row bases, the same order, any alignment
+ *   plan  [device] L entries, as fa_mx_layers_plan wrote them; tiles its total
+ *   a, s  [device] the N factors every layer shares (s NULL for FedAvg)
+ *   c     NULL, or [device] L*N float32, c[l*N + i] = client i's scale of layer l
+ * The plan's tile is a WAVE tile: a lane owns one MX block, and nothing but the
+ * grid-stride loop is shared between the waves of a block, so a wave takes
+ * FA_MX_WAVE_TILE_COLS = 64 blocks of one layer and the four waves of a block
+ * four consecutive wave tiles, which may lie in four layers (a 64-element bias
+ * leaves 62 lanes of ONE wave idle, not 254 of a block).  A layer with a data
+ * row off 16-B alignment (plan[l].aligned == 0) is tiled one column per lane,
+ * 64 columns per wave tile.  Each wave finds its layer by a scalar binary
+ * search of plan[].tile0.  Grid: balanced passes over ceil(tiles / 4) blocks,
+ * at most two per CU.
+ * The outputs are flat, layer l at plan[l].offset (a multiple of 64 elements):
+ *   out_f32, out_bf16   plan[l].offset elements
+ *   out_q               offset bytes (fp8 codes), offset / 2 (e2m1 codes)
+ *   out_e               offset / 32 bytes
+ * so out_f32 / out_bf16 hold `elems` elements, out_q elems (e2m1: elems / 2)
+ * bytes and out_e elems / 32 bytes; what lies between a layer's end and the
+ * next offset is not written.  fa_fedavg_mx_layers: out_f32 and out_bf16 each
+ * optional, one of them given.  fa_fedavg_mx_q_layers: out_q and out_e
+ * required, out_f32 optional.  Layer l of every output holds, bit for bit, what
+ * fa_fedavg_mx_ptrs / fa_fedavg_mx_q_ptrs give for that layer alone.
+ * Checks, before any launch: an unknown fmt / out_fmt, negative L, N or tiles,
+ * a NULL table, plan, a or required output, an output off 16-B alignment
+ * (out_e: any) -> FA_ERR_ARG; N == 0 -> FA_ERR_NO_CLIENTS; L == 0 or tiles == 0
+ * launches nothing.  The plan lies in device memory: that an e2m1 source or
+ * result has no layer of odd size, and that no output overlaps a row, is the
+ * caller's to see to.  Neither allocates nor synchronises.
+ *   fa_mx_layers_plan: the host planner (no GPU).  cols[l]: layer l's LOGICAL
+ *     columns (e2m1: twice the row bytes); aligned[l] != 0: all its data rows
+ *     are 16-B aligned.  plan[l].tile0 = the wave tiles before layer l, where a
+ *     layer has ceil(ceil(cols / 32) / 64) wave tiles if aligned, ceil(cols / 64)
+ *     if not, none for 0 columns; plan[l].offset as fa_layers_plan.  *tiles,
+ *     *elems: the totals.  A negative L or column count, a NULL pointer ->
+ *     FA_ERR_ARG.
+ * Not covered: layer tables of plain fp8 rows, the sharded step, several GPUs,
+ * stream capture, a tuner kind. */
+#define FA_MX_WAVE_TILE_COLS 2048
+int fa_mx_layers_plan(const int64_t* cols, const int32_t* aligned, int64_t L, fa_layer_plan* plan, int64_t* tiles,
+                      int64_t* elems);
+int fa_fedavg_mx_layers(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, const fa_layer_plan* plan,
+                        int64_t L, int64_t N, int64_t tiles, const float* a, const float* s, const float* c,
+                        float divisor, float* out_f32, uint16_t* out_bf16, void* stream);
+int fa_fedavg_mx_q_layers(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, const fa_layer_plan* plan,
+                          int64_t L, int64_t N, int64_t tiles, const float* a, const float* s, const float* c,
+                          float divisor, float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e, void* stream);
 
 /* ---- host staging: page-locked documents and direct DMA ---------------------
  * A result store that keeps documents in page-locked memory lets the ingest

@@ -168,6 +168,18 @@ int fa_fedavg_int_layers_form(int dtype, const void* const* xi, const fa_layer_p
 int fa_fedavg_widen_layers_form(int kind, const void* const* xi, const fa_layer_plan* plan, int64_t L, int64_t N,
                                 int64_t tiles, int units, int64_t grid_cap, const void* a, const void* s,
                                 double divisor, void* out, void* stream);
+/* The MX layer tables (fa_fedavg_mx_layers / fa_fedavg_mx_q_layers) with a
+ * trailing cap on the grid: grid_cap > 0 launches at most that many blocks, so
+ * every wave walks several wave tiles across layer boundaries and restarts its
+ * layer search; 0: the product's grid.  Everything else as the product
+ * entries; a negative grid_cap -> FA_ERR_ARG. */
+int fa_fedavg_mx_layers_form(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, const fa_layer_plan* plan,
+                             int64_t L, int64_t N, int64_t tiles, const float* a, const float* s, const float* c,
+                             float divisor, float* out_f32, uint16_t* out_bf16, void* stream, int64_t grid_cap);
+int fa_fedavg_mx_q_layers_form(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, const fa_layer_plan* plan,
+                               int64_t L, int64_t N, int64_t tiles, const float* a, const float* s, const float* c,
+                               float divisor, float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e,
+                               void* stream, int64_t grid_cap);
 /* Same for the bf16 fold (variant 0 = fa_fedavg_bf16). */
 int fa_fedavg_bf16_variant(const uint16_t* X, int64_t N, int64_t P, int64_t ldx,
                            const float* a, const float* s, float divisor,
