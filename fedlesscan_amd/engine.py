@@ -2304,7 +2304,8 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
     device, contiguous, fold in ONE launch per sub-group (the layers with
     client scales, the layers without) through the MX layer table
     (fold_model_rows, fa_fedavg_mx_layers) unless FEDAVG_LAYER_TABLE=0 or a
-    stream capture is in progress; the same bits either way.
+    stream capture is in progress; a sub-group of one layer folds as a lone
+    layer does; the same bits either way.
 
     out_format (float8_e4m3fn, float8_e5m2, float4_e2m1fn_x2): every layer
     must be a device fp8 or MX layer, and each comes back as MXLayer(q, e)
@@ -2362,17 +2363,19 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
             tabled = [li for li in lis if li in layer_mx]
             if (len(tabled) >= 2 and layer_table_enabled() and not torch.cuda.is_current_stream_capturing()
                     and _mx_group_here(parameters, layer_mx, n_eff, tabled, dev)):
+                folded = set()
                 for sub in ([li for li in tabled if layer_mx[li][1] is None],
                             [li for li in tabled if layer_mx[li][1] is not None]):
-                    if not sub:
+                    if len(sub) < 2:  # a lone layer of its sub-group: the fold of one layer below
                         continue
+                    folded.update(sub)
                     model = [[MXLayer(parameters[i][li], layer_mx[li][0][i],
                                       None if layer_mx[li][1] is None else layer_mx[li][1][i]) for li in sub]
                              for i in range(n_eff)]
                     for li, r in zip(sub, fold_model_rows(ModelRowSet(model), w, sc, total=sum(total_weights),
                                                           out_format=out_format)):
                         outs[li] = r
-                lis = [li for li in lis if li not in layer_mx]
+                lis = [li for li in lis if li not in folded]
             for li in lis:
                 rows = [parameters[i][li].reshape(-1) for i in range(n_eff)]
                 if li in layer_mx:

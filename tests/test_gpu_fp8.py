@@ -45,14 +45,14 @@ def _factors(N, scored, scaled):
     return w, sc, scales
 
 
-def _oracle(fmt, b, w, sc, scales):
+def _oracle(fmt, b, w, sc, scales, total=None):
     """(float32 result, its RNE bf16 bits) of the float32 oracle over the rows upcast on the CPU."""
     X = torch.from_numpy(np.array(b)).view(FMTS[fmt]).to(torch.float32).numpy()
     with np.errstate(all="ignore"):
         if scales is not None:
             X = X * np.array([np.float32(c) for c in scales], dtype=np.float32)[:, None]
         assert X.dtype == np.float32
-        e = O.fedavg_stacked(X, w, sc)
+        e = O.fedavg_stacked(X, w, sc, total=total)
     assert e.dtype == np.float32
     return e, synth.f32_to_bf16_bits(e)
 

@@ -31,9 +31,9 @@ def dev():
     return torch.device("cuda", 0)
 
 
-def _oracle(fmt, q, E, w, sc, scales):
+def _oracle(fmt, q, E, w, sc, scales, total=None):
     """(float32 result, its RNE bf16 bits) of the float32 oracle over the rows dequantised on the CPU.
-    q: [N, row bytes] element bytes, E: [N, ceil(P / 32)] scale bytes."""
+    q: [N, row bytes] element bytes, E: [N, ceil(P / 32)] scale bytes; total: the divisor where it is not sum(w)."""
     if fmt == "e2m1":
         X = np.stack([E2M1[q & 15], E2M1[q >> 4]], axis=-1).reshape(q.shape[0], -1)
     else:
@@ -44,7 +44,7 @@ def _oracle(fmt, q, E, w, sc, scales):
         if scales is not None:
             X = X * np.array([np.float32(c) for c in scales], dtype=np.float32)[:, None]
         assert X.dtype == np.float32
-        e = O.fedavg_stacked(X, w, sc)
+        e = O.fedavg_stacked(X, w, sc, total=total)
     assert e.dtype == np.float32
     return e, synth.f32_to_bf16_bits(e)
 
