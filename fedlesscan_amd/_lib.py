@@ -40,6 +40,7 @@ FA_FP8_TILE_COLS, FA_FP8_ROWS_AHEAD = 8192, 8
 FA_MX_E4M3, FA_MX_E5M2, FA_MX_E2M1 = range(3)
 FA_MX_TILE_COLS, FA_MX_ROWS_AHEAD_FP8, FA_MX_ROWS_AHEAD_FP4 = 8192, 8, 16
 FA_MX_WAVE_TILE_COLS = 2048  # the wave tile of the MX layer tables (fa_fedavg_mx_layers)
+FA_NVFP4_BLOCK, FA_NVFP4_ROWS_AHEAD = 16, 16  # fa_fedavg_nvfp4: elements per e4m3 scale byte, rows of loads ahead
 
 _i64 = ctypes.c_int64
 _vp = ctypes.c_void_p
@@ -112,6 +113,8 @@ _PROTOS = {
     "fa_fedavg_fp8_ptrs": (_int, [_int, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _vp, _vp]),
     "fa_fedavg_mx": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
     "fa_fedavg_mx_ptrs": (_int, [_int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _vp, _vp]),
+    "fa_fedavg_nvfp4": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "fa_fedavg_nvfp4_ptrs": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _vp, _vp]),
     "fa_fedavg_mx_q": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _int, _vp, _vp, _vp]),
     "fa_fedavg_mx_q_ptrs": (_int, [_int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f32, _int, _vp, _int, _vp, _vp, _vp]),
     "fa_fedavg_fp8_q": (_int, [_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _int, _vp, _vp, _vp]),
@@ -190,6 +193,7 @@ _BENCH_PROTOS = {
     "fa_fedavg_f16_ptrs_form": (_int, [_vp, _i64, _i64, _vp, _vp, ctypes.c_uint16, _int, _vp, _vp, _int]),
     "fa_fedavg_fp8_form": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _int, _int]),
     "fa_fedavg_mx_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _int, _int]),
+    "fa_fedavg_nvfp4_form": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _int, _int]),
     "fa_fedavg_mx_q_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _f32, _vp, _int, _vp, _vp, _vp, _int]),
     "fa_fedavg_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp, _vp]),
     "fa_fedavg_int_layers_form": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _f64, _vp, _vp]),

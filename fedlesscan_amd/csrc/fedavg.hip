@@ -295,6 +295,17 @@ int fa_fedavg_mx_ptrs(int fmt, const uint8_t* const* xi, const uint8_t* const* e
     return mx_rows_fold(fmt, xi, ei, N, P, a, s, c, divisor, rows_aligned, out_f32, out_bf16, stream);
 }
 
+int fa_fedavg_nvfp4(const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde, const float* a,
+                    const float* s, const float* c, float divisor, float* out_f32, uint16_t* out_bf16, void* stream) {
+    return nvfp4_fold(X, E, N, P, ldx, lde, a, s, c, divisor, out_f32, out_bf16, stream);
+}
+
+int fa_fedavg_nvfp4_ptrs(const uint8_t* const* xi, const uint8_t* const* ei, int64_t N, int64_t P, const float* a,
+                         const float* s, const float* c, float divisor, int rows_aligned, float* out_f32,
+                         uint16_t* out_bf16, void* stream) {
+    return nvfp4_rows_fold(xi, ei, N, P, a, s, c, divisor, rows_aligned, out_f32, out_bf16, stream);
+}
+
 int fa_fedavg_mx_q(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
                    const float* a, const float* s, const float* c, float divisor, float* out_f32, int out_fmt,
                    uint8_t* out_q, uint8_t* out_e, void* stream) {

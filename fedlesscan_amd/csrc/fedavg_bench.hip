@@ -705,6 +705,26 @@ int fa_fedavg_mx_form(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, in
     }
     return check_launch("fa_fedavg_mx_form");
 }
+int fa_fedavg_nvfp4_form(const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
+                         const float* a, const float* s, const float* c, float divisor, float* out_f32,
+                         uint16_t* out_bf16, void* stream, int form, int blocks_per_cu) {
+    bool go;
+    const int rc = nvfp4_fold_checks(X, E, N, P, ldx, lde, a, out_f32, out_bf16, &go);
+    if (!go) return rc;
+    if (form < 1 || form > 3) return fail(FA_ERR_ARG, "NVFP4 form %d: forms 1, 2 and 3", form);
+    if (blocks_per_cu < 1 || !nvfp4_vec(X, E, ldx, lde, out_f32, out_bf16))
+        return fail(FA_ERR_ARG, "NVFP4 form %d over %d blocks per CU: aligned rows, scale rows and outputs", form,
+                    blocks_per_cu);
+    StreamDevice on_stream_device(stream);
+    const NvPitched src{X, E, ldx, lde};
+    hipStream_t st = (hipStream_t)stream;
+    switch (form) {
+        case 1: launch_nvfp4<1>(st, true, src, N, P, a, s, c, divisor, out_f32, out_bf16, blocks_per_cu); break;
+        case 2: launch_nvfp4<2>(st, true, src, N, P, a, s, c, divisor, out_f32, out_bf16, blocks_per_cu); break;
+        default: launch_nvfp4<3>(st, true, src, N, P, a, s, c, divisor, out_f32, out_bf16, blocks_per_cu); break;
+    }
+    return check_launch("fa_fedavg_nvfp4_form");
+}
 int fa_fedavg_mx_q_form(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
                         const float* a, float divisor, float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e,
                         void* stream, int qform) {

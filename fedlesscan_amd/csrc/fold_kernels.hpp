@@ -3740,13 +3740,13 @@ struct MxRows {  // data(i), scale(i): the lane's pointers into row i
     __device__ __forceinline__ const D* data(int64_t i) const { return d + i * ldd; }
     __device__ __forceinline__ const S* scale(int64_t i) const { return e + i * lde; }
 };
-template <class D>
+template <class D, class S = gu8>
 struct MxTableRows {  // two tables of N bases: the data rows and their scale rows
     const uint8_t* const* xi;
     const uint8_t* const* ei;
     int64_t od, oe;
     __device__ __forceinline__ const D* data(int64_t i) const { return (const D*)xi[i] + od; }
-    __device__ __forceinline__ gu8* scale(int64_t i) const { return (gu8*)ei[i] + oe; }
+    __device__ __forceinline__ const S* scale(int64_t i) const { return (const S*)ei[i] + oe; }
 };
 struct MxPitched {
     const uint8_t *X, *E;
@@ -3809,6 +3809,52 @@ __device__ __forceinline__ void mx_group_add(float (&acc)[32], const u32x4 (&v)[
                                                    SCALED ? sc[i + u] : 1.0f);
 }
 
+// A lane's 32 quotients q of block o0 into out (fp32) and outb (RNE bf16), each
+// optional, one of them given: the epilogue of the MX and NVFP4 folds
+template <int FORM>
+__device__ __forceinline__ void mx_block_store(const float (&q)[32], float* __restrict__ out,
+                                               uint16_t* __restrict__ outb, int64_t o0, u32x4* wave_lds) {
+    if (out) {
+        f32x4* o4 = reinterpret_cast<f32x4*>(out) + 8 * o0;
+        bool exchanged = false;
+        if constexpr ((FORM & kMxExchange) != 0) {
+            // wave-uniform: all 64 lanes are here, so the wave's 64 blocks are 8 KiB contiguous in out
+            if (__builtin_amdgcn_ballot_w64(true) == ~0ull) {
+                const int lane = threadIdx.x & 63;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    wave_lds[8 * lane + k] =
+                        __builtin_bit_cast(u32x4, f32x4{q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]});
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                f32x4* wave_out = o4 - 8 * lane;  // the block of lane 0
+#pragma unroll
+                for (int k = 0; k < 8; ++k) st16(wave_out + 64 * k + lane, wave_lds[64 * k + lane]);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                exchanged = true;
+            }
+        }
+        if (!exchanged) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                st16(o4 + k, __builtin_bit_cast(u32x4, f32x4{q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]}));
+        }
+    }
+    if (outb) {
+        u32x4* o8 = reinterpret_cast<u32x4*>(outb) + 4 * o0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            u32x4 b;
+            b.x = (uint32_t)f2bf_rne(q[8 * k]) | ((uint32_t)f2bf_rne(q[8 * k + 1]) << 16);
+            b.y = (uint32_t)f2bf_rne(q[8 * k + 2]) | ((uint32_t)f2bf_rne(q[8 * k + 3]) << 16);
+            b.z = (uint32_t)f2bf_rne(q[8 * k + 4]) | ((uint32_t)f2bf_rne(q[8 * k + 5]) << 16);
+            b.w = (uint32_t)f2bf_rne(q[8 * k + 6]) | ((uint32_t)f2bf_rne(q[8 * k + 7]) << 16);
+            st16(o8 + k, b);
+        }
+    }
+}
+
 // The lane's block o0 of rows 0..N-1 of src, in row order
 // Q (an MxQ): the block also leaves as MX codes in outq and its scale byte in
 // oute[o0]; the lane owns the whole block, so nothing crosses lanes but the
@@ -3866,46 +3912,7 @@ __device__ __forceinline__ void fold_mx_block(Rows src, int64_t N, const float* 
     float q[32];
 #pragma unroll
     for (int j = 0; j < 32; ++j) q[j] = acc[j] / divisor;
-    // out (fp32) and outb (RNE bf16) are each optional, one of them given
-    if (out) {
-        f32x4* o4 = reinterpret_cast<f32x4*>(out) + 8 * o0;
-        bool exchanged = false;
-        if constexpr ((FORM & kMxExchange) != 0) {
-            // wave-uniform: all 64 lanes are here, so the wave's 64 blocks are 8 KiB contiguous in out
-            if (__builtin_amdgcn_ballot_w64(true) == ~0ull) {
-                const int lane = threadIdx.x & 63;
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    wave_lds[8 * lane + k] =
-                        __builtin_bit_cast(u32x4, f32x4{q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]});
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                f32x4* wave_out = o4 - 8 * lane;  // the block of lane 0
-#pragma unroll
-                for (int k = 0; k < 8; ++k) st16(wave_out + 64 * k + lane, wave_lds[64 * k + lane]);
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                exchanged = true;
-            }
-        }
-        if (!exchanged) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                st16(o4 + k, __builtin_bit_cast(u32x4, f32x4{q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]}));
-        }
-    }
-    if (outb) {
-        u32x4* o8 = reinterpret_cast<u32x4*>(outb) + 4 * o0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            u32x4 b;
-            b.x = (uint32_t)f2bf_rne(q[8 * k]) | ((uint32_t)f2bf_rne(q[8 * k + 1]) << 16);
-            b.y = (uint32_t)f2bf_rne(q[8 * k + 2]) | ((uint32_t)f2bf_rne(q[8 * k + 3]) << 16);
-            b.z = (uint32_t)f2bf_rne(q[8 * k + 4]) | ((uint32_t)f2bf_rne(q[8 * k + 5]) << 16);
-            b.w = (uint32_t)f2bf_rne(q[8 * k + 6]) | ((uint32_t)f2bf_rne(q[8 * k + 7]) << 16);
-            st16(o8 + k, b);
-        }
-    }
+    mx_block_store<FORM>(q, out, outb, o0, wave_lds);
     if constexpr (Q::kOn) {
         const uint32_t E = Q::scale_byte(mx_q_amax(q));
         const typename Q::Block b = Q::prepare(E);
@@ -4039,6 +4046,219 @@ FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_mx_q_scalar(
         if (out) out[col] = q;
     }
     mx_q_column<Q>(q, valid, col, outq, oute);
+}
+
+// ---------------------------------------------------------------------------
+// NVFP4 rows (e2m1 nibbles as MXFP4's; one e4m3fn scale byte per 16 flat
+// elements; a float32 scale per tensor: the client scale c; fa_fedavg_nvfp4,
+// fa_fedavg_nvfp4_ptrs; DESIGN.md 2 and 5 NVFP4).  Per client i and column p
+//   x = f32(q_i[p]);  x = fl(x * f32_e4m3fn(e_i[p >> 4]))  (exact when finite)
+//   x = fl(x * c_i) [scaled];  t = fl(x * a_i);  t = fl(t * s_i) [scored]
+//   acc = t_0;  acc = fl(acc + t_i) in row order;  out = fl(acc / divisor)
+// Geometry: a lane owns one UNIT of 32 columns = TWO NVFP4 blocks: 32 float32
+// accumulators, per row one 16-byte load of codes and one 16-bit load of its
+// two scale bytes; a wave reads 1 KiB of a row and 128 contiguous scale bytes.
+// Tiles of kMxTileCols columns walked as the MX fold walks them, kNvU rows per
+// load group with the scale pair in the row's group, two groups alternating,
+// the MX fold's epilogue (mx_block_store).  The scale has a mantissa, so the
+// scaled convert (which takes an exponent) cannot apply it: the codes are
+// converted with a scale of 1.0, the scale pair by one v_cvt_pk_f32_fp8 of the
+// 16-bit word, and each product is an IEEE multiply: the low scale for the
+// unit's first 16 columns, the high one for its last 16.  The 16-bit load adds
+// a condition to the vector path: scale rows (base and pitch) 2-byte aligned.
+// FORM: kMxAhead | kMxExchange, the bits of the MX fold.
+// ---------------------------------------------------------------------------
+constexpr int kNvBlockLg = 4;  // columns per scale byte
+constexpr int kNvU = 16;       // rows per load group
+
+// The scale pair of a unit as float32 (x: columns 0..15, y: columns 16..31)
+__device__ __forceinline__ f32x2 nv_scales(uint32_t e2) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_cvt_pk_f32_fp8((int)e2, false);
+#else
+    return f32x2{0.0f, 0.0f};
+#endif
+}
+__device__ __forceinline__ float nv_scale(uint32_t e) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_cvt_f32_fp8((int)e, 0);
+#else
+    return 0.0f;
+#endif
+}
+
+// The row sources.  unit(o): the lane's unit o (16 bytes of codes and the scale
+// pair of row i); column(c): one column, its code byte and its scale byte.
+struct NvPitched {
+    const uint8_t *X, *E;
+    int64_t ldx, lde;
+    __device__ __forceinline__ MxRows<u32x4, uint16_t> unit(int64_t o) const {
+        return {reinterpret_cast<const u32x4*>(X) + o, reinterpret_cast<const uint16_t*>(E) + o, ldx >> 4, lde >> 1};
+    }
+    __device__ __forceinline__ MxRows<uint8_t, uint8_t> column(int64_t c) const {
+        return {X + (c >> 1), E + (c >> kNvBlockLg), ldx, lde};
+    }
+};
+struct NvTable {
+    const uint8_t* const* xi;
+    const uint8_t* const* ei;
+    __device__ __forceinline__ MxTableRows<gu32x4, gu16> unit(int64_t o) const { return {xi, ei, o, o}; }
+    __device__ __forceinline__ MxTableRows<gu8> column(int64_t c) const { return {xi, ei, c >> 1, c >> kNvBlockLg}; }
+};
+
+// One row's unit into the lane's 32 accumulators (FIRST: acc = t_0, not 0 + t_0)
+template <bool SCORED, bool SCALED, bool FIRST>
+__device__ __forceinline__ void nv_unit_add(float (&acc)[32], const u32x4& v, uint32_t e2, float a, float s, float c) {
+    const f32x2 sf = nv_scales(e2);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t w = k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w;
+        float x[8];
+        MxE2M1::word<false>(w, 1.0f, x);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float t = mx_term<SCORED, SCALED, false>(x[j], k < 2 ? sf.x : sf.y, a, s, c);
+            acc[8 * k + j] = FIRST ? t : acc[8 * k + j] + t;
+        }
+    }
+}
+
+// One load group: U rows' codes and scale pairs of the lane's unit
+template <int U, class Rows>
+__device__ __forceinline__ void nv_ld(u32x4 (&v)[U], uint32_t (&e)[U], Rows src, int64_t i) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        v[u] = __builtin_nontemporal_load(src.data(i + u));
+        e[u] = __builtin_nontemporal_load(src.scale(i + u));
+    }
+}
+template <int U, bool SCORED, bool SCALED>
+__device__ __forceinline__ void nv_group_add(float (&acc)[32], const u32x4 (&v)[U], const uint32_t (&e)[U],
+                                             const float* __restrict__ a, const float* __restrict__ s,
+                                             const float* __restrict__ sc, int64_t i) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        nv_unit_add<SCORED, SCALED, false>(acc, v[u], e[u], a[i + u], SCORED ? s[i + u] : 1.0f,
+                                           SCALED ? sc[i + u] : 1.0f);
+}
+
+// The lane's unit o0 of rows 0..N-1 of src, in row order
+template <bool SCORED, bool SCALED, int FORM, class Rows>
+__device__ __forceinline__ void fold_nvfp4_unit(Rows src, int64_t N, const float* __restrict__ a,
+                                                const float* __restrict__ s, const float* __restrict__ sc,
+                                                float divisor, float* __restrict__ out, uint16_t* __restrict__ outb,
+                                                int64_t o0, u32x4* wave_lds) {
+    constexpr int U = kNvU;
+    float acc[32];
+    {
+        u32x4 v[1];
+        uint32_t e[1];
+        nv_ld<1>(v, e, src, 0);
+        nv_unit_add<SCORED, SCALED, true>(acc, v[0], e[0], a[0], SCORED ? s[0] : 1.0f, SCALED ? sc[0] : 1.0f);
+    }
+    int64_t i = 1;
+    if constexpr ((FORM & kMxAhead) != 0) {
+        if (i + U <= N) {
+            u32x4 va[U], vb[U];
+            uint32_t ea[U], eb[U];
+            nv_ld<U>(va, ea, src, i);
+            for (;;) {
+                const bool more_b = i + 2 * U <= N;
+                if (more_b) nv_ld<U>(vb, eb, src, i + U);
+                __builtin_amdgcn_sched_barrier(0);  // the younger group's loads are issued ahead of these adds
+                nv_group_add<U, SCORED, SCALED>(acc, va, ea, a, s, sc, i);
+                i += U;
+                if (!more_b) break;
+                const bool more_a = i + 2 * U <= N;
+                if (more_a) nv_ld<U>(va, ea, src, i + U);
+                __builtin_amdgcn_sched_barrier(0);
+                nv_group_add<U, SCORED, SCALED>(acc, vb, eb, a, s, sc, i);
+                i += U;
+                if (!more_a) break;
+            }
+        }
+    } else {
+        for (; i + U <= N; i += U) {
+            u32x4 v[U];
+            uint32_t e[U];
+            nv_ld<U>(v, e, src, i);
+            nv_group_add<U, SCORED, SCALED>(acc, v, e, a, s, sc, i);
+        }
+    }
+    for (; i < N; ++i) {
+        u32x4 v[1];
+        uint32_t e[1];
+        nv_ld<1>(v, e, src, i);
+        nv_unit_add<SCORED, SCALED, false>(acc, v[0], e[0], a[i], SCORED ? s[i] : 1.0f, SCALED ? sc[i] : 1.0f);
+    }
+    float q[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) q[j] = acc[j] / divisor;
+    mx_block_store<FORM>(q, out, outb, o0, wave_lds);
+}
+
+// One column, 8 rows of loads ahead of the ordered adds (a tail lane of the
+// vector path, every lane of the one-column kernel): the f32 quotient
+template <bool SCORED, bool SCALED, class Rows>
+__device__ __forceinline__ float fold_column_nvfp4(Rows src, int64_t col, int64_t N, const float* __restrict__ a,
+                                                   const float* __restrict__ s, const float* __restrict__ sc,
+                                                   float divisor) {
+    auto term = [&](uint32_t byte, uint32_t e, int64_t i) {
+        return mx_term<SCORED, SCALED, false>(MxE2M1::one<false>(byte, col, 1.0f), nv_scale(e), a[i],
+                                              SCORED ? s[i] : 1.0f, SCALED ? sc[i] : 1.0f);
+    };
+    float acc = term(*src.data(0), *src.scale(0), 0);
+    int64_t i = 1;
+    for (; i + 8 <= N; i += 8) {
+        uint8_t v[8], e[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            v[u] = __builtin_nontemporal_load(src.data(i + u));
+            e[u] = __builtin_nontemporal_load(src.scale(i + u));
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc = acc + term(v[u], e[u], i + u);
+    }
+    for (; i < N; ++i) acc = acc + term(*src.data(i), *src.scale(i), i);
+    return acc / divisor;
+}
+
+// The vector path: code rows and outputs 16-B aligned, scale rows 2-B aligned
+// (a stacked matrix: ldx % 16 == 0 and lde % 2 == 0 too), grid-stride over the
+// tiles.  The whole 32-column units have both of their scale bytes; the
+// trailing P % 32 columns (a lone block, a partial block, or a block and a
+// partial one) go column by column to the first idle lane, each with scale
+// byte col >> 4, so no byte past ceil(P / 16) is read.  Src: NvPitched or NvTable.
+template <bool SCORED, bool SCALED, int FORM, class Src>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_nvfp4_gs(
+    Src src, int64_t N, int64_t P, const float* __restrict__ a, const float* __restrict__ s,
+    const float* __restrict__ sc, float divisor, float* __restrict__ out, uint16_t* __restrict__ outb,
+    int64_t ntiles) {
+    u32x4* wave_lds = nullptr;
+    if constexpr ((FORM & kMxExchange) != 0) {
+        __shared__ u32x4 lds[kBlock * 8];  // 64 lanes x 128 B per wave
+        wave_lds = lds + (threadIdx.x >> 6) * 512;
+    }
+    auto unit = [&](int64_t o) {
+        fold_nvfp4_unit<SCORED, SCALED, FORM>(src.unit(o), N, a, s, sc, divisor, out, outb, o, wave_lds);
+    };
+    for (int64_t bid = blockIdx.x; bid < ntiles; bid += gridDim.x)
+        octet_tile<1, kBlock, kMxLG>(bid, P, unit, unit, [&](int64_t col) {
+            for (; col < P; ++col)
+                st_column_bf16(fold_column_nvfp4<SCORED, SCALED>(src.column(col), col, N, a, s, sc, divisor), out, outb,
+                               col);
+        });
+}
+
+// One lane per column: rows and scale rows at any byte offset, any pitch, any
+// output alignment
+template <bool SCORED, bool SCALED, class Src>
+FA_NO_PACKED_F32 __global__ __launch_bounds__(kBlock) void k_fedavg_nvfp4_scalar(
+    Src src, int64_t N, int64_t P, const float* __restrict__ a, const float* __restrict__ s,
+    const float* __restrict__ sc, float divisor, float* __restrict__ out, uint16_t* __restrict__ outb) {
+    const int64_t col = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (col >= P) return;
+    st_column_bf16(fold_column_nvfp4<SCORED, SCALED>(src.column(col), col, N, a, s, sc, divisor), out, outb, col);
 }
 
 // ---------------------------------------------------------------------------
@@ -5798,15 +6018,10 @@ inline int mx_format_check(int fmt, int64_t P) {
     return FA_OK;
 }
 
-// The checks of the stacked fold: *go = true to launch (false with FA_OK: nothing to fold)
-inline int mx_fold_checks(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
-                          const float* a, float* out_f32, uint16_t* out_bf16, bool* go, const void* q_out = nullptr) {
-    *go = false;
-    if (N < 0 || P < 0) return fail(FA_ERR_ARG, "negative size (N=%lld, P=%lld)", (long long)N, (long long)P);
-    if (N == 0) return fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
-    int rc = mx_format_check(fmt, P);
-    if (rc) return rc;
-    const int64_t xb = mx_row_bytes(fmt, P), eb = mx_scale_bytes(P);
+// What the stacked MX and NVFP4 folds check of rows of xb bytes with scale rows of eb bytes, behind their sizes
+inline int scaled_rows_checks(const char* what, int64_t xb, int64_t eb, const uint8_t* X, const uint8_t* E, int64_t N,
+                              int64_t P, int64_t ldx, int64_t lde, const float* a, float* out_f32, uint16_t* out_bf16,
+                              bool* go, const void* q_out) {
     if (ldx < xb || lde < eb)
         return fail(FA_ERR_SHAPE, "row pitch ldx=%lld < %lld bytes or scale pitch lde=%lld < %lld bytes", (long long)ldx,
                     (long long)xb, (long long)lde, (long long)eb);
@@ -5817,10 +6032,21 @@ inline int mx_fold_checks(int fmt, const uint8_t* X, const uint8_t* E, int64_t N
         const void* o = k ? (const void*)out_bf16 : (const void*)out_f32;
         const size_t ob = (size_t)P * (k ? 2 : 4);
         if (o && (overlaps(o, ob, X, xbytes) || overlaps(o, ob, E, ebytes)))
-            return fail(FA_ERR_ARG, "fa_fedavg_mx: an output overlaps the rows or their scales");
+            return fail(FA_ERR_ARG, "%s: an output overlaps the rows or their scales", what);
     }
     *go = true;
     return FA_OK;
+}
+// The checks of the stacked fold: *go = true to launch (false with FA_OK: nothing to fold)
+inline int mx_fold_checks(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
+                          const float* a, float* out_f32, uint16_t* out_bf16, bool* go, const void* q_out = nullptr) {
+    *go = false;
+    if (N < 0 || P < 0) return fail(FA_ERR_ARG, "negative size (N=%lld, P=%lld)", (long long)N, (long long)P);
+    if (N == 0) return fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
+    int rc = mx_format_check(fmt, P);
+    if (rc) return rc;
+    return scaled_rows_checks("fa_fedavg_mx", mx_row_bytes(fmt, P), mx_scale_bytes(P), X, E, N, P, ldx, lde, a, out_f32,
+                              out_bf16, go, q_out);
 }
 inline bool mx_vec(const uint8_t* X, int64_t ldx, const float* out_f32, const uint16_t* out_bf16) {
     return aligned16(X) && (ldx % 16 == 0) && aligned16(out_f32) && aligned16(out_bf16);
@@ -5851,6 +6077,82 @@ inline int mx_rows_fold(int fmt, const uint8_t* const* xi, const uint8_t* const*
                      [&](hipStream_t st) {
                          launch_mx_fmt<kMxForm>(fmt, st, rows_aligned != 0, MxTable{xi, ei}, N, P, a, s, c, divisor,
                                                 out_f32, out_bf16);
+                         return 0;
+                     });
+}
+
+// ---- the NVFP4 folds (fa_fedavg_nvfp4, fa_fedavg_nvfp4_ptrs) -------------------
+// The MX fold's tiles and grid rule over units of two NVFP4 blocks; one
+// geometry, fixed on the host, no tuner kind.  vec: the vector path, else one
+// column per lane.
+static_assert(kNvU == FA_NVFP4_ROWS_AHEAD && (1 << kNvBlockLg) == FA_NVFP4_BLOCK, "the header states the NVFP4 geometry");
+constexpr int kNvForm = kMxAhead | kMxExchange;  // the product's form
+
+template <int FORM, class Src>
+void launch_nvfp4(hipStream_t st, bool vec, Src src, int64_t N, int64_t P, const float* a, const float* s,
+                  const float* c, float d, float* out, uint16_t* outb, int blocks_per_cu = kMxBlocksPerCu) {
+    const OctetGrid g = octet_grid(P, 1, -blocks_per_cu, cu_count(), kMxLG);
+    with_scored(s != nullptr, [&](auto SC) {
+        with_scored(c != nullptr, [&](auto CS) {
+            constexpr bool kScored = decltype(SC)::value, kScaled = decltype(CS)::value;
+            if (vec)
+                hipLaunchKernelGGL((k_fedavg_nvfp4_gs<kScored, kScaled, FORM, Src>), dim3((unsigned)g.grid), dim3(kBlock),
+                                   0, st, src, N, P, a, s, c, d, out, outb, g.tiles);
+            else
+                hipLaunchKernelGGL((k_fedavg_nvfp4_scalar<kScored, kScaled, Src>), grid_for(P), dim3(kBlock), 0, st, src,
+                                   N, P, a, s, c, d, out, outb);
+        });
+    });
+}
+
+inline int nvfp4_size_check(int64_t P) {
+    if (P & 1) return fail(FA_ERR_ARG, "NVFP4 rows hold two columns per byte: P=%lld is odd", (long long)P);
+    return FA_OK;
+}
+inline int64_t nvfp4_scale_bytes(int64_t P) { return (P + FA_NVFP4_BLOCK - 1) / FA_NVFP4_BLOCK; }
+
+// The checks of the stacked fold: *go = true to launch (false with FA_OK: nothing to fold)
+inline int nvfp4_fold_checks(const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
+                             const float* a, float* out_f32, uint16_t* out_bf16, bool* go) {
+    *go = false;
+    if (N < 0 || P < 0) return fail(FA_ERR_ARG, "negative size (N=%lld, P=%lld)", (long long)N, (long long)P);
+    if (N == 0) return fail(FA_ERR_NO_CLIENTS, "no client results to aggregate (N == 0)");
+    const int rc = nvfp4_size_check(P);
+    if (rc) return rc;
+    return scaled_rows_checks("fa_fedavg_nvfp4", P / 2, nvfp4_scale_bytes(P), X, E, N, P, ldx, lde, a, out_f32, out_bf16,
+                              go, nullptr);
+}
+// The vector path's conditions: the MX fold's, and scale rows the 16-bit load can read
+inline bool nvfp4_vec(const uint8_t* X, const uint8_t* E, int64_t ldx, int64_t lde, const float* out_f32,
+                      const uint16_t* out_bf16) {
+    return mx_vec(X, ldx, out_f32, out_bf16) && ((uintptr_t)E % 2 == 0) && (lde % 2 == 0);
+}
+
+inline int nvfp4_fold(const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde, const float* a,
+                      const float* s, const float* c, float divisor, float* out_f32, uint16_t* out_bf16, void* stream) {
+    bool go;
+    const int rc = nvfp4_fold_checks(X, E, N, P, ldx, lde, a, out_f32, out_bf16, &go);
+    if (!go) return rc;
+    StreamDevice on_stream_device(stream);
+    launch_nvfp4<kNvForm>((hipStream_t)stream, nvfp4_vec(X, E, ldx, lde, out_f32, out_bf16), NvPitched{X, E, ldx, lde}, N,
+                          P, a, s, c, divisor, out_f32, out_bf16);
+    return check_launch("fa_fedavg_nvfp4");
+}
+
+// xi, ei: [device] tables of the N code rows and of their N scale rows;
+// rows_aligned: every code row 16-B and every scale row 2-B aligned
+inline int nvfp4_rows_fold(const uint8_t* const* xi, const uint8_t* const* ei, int64_t N, int64_t P, const float* a,
+                           const float* s, const float* c, float divisor, int rows_aligned, float* out_f32,
+                           uint16_t* out_bf16, void* stream) {
+    const int rc = nvfp4_size_check(P);
+    if (rc) return rc;
+    if (P > 0 && !ei) return fail(FA_ERR_ARG, "null scale-row table");
+    const bool fits = !rows_aligned || (aligned16(out_f32) && aligned16(out_bf16));
+    return rows_fold("fa_fedavg_nvfp4_ptrs", xi, N, P, a, bf16_any_out(out_f32, out_bf16), stream,
+                     fits ? nullptr : "the vector path of the NVFP4 row-table fold needs 16-B aligned rows and outputs",
+                     [&](hipStream_t st) {
+                         launch_nvfp4<kNvForm>(st, rows_aligned != 0, NvTable{xi, ei}, N, P, a, s, c, divisor, out_f32,
+                                               out_bf16);
                          return 0;
                      });
 }

@@ -56,6 +56,26 @@ class ScaledLayer(NamedTuple):
 _MX_FORMATS = {torch.float8_e4m3fn: _lib.FA_MX_E4M3, torch.float8_e5m2: _lib.FA_MX_E5M2,
                torch.float4_e2m1fn_x2: _lib.FA_MX_E2M1}
 _MX_SCALE_DTYPES = (torch.uint8, torch.float8_e8m0fnu)
+# float4_e2m1fn_x2 rows whose block scales have this dtype are NVFP4: one e4m3fn scale byte per 16 flat elements
+_NVFP4_SCALE_DTYPE = torch.float8_e4m3fn
+_SCALE_BYTES_MSG = "E8M0 bytes (float8_e8m0fnu or uint8; float8_e4m3fn with float4_e2m1fn_x2 rows: NVFP4)"
+
+
+def _is_nvfp4(e) -> bool:
+    return isinstance(e, torch.Tensor) and e.dtype == _NVFP4_SCALE_DTYPE
+
+
+def _block_scale_kind(dt: torch.dtype, e, what: str) -> int:
+    """The elements per scale byte of rows of dtype dt with the block scales e:
+    32 (MX, E8M0 bytes) or 16 (NVFP4, e4m3fn bytes with float4 rows)."""
+    if _is_nvfp4(e):
+        if dt != torch.float4_e2m1fn_x2:
+            raise InvalidParameterShapeError(f"{what}: float8_e4m3fn block scales are NVFP4's and go with "
+                                             f"float4_e2m1fn_x2 rows, got {dt} rows")
+        return _lib.FA_NVFP4_BLOCK
+    if not (isinstance(e, torch.Tensor) and e.dtype in _MX_SCALE_DTYPES):
+        raise InvalidParameterShapeError(f"{what} must hold {_SCALE_BYTES_MSG}, got {getattr(e, 'dtype', type(e))}")
+    return 32
 
 
 class MXLayer(NamedTuple):
@@ -68,7 +88,11 @@ class MXLayer(NamedTuple):
     along it), scale an optional dequantisation scale of the whole tensor (as
     ScaledLayer's).  The layer counts as upcast(q) * 2^(e - 127) [* scale]; the
     result has q's shape, the last dimension doubled for float4.  Every client
-    wraps a layer, in one format, or none does."""
+    wraps a layer, in one format, or none does.
+    NVFP4: q float4_e2m1fn_x2 and e of dtype float8_e4m3fn, one scale byte per
+    16 elements of the flattened layer (ceil(size / 16)), scale the tensor's
+    float32 scale: the layer counts as upcast(q) * float32(e) [* scale]
+    (fa_fedavg_nvfp4_ptrs, a fold per layer)."""
     q: torch.Tensor
     e: torch.Tensor
     scale: Optional[float] = None
@@ -482,6 +506,10 @@ def fold_stacked(X: torch.Tensor, weights: Sequence, scores: Optional[Sequence] 
     uint8, any pitch) with X [N, P] of float8_e4m3fn / float8_e5m2 or [N, P / 2]
     of float4_e2m1fn_x2; element p of row i counts as upcast(q) * 2^(E[i, p >>
     5] - 127), then scales= as for fp8 rows (MXLayer says the rest).
+    NVFP4 rows: X [N, P / 2] of float4_e2m1fn_x2 with block_scales= E of dtype
+    float8_e4m3fn, [N, ceil(P / 16)] at any pitch; element p counts as
+    upcast(q) * float32(E[i, p >> 4]), scales= the tensors' float32 scales
+    (fa_fedavg_nvfp4); out_format / out_mx do not go with them.
     fp8 and MX rows: out_format= (float8_e4m3fn, float8_e5m2 or
     float4_e2m1fn_x2) quantises the result to MX in the same launch
     (fa_fedavg_fp8_q / fa_fedavg_mx_q; the contract is DESIGN.md 2's) and
@@ -1082,7 +1110,7 @@ _NO_CAPTURE_TABLE = (torch.float64, torch.int32, torch.int64)
 # there and itself in mx_table_folds)
 stats = {"rows16_folds": 0, "rows64_folds": 0, "stacked_groups": 0, "layer_table_folds": 0, "rows_int_folds": 0,
          "widened_folds": 0, "widened_row_folds": 0, "widened_table_folds": 0, "fp8_folds": 0,
-         "mx_folds": 0, "mx_out_folds": 0, "mx_table_folds": 0}
+         "mx_folds": 0, "mx_out_folds": 0, "mx_table_folds": 0, "nvfp4_folds": 0}
 
 
 class RowSet:
@@ -1112,6 +1140,7 @@ class RowSet:
     bases for fa_fedavg_mx_ptrs (`cols`: the columns of the fold)."""
 
     scale_rows = None  # the E8M0 scale rows of an MX row set (a set assembled without __init__ has none)
+    block = 32  # the elements per scale byte: 32 (MX) or 16 (NVFP4: float8_e4m3fn scale rows)
 
     def __init__(self, rows: Sequence[torch.Tensor], block_scales: Optional[Sequence[torch.Tensor]] = None):
         rows = list(rows)
@@ -1152,21 +1181,26 @@ class RowSet:
         if self.dtype not in _MX_FORMATS:
             raise InvalidParameterShapeError(f"block_scales are for fp8 / float4_e2m1fn_x2 rows, got {self.dtype}")
         self.cols = _mx_cols(self.dtype, self.P)
-        nb = (self.cols + 31) // 32
         if len(es) != N:
             raise InvalidParameterShapeError(f"{N} rows but {len(es)} block-scale rows")
         for i, e in enumerate(es):
-            if not (isinstance(e, torch.Tensor) and e.dtype in _MX_SCALE_DTYPES):
-                raise InvalidParameterShapeError(f"block_scales[{i}] must hold E8M0 bytes (float8_e8m0fnu or uint8), "
-                                                 f"got {getattr(e, 'dtype', type(e))}")
+            blk = _block_scale_kind(self.dtype, e, f"block_scales[{i}]")
+            if i == 0:
+                self.block = blk  # 32: MX rows; 16: NVFP4 rows
+            elif blk != self.block:
+                raise InvalidParameterShapeError(f"block_scales[{i}]: the rows of one set fold in one format, MXFP4 (E8M0 "
+                                                 f"scales) or NVFP4 (float8_e4m3fn scales), got {e.dtype}")
+            nb = (self.cols + blk - 1) // blk
             if e.numel() != nb or not e.is_contiguous() or e.device != dev:
                 raise InvalidParameterShapeError(f"block_scales[{i}]: {e.numel()} scale bytes for {self.cols} columns "
-                                                 f"(one per 32: {nb}, contiguous, on {dev})")
+                                                 f"(one per {blk}: {nb}, contiguous, on {dev})")
         self.scale_rows = es
         if self.P > 0:
             self.host_ptrs = np.fromiter(map(torch.Tensor.data_ptr, self.rows + es), dtype=np.int64, count=2 * N)
             self.ptrs = torch.from_numpy(self.host_ptrs).to(dev)
             self.aligned = not (self.host_ptrs[:N] % 16).any()
+            if self.block == _lib.FA_NVFP4_BLOCK:  # the vector path reads a unit's two scale bytes in one 16-bit load
+                self.aligned = self.aligned and not (self.host_ptrs[N:] % 2).any()
 
     def overlaps(self, t: torch.Tensor) -> bool:
         """Does tensor t share a byte with any row (or scale row)?"""
@@ -1360,8 +1394,9 @@ def _fold_mx(X: Optional[torch.Tensor], E: Optional[torch.Tensor], rs: Optional[
     in ONE staged upload, the bf16 fold's outputs.  Everything is decided here
     on the host before the launch; an output that shares bytes with a row or a
     scale row is folded into a fresh buffer and copied."""
+    nv = _is_nvfp4(E) if X is not None else rs.block == _lib.FA_NVFP4_BLOCK
     if torch.cuda.is_current_stream_capturing():
-        raise InvalidParameterShapeError("the MX fold does not run under stream capture "
+        raise InvalidParameterShapeError(f"the {'NVFP4' if nv else 'MX'} fold does not run under stream capture "
                                          "(its factors and scales are staged by a copy the graph would not own)")
     if X is not None:
         N, Pb, ldx = _check_matrix(X)
@@ -1370,13 +1405,11 @@ def _fold_mx(X: Optional[torch.Tensor], E: Optional[torch.Tensor], rs: Optional[
         if E is None:
             raise InvalidParameterShapeError(f"{X.dtype} rows fold only with their block_scales")
         dev, fmt, P = X.device, _MX_FORMATS[X.dtype], _mx_cols(X.dtype, Pb)
-        nb = (P + 31) // 32
-        if not (isinstance(E, torch.Tensor) and E.dtype in _MX_SCALE_DTYPES):
-            raise InvalidParameterShapeError("block_scales must hold E8M0 bytes (float8_e8m0fnu or uint8), got "
-                                             f"{getattr(E, 'dtype', type(E))}")
+        blk = _block_scale_kind(X.dtype, E, "block_scales")
+        nb = (P + blk - 1) // blk
         if E.device != dev or tuple(E.shape) != (N, nb) or (nb > 1 and E.stride(1) != 1):
             raise InvalidParameterShapeError(f"block_scales must be [{N}, {nb}] on {dev} with unit column stride (one "
-                                             f"byte per 32 of {P} columns), got {tuple(E.shape)}")
+                                             f"byte per {blk} of {P} columns), got {tuple(E.shape)}")
         lde = E.stride(0) if N > 1 else max(nb, 1)
         if lde < nb:
             raise InvalidParameterShapeError(f"block_scales rows overlap (pitch {lde} < {nb})")
@@ -1387,6 +1420,9 @@ def _fold_mx(X: Optional[torch.Tensor], E: Optional[torch.Tensor], rs: Optional[
         raise InvalidParameterShapeError(f"float4_e2m1fn_x2 rows hold two columns per byte: {P} columns")
     if scales is not None and len(scales) != N:
         raise InvalidParameterShapeError(f"{N} rows but {len(scales)} scales")
+    if nv and (out_format is not None or out_mx is not None):
+        raise InvalidParameterShapeError("out_format / out_mx do not go with NVFP4 rows (float8_e4m3fn block scales): "
+                                         "their fold returns float32 / bfloat16")
     _check_out("out", out, torch.float32, P)
     _check_out("out_bf16", out_bf16, torch.bfloat16, P)
 
@@ -1417,7 +1453,16 @@ def _fold_mx(X: Optional[torch.Tensor], E: Optional[torch.Tensor], rs: Optional[
     staged = stage_factors(parts, dev)
     a, s = staged[0], (staged[1] if f.s is not None else None)
     c = staged[-1] if scales is not None else None
-    if qo is not None and X is not None:
+    if nv and X is not None:
+        _lib.call("fa_fedavg_nvfp4", X.data_ptr(), E.data_ptr(), N, P, ldx, lde, a.data_ptr(), _ptr(s), _ptr(c),
+                  float(f.div), _ptr(out), _ptr(outb), stream_ptr(dev))
+    elif nv:
+        aligned = (rs.aligned and (out is None or out.data_ptr() % 16 == 0)
+                   and (outb is None or outb.data_ptr() % 16 == 0))
+        xi = rs.ptrs.data_ptr() if P else 0
+        _lib.call("fa_fedavg_nvfp4_ptrs", xi, xi + 8 * N, N, P, a.data_ptr(), _ptr(s), _ptr(c), float(f.div),
+                  int(aligned), _ptr(out), _ptr(outb), stream_ptr(dev))
+    elif qo is not None and X is not None:
         _lib.call("fa_fedavg_mx_q", fmt, X.data_ptr(), E.data_ptr(), N, P, ldx, lde, a.data_ptr(), _ptr(s), _ptr(c),
                   float(f.div), _ptr(out), *qo.args(), stream_ptr(dev))
     elif qo is not None:
@@ -1434,7 +1479,7 @@ def _fold_mx(X: Optional[torch.Tensor], E: Optional[torch.Tensor], rs: Optional[
         xi = rs.ptrs.data_ptr() if P else 0
         _lib.call("fa_fedavg_mx_ptrs", fmt, xi, xi + 8 * N, N, P, a.data_ptr(), _ptr(s), _ptr(c), float(f.div),
                   int(aligned), _ptr(out), _ptr(outb), stream_ptr(dev))
-    stats["mx_folds"] += 1
+    stats["nvfp4_folds" if nv else "mx_folds"] += 1
     if dst is not None and dst is not out:
         dst.reshape(-1)[:P].copy_(out)
         out = dst
@@ -1810,6 +1855,9 @@ class ModelRowSet:
                     f"layer {lis[k]}: all clients' tensors must be contiguous with one shape, dtype and device")
             cols = _mx_cols(dt, qs[0].numel())
             nb = (cols + 31) // 32
+            if any(map(_is_nvfp4, es)):
+                raise InvalidParameterShapeError(f"layer {lis[k]}: NVFP4 layers (float8_e4m3fn block scales) have no "
+                                                 "layer table: aggregate_layers folds each in a launch of its own")
             for i, e in enumerate(es):
                 if not (isinstance(e, torch.Tensor) and e.dtype in _MX_SCALE_DTYPES):
                     raise InvalidParameterShapeError(f"layer {lis[k]}, client {i}: the scale row must hold E8M0 bytes "
@@ -2248,6 +2296,9 @@ def _unwrap_mx(parameters, n_eff):
         if len({p[li].q.dtype for p in plain}) != 1 or plain[0][li].q.dtype not in _MX_FORMATS:
             raise InvalidParameterShapeError(f"layer {li}: MX layers fold in one format, every client's alike; got "
                                              f"{sorted({str(p[li].q.dtype) for p in plain})}")
+        if len({_is_nvfp4(p[li].e) for p in plain}) != 1:
+            raise InvalidParameterShapeError(f"layer {li}: MX layers fold in one format, every client's alike; got MXFP4 "
+                                             "(E8M0 scales) and NVFP4 (float8_e4m3fn scales)")
         mx[li] = ([p[li].e.reshape(-1) for p in plain], [p[li].scale for p in plain] if all(given) else None)
         for p in plain:
             p[li] = p[li].q
@@ -2360,7 +2411,7 @@ def aggregate_layers(parameters: Sequence[Sequence], weights: Sequence, scores: 
             # device fp8 layers: each folds from the clients' own bytes through its row table.  Two or more
             # MX layers on the fold's device: one table and one launch per sub-group (the layers with client
             # scales, the layers without; FEDAVG_LAYER_TABLE=0: a fold per layer); the same bits either way
-            tabled = [li for li in lis if li in layer_mx]
+            tabled = [li for li in lis if li in layer_mx and not _is_nvfp4(layer_mx[li][0][0])]  # NVFP4: no table
             if (len(tabled) >= 2 and layer_table_enabled() and not torch.cuda.is_current_stream_capturing()
                     and _mx_group_here(parameters, layer_mx, n_eff, tabled, dev)):
                 folded = set()

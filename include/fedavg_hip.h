@@ -757,8 +757,9 @@ int fa_fedavg_fp8_ptrs(int fmt, const uint8_t* const* xi, int64_t N, int64_t P,
  * through LDS so that each store instruction writes 1 KiB contiguous; the
  * P % 32 trailing columns fold in one lane.  Neither allocates nor
  * synchronises.  Not covered: host rows, the sharded step, stream capture, a
- * tuner kind, MXFP6, NVFP4.  MX output: fa_fedavg_mx_q below; every layer of a
- * model in one launch: fa_fedavg_mx_layers further below. */
+ * tuner kind, MXFP6.  MX output: fa_fedavg_mx_q below; every layer of a model
+ * in one launch: fa_fedavg_mx_layers further below; NVFP4 rows (block 16, e4m3
+ * scales): fa_fedavg_nvfp4 below. */
 #define FA_MX_E4M3 0
 #define FA_MX_E5M2 1
 #define FA_MX_E2M1 2
@@ -771,6 +772,46 @@ int fa_fedavg_mx(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t
 int fa_fedavg_mx_ptrs(int fmt, const uint8_t* const* xi, const uint8_t* const* ei, int64_t N, int64_t P,
                       const float* a, const float* s, const float* c, float divisor, int rows_aligned,
                       float* out_f32, uint16_t* out_bf16, void* stream);
+
+/* ---- NVFP4 client rows (new symbols, ABI still 7) -----------------------------
+ * e2m1 nibbles in MXFP4's layout (two columns per byte, the even column in the
+ * low nibble), one e4m3fn scale BYTE per FA_NVFP4_BLOCK = 16 flat elements (a
+ * last partial block is allowed: a scale row has ceil(P / 16) bytes), and one
+ * float32 scale per tensor, which is the per-client scale c.  Folded from the
+ * bytes themselves.  Per client i and column p (a, s, c as fa_fedavg_mx):
+ *   x   = f32(q_i[p])                         exact
+ *   x   = fl32(x * f32_e4m3fn(e_i[p >> 4]))   the byte decoded literally: sign
+ *                                             bit honoured, subnormals, +-0,
+ *                                             0x7f / 0xff NaN; exact when finite
+ *   x   = fl32(x * c_i)                       only with c
+ *   t   = fl32(x * a_i);  t = fl32(t * s_i) with s
+ *   acc = t_0;  acc = fl32(acc + t_i) in client order, no FMA
+ *   out = fl32(acc / divisor)
+ * -- bit for bit fa_fedavg_f32 over the dequantised rows; no factor is merged
+ * with another.  The arguments, checks and status codes of fa_fedavg_mx /
+ * fa_fedavg_mx_ptrs without fmt: ldx >= P / 2, lde >= ceil(P / 16), no output
+ * inside X or E, an odd P -> FA_ERR_ARG.
+ * Geometry: a lane owns 32 columns = TWO blocks (32 float32 accumulators); per
+ * row one 16-byte load of codes and ONE 16-BIT load of its two scale bytes, so
+ * the vector path needs, beyond fa_fedavg_mx's conditions (X and the outputs
+ * 16-B aligned, ldx % 16 == 0), scale rows that are 2-B aligned: E % 2 == 0 and
+ * lde % 2 == 0; for fa_fedavg_nvfp4_ptrs rows_aligned != 0 promises 16-B
+ * aligned code rows and 2-B aligned scale rows.  Anything else folds one
+ * column per lane, with the same bits.  Tiles of FA_MX_TILE_COLS columns over
+ * at most two blocks per CU, FA_NVFP4_ROWS_AHEAD rows (codes and scale pair)
+ * loaded while the previous group folds, the MX fold's LDS exchange of the
+ * results; the P % 32 trailing columns fold in one lane, each with scale byte
+ * p >> 4, so no byte past a scale row's ceil(P / 16) is read.  Neither entry
+ * allocates nor synchronises.  Not covered: an NVFP4 or MX result, a layer
+ * table, host rows, the sharded step, stream capture, a tuner kind. */
+#define FA_NVFP4_BLOCK 16
+#define FA_NVFP4_ROWS_AHEAD 16
+int fa_fedavg_nvfp4(const uint8_t* X, const uint8_t* E, int64_t N, int64_t P,
+                    int64_t ldx, int64_t lde, const float* a, const float* s, const float* c, float divisor,
+                    float* out_f32, uint16_t* out_bf16, void* stream);
+int fa_fedavg_nvfp4_ptrs(const uint8_t* const* xi, const uint8_t* const* ei, int64_t N, int64_t P,
+                         const float* a, const float* s, const float* c, float divisor, int rows_aligned,
+                         float* out_f32, uint16_t* out_bf16, void* stream);
 
 /* ---- MX output of the MX and fp8 folds (new symbols, ABI still 7) -------------
  * The folds above with their result quantised to MX in the same launch: the
@@ -806,7 +847,8 @@ int fa_fedavg_mx_ptrs(int fmt, const uint8_t* const* xi, const uint8_t* const* e
  * Neither entry allocates nor synchronises.  Not covered: MX output of the
  * float32 / bf16 / float16 / float64 folds, fp8 output with a per-tensor scale,
  * the layer tables of the fp8 sources, the sharded step, stream capture, MXFP6,
- * NVFP4, stochastic rounding. */
+ * MX output of NVFP4 rows, an NVFP4 result (it needs a per-tensor amax pass),
+ * stochastic rounding. */
 int fa_fedavg_mx_q(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P,
                    int64_t ldx, int64_t lde, const float* a, const float* s, const float* c, float divisor,
                    float* out_f32, int out_fmt, uint8_t* out_q, uint8_t* out_e, void* stream);

@@ -128,6 +128,15 @@ int fa_fedavg_fp8_form(const uint8_t* X, int64_t N, int64_t P, int64_t ldx, cons
 int fa_fedavg_mx_form(int fmt, const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
                       const float* a, const float* s, const float* c, float divisor, float* out_f32,
                       uint16_t* out_bf16, void* stream, int form, int blocks_per_cu);
+/* The vector path of fa_fedavg_nvfp4 in one form of the unit fold over a grid
+ * of blocks_per_cu (>= 1) blocks per CU, balanced passes: form bit 0 = the next
+ * row group's loads issued ahead of this group's adds, bit 1 = float32 results
+ * exchanged through LDS.  Forms 1, 2 and 3 (the product's).  X and the outputs
+ * 16-B aligned, ldx % 16 == 0, E and lde even, else FA_ERR_ARG; the other
+ * checks as fa_fedavg_nvfp4.  tools/nvfp4_bench.py --forms. */
+int fa_fedavg_nvfp4_form(const uint8_t* X, const uint8_t* E, int64_t N, int64_t P, int64_t ldx, int64_t lde,
+                         const float* a, const float* s, const float* c, float divisor, float* out_f32,
+                         uint16_t* out_bf16, void* stream, int form, int blocks_per_cu);
 /* The vector path of fa_fedavg_mx_q (FedAvg, no per-client scales) in one form
  * of the quantising epilogue: bit 0 = a full wave's fp8 codes exchanged
  * through LDS (1 KiB contiguous per store instruction; nothing for an e2m1
